@@ -19,7 +19,7 @@ the ciphertexts produced into HBM (one window's block per instance, overwritten 
 HBM).  Instance 0 of rank 0 carries the fixture's seed: once a whole pass has run its output label is compared with the fixture
 (`headline_output_label_match`: the very kernel instantiation that is timed).
 
-Beside it, measured in the same run on rank 0 (N = 1):
+Beside it, with `--full`, measured in the same run on rank 0 (N = 1):
   e2e_with_commitment   ONE WHOLE PASS of `--e2e-instances` instances with every ciphertext copied out over PCIe and folded into its
                         instance's CBC-MAC (src/ciphertext_hasher.rs:23-29) — what the reference's timed garble does
                         (examples/groth16_garble.rs:111-129).  Instance 0 carries the fixture's seed: its final MAC and output label
@@ -33,6 +33,12 @@ Beside it, measured in the same run on rank 0 (N = 1):
 
 `--workload cc16` is BASELINE config 5: 16 cut-and-choose instances from one master seed, instance i -> rank i mod N, garbled with
 the ciphertext commitments, one all-gather of the GarbledInstanceCommit records.
+
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps, writes `--dump-outputs DIR` if asked and prints the
+result line.  Everything under "Beside it" above, the check of the timed configuration's ciphertexts, the AES ceiling measured on this
+machine and the fixture checks of the other workloads run with `--full` only (legs that would not end within `--extras-budget` seconds
+of process start are skipped and say so).  The headline plan's file (~50 s of host CPU to build) is loaded from the plan cache when
+__graft_entry__.build() or an earlier run left it there.
 
 `--gpus N` without a launcher spawns the N ranks itself (python -m torch.distributed.run) before anything touches a GPU.
 """
@@ -66,7 +72,13 @@ def run_verifier(args):
     case = json.load(open(os.path.join(ROOT, "tests", "golden", FIXTURE[args.workload])))
     units = (SMALL_BATCH_UNITS if args.units == "fq6" else VERIFIER_UNITS) + (["fp254::exp_chunk"] if compressed else [])
     engine = gsv.Engine(local_rank)  # raises without a HIP device: no CPU fallback
-    extras = rank == 0 and world == 1
+    extras = args.full and rank == 0 and world == 1  # every leg beside the timed steps belongs to `--full`
+
+    def fits(seconds):
+        """--full: does a leg of about `seconds` still end inside --extras-budget (counted from process start)?  The callers pass what
+        the leg took on one MI355X (profiles/r06_final/bench_driver_command_run2_warm_plan_cache.err) plus a few seconds of set-up; a leg
+        that does not fit is left out and the later, shorter ones are still tried."""
+        return time.time() - T_START + seconds < args.extras_budget
     want_small = extras and compressed and args.small_batch_units == "fq6" and args.units == "fq12" and not (args.no_rate_by_instances and args.no_cc16 and args.no_mode_rates)
     # The small-batch plan's FILE is built in the background, BEHIND the timed steps (round 6; round 5 built it beside the headline plan: two
     # CPU-bound builds on a 16-core quota, 86 s each instead of 50 s); it is loaded when the legs that follow the timed steps need it.  Only the
@@ -155,9 +167,9 @@ def run_verifier(args):
         work.sess.sync()
 
     t_first_launch = time.time() - T_START
-    r = timed_steps(work, slices, args.warmup, args.steps, dist, sync, args.time_budget, T_START)
-    # (the T-table ceiling of this box: a child process of a few seconds, behind the timed steps since round 6)
-    aes_and_per_s, aes_src = measure_aes_ceiling(log) if rank == 0 else (AES_CEILING_AND_PER_S_R02, "not measured on this rank")
+    r = timed_steps(work, slices, args.warmup, args.steps, dist, sync)  # --steps is the number of timed steps: nothing shortens it
+    # (the T-table ceiling of this box: a child process of a few seconds, behind the timed steps since round 6; a run of its own: --full)
+    aes_and_per_s, aes_src = measure_aes_ceiling(log) if rank == 0 and args.full else (AES_CEILING_AND_PER_S_R02, "round-2 constant: not measured on this rank" if rank else "round-2 constant: measured in this run with --full")
     label_match = None
     if rank == 0 and (args.warmup + r["steps_run"]) >= len(slices) and r["commit_table"] is not None:
         # the last completed pass's output label of instance 0 (fixture seed), as gathered in its commit record: commit(label0) of output 0
@@ -166,12 +178,34 @@ def run_verifier(args):
         _, _, _, outc, _, _ = sharding.record_fields(rec, plan.info["n_outputs"], n_in)
         exp = sharding.commit_labels(np.frombuffer(bytes.fromhex(case["first_output_label0"]), np.uint8)[None, :])[0]
         label_match = bool((outc[0, 1] == exp).all())
+    if args.dump_outputs and rank == 0:
+        # What the timed path computed, as a caller can observe it.  Seeds are fixed by rank and index: the same arguments give the same
+        # arrays in every run and every build.
+        done = args.warmup + r["steps_run"]
+        k = done % len(slices)
+        if done and k == 0 and r["commit_table"] is not None:
+            # the last timed step ended a pass: the session has gathered its output labels and timed_steps returned the commit records
+            table = np.asarray(r["commit_table"][:B])
+            dump_outputs(args.dump_outputs, {"output_label0": work.sess.read_outputs(), "commit_records_sample": table[sample_rows(B, 64)]})
+        else:
+            # the last timed step left the pass open and the session hands nothing out before a pass has ended (its wires and ciphertexts
+            # stay on the device).  The pass is continued by the next eight windows of its schedule (about a second) with the ciphertext
+            # streams of the first instances drained and CBC-MAC'ed: every ciphertext of those windows is a function of the labels the
+            # timed steps left in the wire file, so the MACs change with any of them.
+            if done == 0:
+                work.new_pass()
+            wins = [w for w in work_windows if w[0] >= slices[k][0]][:8]
+            n_chk = min(B, 64)
+            work.sess.set_drain_instances(n_chk)
+            macs = work.sess.garble_calls(wins[0][0], sum(w[1] for w in wins))
+            work.sess.set_drain_instances(0)
+            dump_outputs(args.dump_outputs, {"next_windows_ciphertext_mac": np.frombuffer(b"".join(macs[:n_chk]), np.uint8).reshape(n_chk, 16)})
     # ---- the timed configuration's ciphertexts (examples/groth16_garble.rs:255-263 compares the garbler's and the evaluator's ciphertext
     # hash): ONE MORE whole pass of the very session that was timed — same instances, same kernel instantiation, same windows — with the
     # streams of its first instances drained and CBC-MAC'ed (gsv_session_set_drain_instances: every instance is garbled, 8 x 47.7 GB cross
     # PCIe instead of 1 024 x), against the oracle's flat-stream fixtures.  Outside the timed region.
     head_ct = None
-    if rank == 0 and world == 1 and not args.no_headline_ct_check and time.time() - T_START < args.time_budget + 60:
+    if extras and not args.no_headline_ct_check and fits(120):
         try:
             n_chk = min(8, B) if head_gold is not None else 1
             work.sess.set_drain_instances(n_chk)
@@ -208,7 +242,7 @@ def run_verifier(args):
             plan_small, plan_small_info = None, {"error": repr(e)}
     plan_sb = plan_small or plan
     # ---- CPU baseline: the restated per-gate loop on a prefix of the very stream the GPU garbles (rank 0 at N = 1 only)
-    if extras and not args.no_cpu_baseline:
+    if extras and not args.no_cpu_baseline and fits(60):
         try:
             import oracle_lib as o
             result["cpu_baseline"] = cpu_baseline(o, case["circuit"], case["seed"], log)
@@ -219,7 +253,7 @@ def run_verifier(args):
     # ---- ONE WHOLE PASS with the commitment: every ciphertext of every instance drained over PCIe and folded into its CBC-MAC while the
     # GPU garbles the next window (the like-for-like of the reference's timed garble, examples/groth16_garble.rs:111-129).  Instance 0
     # carries the fixture's seed: its MAC over the whole stream and its output label are this run's ciphertext-hash check.
-    if extras and not args.no_e2e:
+    if extras and not args.no_e2e and fits(70):
         try:
             Be = max(1, args.e2e_instances)
             seeds = [case["seed"]] + instance_seeds(rank, Be)[1:]
@@ -282,7 +316,7 @@ def run_verifier(args):
         rbi = {}
         try:
             for Bi, whole in ((1, True), (16, True), (256, False)):
-                if time.time() - T_START > args.extras_budget - 500:
+                if not fits({1: 35, 16: 40, 256: 25}[Bi]):
                     rbi[str(Bi)] = {"skipped": "time budget"}
                     continue
                 # sixteen instances: the session as a ciphertext RING (gsv_plan_session_opts.retain_stream = GSV_STREAM_RING) — the whole pass one
@@ -312,14 +346,14 @@ def run_verifier(args):
                     log("bench.py: %d instance(s): %.3g gates/s" % (Bi, g * Bi / dt))
                     if Bi == 16:
                         rbi["16"]["ciphertext_ring_records"] = si["ct_ring_records"]
-                        if time.time() - T_START < args.extras_budget - 450:
+                        if fits(40):
                             w.close()
                             w = VerifierWork(gsv, engine, plan_sb, Bi, [case["seed"]] + instance_seeds(rank, Bi)[1:])
                             dtw, siw = w.run_pass(), w.sess.schedule_info()
                             rbi["16"]["default_windows"] = {"gates_per_s": gates * Bi / dtw, "seconds": dtw, "windows": siw["n_windows"], "depth_steps": siw["critical_steps"],
                                                             "output_label_match": hashlib.sha256(w.sess.read_outputs()[0].tobytes()).hexdigest() == case["output_label0_sha256"]}
                             log("bench.py: 16 instances in default windows: %.3g gates/s" % (gates * Bi / dtw))
-                    if Bi == 1 and time.time() - T_START < args.extras_budget - 400:
+                    if Bi == 1 and fits(40):
                         # BASELINE's single-instance target is stated WITH the ciphertext hash: the same pass again, the stream drained and
                         # folded into ONE serial CBC-MAC chain on one host core (the chain, ~1.1e8 blocks/s = 27 s, is nearly as long as the
                         # garbling).  The session's default: two launch windows (the scope in which the instance's call chains overlap), the
@@ -342,7 +376,7 @@ def run_verifier(args):
             rbi["error"] = repr(e)
         result["rate_by_instances"] = rbi
     # ---- BASELINE config 5 at its real size on this one GPU, all 16 commit records against the oracle-built fixture
-    if extras and not args.no_cc16 and compressed and time.time() - T_START < args.extras_budget - 150:
+    if extras and not args.no_cc16 and compressed and fits(50):
         try:
             gold16 = cc16_verifier_fixture(case)
             result["cc16_one_gpu"] = cc16_one_gpu(gsv, engine, plan_sb, case, gold16, log) if gold16 is not None else {"skipped": "no cc16 fixture for this circuit"}
@@ -350,14 +384,14 @@ def run_verifier(args):
                 result["cc16_one_gpu"]["plan_units"] = "fq6 (small-batch plan)" if plan_small is not None else "fq12"
         except Exception as e:  # noqa: BLE001
             result["cc16_one_gpu"] = {"error": repr(e)}
-    if extras and not args.no_mode_rates:
+    if extras and not args.no_mode_rates and fits(15):
         try:
             result["mode_rates"] = mode_rates(gsv, engine, np)
         except Exception as e:  # noqa: BLE001
             result["mode_rates"] = {"error": repr(e)}
         # the second phase of the reference's benchmark (examples/groth16_garble.rs:171-230): ONE instance garbled and — window by window, from
         # the garbler's device block, nothing retained, nothing over PCIe — evaluated at the same time with the valid proof's input bits
-        if compressed and "input_bits_hex" in case and time.time() - T_START < args.extras_budget - 60:
+        if compressed and "input_bits_hex" in case and fits(50):
             try:
                 result["mode_rates"]["garble_then_evaluate"] = garble_then_evaluate(gsv, engine, plan_sb, case, np)
                 log("bench.py: garble + evaluate side by side, one instance: %.1f s, decoded output %s" % (result["mode_rates"]["garble_then_evaluate"]["seconds"], result["mode_rates"]["garble_then_evaluate"]["decoded_output"]))
@@ -509,11 +543,13 @@ def run_cc16(args):
     engine = gsv.Engine(local_rank)
     gold = json.load(open(os.path.join(ROOT, "tests", "golden", "cc16_golden.json")))
     total = gold["total"]
-    # shortened circuit: every record against the fixture
-    prog = gsv.Program.from_circuit(gold["circuit"])
-    table, seeds = sharding.cut_and_choose_commit(gold["circuit"], gold["master_seed"], total, rank, world, engine=engine, program=prog, device="cuda" if world > 1 else None)
-    short_ok = bool(hashlib.sha256(table.tobytes()).hexdigest() == gold["table_sha256"] and [int(x) for x in seeds] == gold["seeds"])
-    prog.close()
+    short_ok, short_sha = None, None
+    if args.full:  # shortened circuit: every record against the fixture (all ranks take part in its all-gather)
+        prog = gsv.Program.from_circuit(gold["circuit"])
+        table, seeds = sharding.cut_and_choose_commit(gold["circuit"], gold["master_seed"], total, rank, world, engine=engine, program=prog, device="cuda" if world > 1 else None)
+        short_sha = hashlib.sha256(table.tobytes()).hexdigest()
+        short_ok = bool(short_sha == gold["table_sha256"] and [int(x) for x in seeds] == gold["seeds"])
+        prog.close()
     case = json.load(open(os.path.join(ROOT, "tests", "golden", FIXTURE["verifier_compressed"])))
     # at most 16 instances per GPU = one per workgroup: the small-batch plan (Fq6-level units, full LDS window), as in cc16_one_gpu
     units = (SMALL_BATCH_UNITS if args.small_batch_units == "fq6" else VERIFIER_UNITS) + ["fp254::exp_chunk"]
@@ -533,11 +569,11 @@ def run_cc16(args):
     if rank == 0:
         el = sum(times)
         ct = [bytes(tab[i][8:24]).hex() for i in range(total)]
-        # the gathered table of the FULL verifier against the oracle's 16 flat garblings (tests/golden/cc16_verifier_golden.json)
+        # --full: the gathered table of the FULL verifier against the oracle's 16 flat garblings (tests/golden/cc16_verifier_golden.json)
         full = None
         try:
             vg = json.load(open(os.path.join(ROOT, "tests", "golden", "cc16_verifier_golden.json")))
-            if vg["master_seed"] == gold["master_seed"] and vg["total"] == total:
+            if args.full and vg["master_seed"] == gold["master_seed"] and vg["total"] == total:
                 t_np = tab.cpu().numpy() if hasattr(tab, "cpu") else np.asarray(tab)
                 rec_ok = [hashlib.sha256(np.ascontiguousarray(t_np[i]).tobytes()).hexdigest() == vg["record_sha256"][i] for i in range(total)]
                 full = {"records_matching": int(sum(rec_ok)), "all_16_match": bool(all(rec_ok)), "fixture": "tests/golden/cc16_verifier_golden.json"}
@@ -552,7 +588,9 @@ def run_cc16(args):
                              "instances_total": total, "instances_per_gpu": len(sharding.shard_instances(total, rank, world)), "gates_per_instance": gates, "plan": plan_info,
                              "reference_published": "16 instances on 8 physical cores: ~11 m 58 s, ~249 M gates/s (README.md:13)"},
                   "commit_records_gathered": list(tab.shape), "distinct_ciphertext_commitments": len(set(ct)), "full_verifier_records_vs_oracle": full,
-                  "shortened_circuit_check": {"circuit": gold["circuit"], "table_sha256": hashlib.sha256(table.tobytes()).hexdigest(), "fixture": gold["table_sha256"], "match": short_ok}}
+                  "shortened_circuit_check": {"circuit": gold["circuit"], "table_sha256": short_sha, "fixture": gold["table_sha256"], "match": short_ok}}
+        if args.dump_outputs:  # the gathered table of the last timed job: one GarbledInstanceCommit record per instance
+            dump_outputs(args.dump_outputs, {"commit_records": tab})
         print(json.dumps(result), flush=True)
         if save_later:
             try:
@@ -605,13 +643,13 @@ def run_synthetic(args):
 
     def sync():
         torch.cuda.synchronize(); sess.sync()
-    r = timed_steps(Work(), [(0, 1, gpr * replays)], args.warmup, args.steps, dist, sync, args.time_budget, T_START)
+    r = timed_steps(Work(), [(0, 1, gpr * replays)], args.warmup, args.steps, dist, sync)
     if rank == 0:
         el, K = r["elapsed"], r["steps_run"]
         stream_s = sum(r["step_ms"]) / 1e3
         g_rank = r["gates_per_instance"] * B
         achieved = g_rank * bytes_per_gate / stream_s / 1e9
-        aes_and_per_s, aes_src = measure_aes_ceiling(lambda m: print(m, file=sys.stderr))
+        aes_and_per_s, aes_src = measure_aes_ceiling(lambda m: print(m, file=sys.stderr)) if args.full else (AES_CEILING_AND_PER_S_R02, "round-2 constant: measured in this run with --full")
         result = {"metric": "gates/sec (garble) on Groth16/BN254 verifier at 1/2/4/8 GPUs; ciphertext-hash match", "value": g_rank * world / el, "unit": "gates/s", "n_gpus": world,
                   "steps": K, "warmup": args.warmup, "ms_per_step": el / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
                   "config": {"workload": "Groth16-shaped SYNTHETIC: chain of %d %s links = %d gates per instance; %d cut-and-choose instances per GPU" % (replays, args.component, gpr * replays, B),
@@ -620,14 +658,16 @@ def run_synthetic(args):
                                "kernel": "run_program_kernel<false, %d, 0, %s>" % (ni, "true" if prog.info.get("and_terms", 2) == 4 else "false"), "kernel_ms_avg": stream_s * 1e3 / K, "bytes_per_gate": bytes_per_gate,
                                "algorithmic_bytes_per_launch": g_rank / K * bytes_per_gate, "binding_limit": "aes-issue",
                                "aes_ceiling_gates_per_s": aes_and_per_s / f_nf, "aes_ceiling_frac": (g_rank / stream_s) / (aes_and_per_s / f_nf), "aes_ceiling_source": aes_src}}
-        if not args.no_check:
+        if args.dump_outputs:  # the chain's output labels after the last timed step, every instance
+            dump_outputs(args.dump_outputs, {"output_label0": sess.read_outputs()})
+        if args.full and not args.no_check:
             import oracle_lib as o
             os.environ["GSV_INSTANCES_PER_WG"] = str(ni)
             chk = gsv.CircuitBuilder.streaming_garbling(args.component, [seeds[1], seeds[0], seeds[2]], engine=engine, program=prog, replays=2, keep_ciphertexts=False)
             del os.environ["GSV_INSTANCES_PER_WG"]
             ref = o.garble(args.component + "_chain:2", seeds[0], capture_ct=False)
             result["ciphertext_hash_match"] = bool(chk.ciphertext_hash[1] == ref.ct_hash.tobytes() and (chk.output_label0[1] == ref.output_label0).all())
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             import oracle_lib as o
             result["cpu_baseline"] = cpu_baseline(o, args.component + "_chain:16", seeds[0], lambda m: None)
         print(json.dumps(result), flush=True)
@@ -649,9 +689,13 @@ def main():
                     help="verifier_compressed (default): the restated groth16_verify_compressed circuit with ONE public input (the reference's benchmark configuration) as a plan of component "
                          "programs; verifier_compressed_2pub / verifier: round-2 fixtures (two public inputs, with / without point decompression); cc16: BASELINE config 5 (16 instances from one "
                          "master seed over the ranks, commitments, one all-gather); synthetic: the Groth16-shaped chain")
-    ap.add_argument("--time-budget", type=float, default=840.0, help="seconds from process start within which the timed steps must end; steps are reduced (and reported) if they would not fit")
-    ap.add_argument("--extras-budget", type=float, default=1350.0, help="seconds from process start within which the legs BEHIND the timed steps (CPU baseline, whole passes with commitments at 64 / 1 / 16 "
-                    "instances, cc16 on one GPU, garble || evaluate) must end: a leg that would not fit is skipped and reported as such (the driver stops the run at 1 800 s)")
+    ap.add_argument("--full", action="store_true", help="beside the timed steps, measure and check everything else this benchmark knows: the timed configuration's ciphertexts against the "
+                    "oracle's MACs, the CPU baseline, whole passes with commitments at 64 / 1 / 16 instances, cc16 on one GPU, evaluate / Blake3 rates, garble || evaluate, the AES ceiling of "
+                    "this machine.  Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the timed path computed as DIR/<name>.npy (float32): the output labels of every instance and a "
+                    "fixed sample of the commit records when the last timed step ended a pass; otherwise the CBC-MACs of the ciphertexts of the next eight windows of the open pass, first 64 instances")
+    ap.add_argument("--extras-budget", type=float, default=540.0, help="--full: seconds from process start within which the legs BEHIND the timed steps (ciphertext check, CPU baseline, whole passes with "
+                    "commitments at 64 / 1 / 16 instances, cc16 on one GPU, garble || evaluate) must end: a leg that would not fit is skipped and reported as such, so that the run ends within ten minutes")
     ap.add_argument("--plan-cache", default=None, help="directory of the plan file shared by the ranks of a node (default: $GSV_PLAN_CACHE, /dev/shm, /tmp)")
     ap.add_argument("--no-plan-cache", action="store_true")
     ap.add_argument("--no-check", action="store_true")

@@ -240,6 +240,61 @@ class VerifierWork:
         self.sess.close()
 
 
+def prebuild_headline_plan(log=None):
+    """Called by __graft_entry__.build(): on a machine WITH a HIP device, build the plan file of bench.py's default workload (Fq12-level
+    units, window_div 4: ~50 s of host CPU, 41.8 GB) into the plan cache unless it is there, so that a `bench.py` process loads it in
+    seconds instead of building it in front of its first step.  The builder needs no device; a machine without one has no use for the
+    file.  The cache is what bench.py itself has always used ($GSV_PLAN_CACHE, else a directory of this user's in /dev/shm, else /tmp):
+    memory first — a disk that tests write their ciphertext files to is no place for 42 GB.  A plan file is keyed by the engine library,
+    so the files earlier builds left in this user's /dev/shm or /tmp directory are removed first.
+    Returns the file's path, or None when nothing was (or had to be) built.  Never fatal: bench.py builds what it does not find."""
+    log = log or (lambda m: print(m, file=sys.stderr, flush=True))
+    try:
+        import torch
+        if not torch.cuda.is_available():
+            return None
+        import garbled_snark_verifier_amd as gsv
+        case = json.load(open(os.path.join(ROOT, "tests", "golden", FIXTURE["verifier_compressed"])))
+        units = VERIFIER_UNITS + ["fp254::exp_chunk"]
+        path = _plan_cache_path(argparse.Namespace(no_plan_cache=False, plan_cache=None), case["circuit"], units, 4)
+        if not path or os.path.exists(path):
+            return None
+        own = os.path.dirname(path)
+        if os.path.basename(own) == "gsv_plan_cache_%d" % os.getuid():
+            for f in os.listdir(own):
+                if f.startswith("plan_") and f.endswith(".gsvplan"):
+                    os.remove(os.path.join(own, f))
+        t0 = time.time()
+        try:
+            gsv.Plan.build_file(case["circuit"], units, path, window_div=4)
+        except BaseException:
+            if os.path.exists(path):
+                os.remove(path)  # never leave half a file where bench.py would load it
+            raise
+        log("bench_support: headline plan file built in %.1f s: %s" % (time.time() - t0, path))
+        return path
+    except Exception as e:  # noqa: BLE001
+        log("bench_support: headline plan file not prebuilt (%r): bench.py will build it" % (e,))
+        return None
+
+
+def sample_rows(n, k, seed=20240607):
+    """A fixed, seeded sample of min(n, k) of the rows 0..n-1, ascending: the same rows in every run and every build."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(directory, arrays):
+    """`--dump-outputs DIR`: every array of {name: array} as DIR/<name>.npy in float32 (bytes and labels are exact in it)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32))
+
+
 def _plan_cache_path(args, circuit, units, window_div=4):
     if args.no_plan_cache:
         return None

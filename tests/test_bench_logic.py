@@ -255,3 +255,23 @@ def test_bench_reexports_its_support_module():
                  "VERIFIER_UNITS", "SMALL_BATCH_UNITS", "FIXTURE", "garble_then_evaluate", "cc16_one_gpu", "measure_aes_ceiling", "_plan_cache_path", "T_START"):
         assert getattr(bench, name) is getattr(bench_support, name), name
     assert all(hasattr(bench, f) for f in ("run_verifier", "run_cc16", "run_synthetic", "main"))
+
+
+def test_dump_outputs_are_exact_and_the_sample_is_fixed(tmp_path):
+    """`--dump-outputs DIR`: bytes as exact float32 arrays, float64 kept, and the sampled rows the same in every run."""
+    import numpy as np
+    import bench
+    a = np.arange(256, dtype=np.uint8).reshape(16, 16)
+    bench.dump_outputs(str(tmp_path / "out"), {"labels": a, "times": np.array([1.5, 2.5])})
+    b = np.load(str(tmp_path / "out" / "labels.npy"))
+    assert b.dtype == np.float32 and (b == a).all() and np.load(str(tmp_path / "out" / "times.npy")).dtype == np.float64
+    rows = bench.sample_rows(1024, 64)
+    assert len(rows) == 64 and (np.diff(rows) > 0).all() and (rows == bench.sample_rows(1024, 64)).all() and (bench.sample_rows(5, 64) == np.arange(5)).all()
+
+
+def test_a_plain_run_and_a_full_run_are_told_apart():
+    """`--full` and `--dump-outputs` are options of bench.py; everything beside the timed steps is keyed to `--full`."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert "extras = args.full and rank == 0 and world == 1" in src

@@ -4,18 +4,16 @@
     C type by C type), and the `#[repr(C)]` structs have the C structs' fields in the C order;
   * every `ffi::gsv_*` the mode files call is declared in gpu_ffi.rs;
   * streaming_mode_unit_hook.patch applies, hunk by hunk, to the reference's own src/circuit/{component_key,modes,streaming_mode,mod}.rs
-    (copies in a scratch directory; skipped where /root/reference does not exist) and the patched files hold the names the shim uses.
+    (by the recorded hashes of the lines each hunk replaces: tests/golden/unit_hook_patch_golden.json) and the patched files hold the names
+    the shim uses.
 The call sequence itself is compiled and run as tests/ext_host/ext_host.cpp (tests/test_ext_host.py)."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RUST = os.path.join(ROOT, "bindings", "rust")
-REF = "/root/reference"
 
 # C parameter type (whitespace-normalised, parameter name stripped) -> Rust type in gpu_ffi.rs
 C2RUST = {
@@ -120,17 +118,53 @@ def test_mode_files_call_only_declared_functions():
         assert used and used <= declared, (f, used - declared)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src", "circuit")) or shutil.which("patch") is None, reason="the reference tree (or patch) is not on this machine")
+def patch_hunks():
+    """streaming_mode_unit_hook.patch as {file: [(old_start, old_len, pre-image lines, post-image lines)]}."""
+    out, cur, hunk = {}, None, None
+    for line in open(os.path.join(RUST, "streaming_mode_unit_hook.patch")).read().split("\n"):
+        if line.startswith("#") or line.startswith("--- "):
+            continue
+        if line.startswith("+++ "):
+            cur = out.setdefault(line[4:].strip().split("/", 1)[1], [])
+            continue
+        m = re.match(r"@@ -(\d+),(\d+) \+\d+,(\d+) @@", line)
+        if m:
+            hunk = (int(m.group(1)), int(m.group(2)), [], [], int(m.group(3)))
+            cur.append(hunk)
+        elif hunk is not None and (len(hunk[2]) < hunk[1] or len(hunk[3]) < hunk[4]):
+            if line[:1] in (" ", ""):
+                hunk[2].append(line[1:]); hunk[3].append(line[1:])
+            elif line[0] == "-":
+                hunk[2].append(line[1:])
+            else:
+                assert line[0] == "+", line
+                hunk[3].append(line[1:])
+    return {f: [h[:4] for h in hs] for f, hs in out.items()}
+
+
 def test_unit_hook_patch_applies_to_the_reference_sources(tmp_path):
-    """Copies of the four files the patch touches, patched in a scratch directory: every hunk applies, nothing is rejected."""
+    """Every hunk applies to the reference's own files at the line it names, without offset or fuzz, and nothing is rejected.  The
+    reference's files are not in this repository: tests/golden/unit_hook_patch_golden.json records, for each hunk, the sha256 of the
+    lines of the reference's file that the hunk replaces (tests/golden/make_unit_hook_patch_golden.py wrote it from a checkout of the
+    reference) — a hunk applies exactly when its own pre-image (context and removed lines) has that hash.  The patched files are then
+    built from the pre-images (every line outside a hunk blank) and must hold the names the shim uses."""
+    import hashlib
+    import json
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "unit_hook_patch_golden.json")))
+    hunks = patch_hunks()
+    assert sorted(hunks) == sorted(gold["files"]) == sorted("src/circuit/" + f for f in ("component_key.rs", "modes.rs", "streaming_mode.rs", "mod.rs"))
     dst = tmp_path / "src" / "circuit"
     dst.mkdir(parents=True)
-    for f in ("component_key.rs", "modes.rs", "streaming_mode.rs", "mod.rs"):
-        shutil.copy(os.path.join(REF, "src", "circuit", f), dst / f)
-    with open(os.path.join(RUST, "streaming_mode_unit_hook.patch")) as fh:
-        r = subprocess.run(["patch", "-p1", "--no-backup-if-mismatch", "-d", str(tmp_path)], stdin=fh, capture_output=True, text=True)
-    assert r.returncode == 0 and "FAILED" not in r.stdout and "fuzz" not in r.stdout, r.stdout + r.stderr
-    assert not list(tmp_path.rglob("*.rej"))
+    for f, hs in hunks.items():
+        g = gold["files"][f]
+        assert [(h[0], h[1]) for h in hs] == [(x["old_start"], x["old_len"]) for x in g["hunks"]], f
+        lines, shift = [""] * g["n_lines"], 0
+        for (start, n, pre, post), x in zip(hs, g["hunks"]):
+            assert len(pre) == n and start - 1 + n <= g["n_lines"], (f, start)
+            assert hashlib.sha256("\n".join(pre).encode()).hexdigest() == x["sha256"], "%s: the hunk at line %d does not match the reference's lines" % (f, start)
+            lines[start - 1 + shift:start - 1 + shift + n] = post
+            shift += len(post) - n
+        (dst / os.path.basename(f)).write_text("\n".join(lines) + "\n")
     modes = (dst / "modes.rs").read_text()
     for name in ("fn execution_finished", "fn unit_begin", "fn unit_end", "fn unit_call", "pub mod gpu_garble_mode", "pub mod gpu_evaluate_mode", "pub use gpu_recorder::UnitAction"):
         assert name in modes, name
