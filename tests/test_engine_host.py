@@ -357,6 +357,37 @@ def test_warmup_recorders_give_the_same_plan(monkeypatch):
     assert (ref.ciphertexts == cts).all() and (ref.output_label0 == out).all() and h.cbcmac(cts) == ref.ct_hash.tobytes()
 
 
+def test_oracle_prefix_mac_equals_the_stream_before_every_call_boundary():
+    """oracle_lib.bench_garble_prefix(circuit, N) stops in front of gate N of the flat stream and returns the CBC-MAC state reached:
+    with N = a call's gate offset (Plan.call_info: gid_off, gates, ct_off, n_ct, n_steps) that is the MAC of the ciphertexts of the
+    calls before it — what Session.garble_calls returns after a slice that ends there (the GPU form:
+    test_gpu_parity.py::test_verifier_lockstep_two_instances_per_workgroup).  Checked on the host interpreter's stream of fq12_mix at
+    EVERY call boundary and at the end, and one gate to either side of a boundary whose neighbours are AND-family gates."""
+    import garbled_snark_verifier_amd as gsv
+    units = ["fq12::mul_montgomery", "fq12::square_montgomery"]
+    seed = 4
+    plan = gsv.Plan.from_circuit("fq12_mix", units)
+    ci = plan.call_info()
+    sp = h.SimPlan("fq12_mix", units)
+    assert sp.info["n_calls"] == len(ci) >= 4 and sp.info["n_gates"] == plan.info["n_gates"] == int(ci[-1, 0] + ci[-1, 1])
+    assert (ci[1:, 0] == ci[:-1, 0] + ci[:-1, 1]).all() and (ci[1:, 2] == ci[:-1, 2] + ci[:-1, 3]).all() and ci[0, 0] == 0 and ci[0, 2] == 0
+    labs = h.labels_from_seed(seed, 3 + sp.info["n_inputs"])
+    _, cts = sp.garble(labs[0], labs[1:3], labs[3:])
+    assert cts.shape[0] == sp.info["n_ct"] == int(ci[-1, 2] + ci[-1, 3])
+    for k in range(1, len(ci)):
+        _, gates, mac = o.bench_garble_prefix("fq12_mix", int(ci[k, 0]), seed)
+        assert gates == int(ci[k, 0]) and mac == h.cbcmac(cts[:int(ci[k, 2])]), "boundary in front of call %d" % k
+    _, gates, mac = o.bench_garble_prefix("fq12_mix", sp.info["n_gates"], seed)
+    assert gates == sp.info["n_gates"] and mac == h.cbcmac(cts) == o.garble("fq12_mix", seed, capture_ct=False).ct_hash.tobytes()
+    assert o.bench_garble_prefix("fq12_mix", 0, seed)[2] == bytes(16)
+    # the limit gate itself is NOT garbled: N + 1 adds at most one ciphertext, N - 1 drops at most one
+    k = len(ci) // 2
+    n, c = int(ci[k, 0]), int(ci[k, 2])
+    assert o.bench_garble_prefix("fq12_mix", n + 1, seed)[2] in (h.cbcmac(cts[:c]), h.cbcmac(cts[:c + 1]))
+    assert o.bench_garble_prefix("fq12_mix", n - 1, seed)[2] in (h.cbcmac(cts[:c]), h.cbcmac(cts[:c - 1]))
+    plan.close()
+
+
 @pytest.mark.skipif(os.environ.get("GSV_SLOW_TESTS") != "1", reason="slow (two Miller-loop plan builds, ~45 GB of host memory): set GSV_SLOW_TESTS=1")
 def test_warmup_recorders_give_the_same_miller_loop_plan(monkeypatch):
     """The case the warm-ups exist for: the Miller loop's 178 constant line functions (circuits.hpp add_ell_warmups) recorded by the

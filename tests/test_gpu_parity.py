@@ -1375,7 +1375,8 @@ def test_verifier_lockstep_two_instances_per_workgroup(engine, compressed_verifi
     """The bench's configuration on real verifier programs: 1024 instances, four per workgroup (the kernel instantiation
     run_program_kernel<false, 4, 0>, groups in lockstep on the LDS-only step barrier), then 512 instances, two per workgroup
     (<false, 2, 0>), all with the SAME seed, through the first slice of the plan with the ciphertexts drained: every instance
-    must produce the same CBC-MAC state, a second run the same again, and both layouts the same as one instance alone."""
+    must produce the same CBC-MAC state, a second run the same again, both layouts the same as one instance alone — and the same as
+    the CPU oracle's MAC state after the slice's gates of the flat stream (oracle_lib.bench_garble_prefix)."""
     import bench
     import garbled_snark_verifier_amd as gsv
     case, plan = compressed_verifier_plan
@@ -1396,6 +1397,10 @@ def test_verifier_lockstep_two_instances_per_workgroup(engine, compressed_verifi
             seen.append(hashes[0])
         sess.close()
     assert len(set(seen)) == 1
+    # ... and that MAC state is the CPU oracle's after the same gates of the FLAT stream: the slice starts the pass, so the calls before its end
+    # are the first sl[2] gates (tests/test_engine_host.py::test_oracle_prefix_mac_equals_the_stream_before_every_call_boundary)
+    assert first == 0 and sl[2] == int(ci[:n, 1].sum())
+    assert seen[0] == o.bench_garble_prefix(case["circuit"], sl[2], seed=7)[2], "four / two instances per workgroup: not the oracle's stream"
     # the same slice for ONE instance (one per workgroup, run_program_kernel<false, 1, 0>) gives the same stream
     one = gsv.Session(engine, plan, 1, retain_stream=False, concurrent_calls=1)
     one.set_garble_inputs(d[None], np.stack([f, t])[None], inp[None])
@@ -1408,6 +1413,93 @@ def test_verifier_lockstep_two_instances_per_workgroup(engine, compressed_verifi
     par.set_garble_inputs(d[None], np.stack([f, t])[None], inp[None])
     assert par.garble_calls(first, n)[0] == seen[0]
     par.close()
+
+
+@pytest.mark.parametrize("spec,n_seeds", [("fq_inverse", 3), ("g1_to_affine", 3), ("fq12_inverse", 3), ("fq_sqrt", 2)])
+def test_verifier_latency_bound_units_per_workgroup_layouts(engine, monkeypatch, spec, n_seeds):
+    """The timed configuration's own code against the oracle: the verifier's latency-bound parts — the Fq inversion, the
+    projective-to-affine conversion and the Fq12 inversion around it, the square root's exponentiation ladder — as plans of the TIMED
+    plan's units (conftest.VERIFIER_PLAN_UNITS, window_div 4: inverse::iteration_group, inverse::divide_chains, fp254::exp_chunk in the
+    four-wire record form, so the FW instantiations with the per-group step barrier, the rotated lane index and the four-lane AES form),
+    at one, two and four instances per workgroup.  Six instances (ragged at four per workgroup) with distinct seeds laid out so that
+    every seed sits at several workgroup positions; per instance the CBC-MAC of the retained stream, the output label0s and the gate /
+    ciphertext counts == the CPU oracle's flat stream, then the retained stream evaluated: bits == the oracle's, active labels ==
+    select(label0, bit).  The inversions' plans hold two-wire calls (glue) too, and the whole retained stream is ONE window: the two-wire
+    programs run in the FW kernel under the group barrier beside the four-wire ones (engine_plan_session.ipp: a window is launched FW as
+    soon as any call in it is four-wire).  A last pass at four per workgroup without the stream retained, eight calls in flight, windows
+    of half the stream: the dataflow between calls under the group barrier, MACs == the oracle's."""
+    from concurrent.futures import ThreadPoolExecutor
+    import bn254_ref as T
+    import garbled_snark_verifier_amd as gsv
+    from conftest import VERIFIER_PLAN_UNITS
+    B = 6
+    seeds = [3000 + 10 * len(spec) + k for k in range(n_seeds)]
+    seed_of = [0, 1, 2, 1, 2, 0] if n_seeds == 3 else [0, 1, 1, 0, 0, 1]
+    bits_of = [0, 1, 2, 2, 0, 1] if n_seeds == 3 else [0, 1, 0, 1, 0, 1]  # every instance its own (seed, input) pair
+    n_in, n_out = o.circuit_info(spec)
+    rng = np.random.default_rng(len(spec))
+    values = [int.from_bytes(rng.bytes(40), "little") % (T.P - 1) + 1 for _ in range(3)]
+    if spec == "fq_inverse":  # field elements in Montgomery form: the outputs are decoded below
+        in_bits = [o.int_to_bits(v * o.FQ_R % T.P, 254) for v in values]
+    else:
+        in_bits = [rng.integers(0, 2, n_in).astype(np.uint8) for _ in range(3)]
+    with ThreadPoolExecutor(max_workers=6) as pool:  # the oracle's runs (seconds each) beside the plan build
+        ref_f = [pool.submit(o.garble, spec, sd, capture_ct=False) for sd in seeds]
+        exe_f = [pool.submit(o.execute, spec, b) for b in in_bits[:max(bits_of) + 1]]
+        plan = gsv.Plan.from_circuit(spec, VERIFIER_PLAN_UNITS, window_div=4)
+        refs = [f.result() for f in ref_f]
+        exes = [f.result()[0] for f in exe_f]
+    forms = plan.call_record_forms()
+    assert forms.count(4) >= 1 and set(forms) <= {2, 4}
+    both = spec in ("fq12_inverse", "g1_to_affine")
+    assert not both or forms.count(2) >= 1
+    for ref in refs:
+        assert plan.info["n_gates"] == int(ref.gate_counts.sum()) and plan.info["n_ciphertexts"] == ref.n_ciphertexts and plan.info["n_inputs"] == n_in
+    labs = [gsv.labels_from_seed(sd, n_in) for sd in seeds]
+    delta = np.stack([labs[k][0] for k in seed_of]); consts = np.stack([np.stack([labs[k][1], labs[k][2]]) for k in seed_of]); inputs = np.stack([labs[k][3] for k in seed_of])
+    bits = np.stack([in_bits[k] for k in bits_of])
+    active = np.where(bits[:, :, None] == 1, inputs ^ delta[:, None, :], inputs)
+    consts_active = np.stack([consts[:, 0], consts[:, 1] ^ delta], axis=1)
+
+    def mixed_windows(sess):
+        return [w for w, (c0, n, _) in enumerate(sess.windows()) if len(set(forms[c0:c0 + n])) == 2]
+
+    for ni in (1, 2, 4):
+        monkeypatch.setenv("GSV_INSTANCES_PER_WG", str(ni))
+        sess = gsv.Session(engine, plan, B)  # the whole stream retained
+        assert sess.instances_per_workgroup == ni
+        mixed = mixed_windows(sess)
+        assert mixed or not both, "no window holds both record forms"
+        sess.set_garble_inputs(delta, consts, inputs)
+        sess.garble(0)
+        out = sess.read_outputs()
+        for i in range(B):
+            ref = refs[seed_of[i]]
+            assert sess.ciphertext_hash(i) == ref.ct_hash.tobytes(), "%s, %d per workgroup, instance %d: ciphertext stream differs" % (spec, ni, i)
+            assert (out[i] == ref.output_label0).all(), "%s, %d per workgroup, instance %d: output labels differ" % (spec, ni, i)
+        sess.set_evaluate_inputs(consts_active, active, bits)
+        sess.evaluate(0)
+        oa, ob = sess.read_outputs(with_bits=True)
+        for i in range(B):
+            assert (ob[i] == exes[bits_of[i]]).all(), "%s, %d per workgroup, instance %d: plaintext bits differ" % (spec, ni, i)
+            assert (oa[i] == np.where(ob[i][:, None] == 1, out[i] ^ delta[i][None, :], out[i])).all(), "%s, %d per workgroup, instance %d: active label != select(label0, bit)" % (spec, ni, i)
+            if spec == "fq_inverse":  # a plaintext check that does not pass through circuits.hpp
+                a, inv = o.bits_to_int(bits[i]) * T.RINV % T.P, o.bits_to_int(ob[i]) * T.RINV % T.P
+                assert a == values[bits_of[i]] and a * inv % T.P == 1
+        print("%s: %d calls, %d four-wire, %d two-wire; %d per workgroup: windows %s, mixed %s" % (spec, len(forms), forms.count(4), forms.count(2), ni, sess.windows(), mixed))
+        sess.close()
+    # four per workgroup, one window of the stream on the device at a time, up to eight independent calls side by side
+    sess = gsv.Session(engine, plan, B, retain_stream=False, concurrent_calls=8, window_ct_records=(plan.info["n_ciphertexts"] + 1) // 2)
+    assert sess.instances_per_workgroup == 4 and len(sess.windows()) >= 2
+    assert mixed_windows(sess) or not both
+    sess.set_garble_inputs(delta, consts, inputs)
+    hashes = sess.garble_streaming()
+    out = sess.read_outputs()
+    for i in range(B):
+        assert hashes[i] == refs[seed_of[i]].ct_hash.tobytes() and (out[i] == refs[seed_of[i]].output_label0).all(), "%s, not retained, instance %d" % (spec, i)
+    print("%s: not retained: windows %s, mixed %s" % (spec, sess.windows(), mixed_windows(sess)))
+    sess.close()
+    plan.close()
 
 
 @pytest.mark.slow  # (round 6: opt-in, `-m "gpu and slow"` — a whole pass at four instances per workgroup takes ~95 s however few workgroups run it (a workgroup's time is
