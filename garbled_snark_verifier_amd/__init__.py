@@ -98,6 +98,14 @@ class _PlanScheduleInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in _SCHED_FIELDS]
 
 
+class _CompileOpts(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("struct_size", "window_div", "keep_trace", "background", "consume_recorder", "reserved")] + [("for_plan", C.c_void_p)]
+
+
+class _PlanRecorderOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("window_div", C.c_uint32), ("plan_file", C.c_char_p)]
+
+
 class _Gate(C.Structure):
     _fields_ = [("wire_a", C.c_uint64), ("wire_b", C.c_uint64), ("wire_c", C.c_uint64), ("gate_type", C.c_uint8), ("pad", C.c_uint8 * 7)]
 
@@ -140,6 +148,7 @@ def lib():
         L.gsv_recorder_record_circuit.argtypes = [vp, C.c_char_p]
         L.gsv_recorder_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.gsv_program_compile.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(vp)]
+        L.gsv_program_compile_opts.argtypes = [vp, vp, C.POINTER(vp)]  # (opts: any structure laid out as gsv_compile_opts)
         L.gsv_program_destroy.argtypes = [vp]
         L.gsv_program_destroy.restype = None
         L.gsv_program_get_info.argtypes = [vp, C.POINTER(_ProgramInfo)]
@@ -172,6 +181,7 @@ def lib():
         L.gsv_plan_from_circuit.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
         L.gsv_plan_io.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.gsv_plan_recorder_create.argtypes = [C.POINTER(vp)]
+        L.gsv_plan_recorder_create_opts.argtypes = [vp, C.POINTER(vp)]  # (opts: any structure laid out as gsv_plan_recorder_opts)
         L.gsv_plan_recorder_destroy.argtypes = [vp]
         L.gsv_plan_recorder_destroy.restype = None
         L.gsv_plan_recorder_allocate_wire.argtypes = [vp, C.c_uint16, C.POINTER(C.c_uint64)]
@@ -290,10 +300,14 @@ class Program:
             L.gsv_recorder_destroy(r)
 
     @classmethod
-    def from_gates(cls, n_inputs, gates, outputs, credits=None):
+    def from_gates(cls, n_inputs, gates, outputs, credits=None, feedback=None, for_plan=None, window_div=None):
         """Record an explicit gate list through the CircuitMode-shaped recorder API.
         gates: iterable of (gate_type, a, b, c) with wire ids: 0/1 constants, inputs 2..2+n_inputs-1, further
-        wires in first-write order; c == None marks a dead gate (UNREACHABLE)."""
+        wires in first-write order; c == None marks a dead gate (UNREACHABLE).
+        feedback: [(output index, input index)] copied after every replay (gsv_program_compile's feedback lists; the sources may be
+        the destinations of other pairs).  for_plan: the PlanRecorder the program is a unit of — it is compiled once, for the
+        recorder's window_div (gsv_program_compile_opts), and cannot have feedback.  window_div = 2 | 4: ONE image for half / a quarter
+        of the LDS label window, the trace is not kept (no variant is compiled when a session asks for another layout)."""
         L = lib()
         r = C.c_void_p()
         _chk(L.gsv_recorder_create(C.byref(r)))
@@ -317,6 +331,19 @@ class Program:
             _chk(L.gsv_recorder_push_gates(r, arr, len(gates)))
             outs = (C.c_uint64 * max(1, len(outputs)))(*outputs)
             _chk(L.gsv_recorder_declare_outputs(r, outs, len(outputs)))
+            if for_plan is not None or window_div is not None:
+                if feedback:
+                    raise ValueError("feedback lists go through gsv_program_compile: not with for_plan / window_div")
+                h = C.c_void_p()
+                o = _CompileOpts(struct_size=C.sizeof(_CompileOpts), window_div=int(window_div or 0), for_plan=for_plan.h if for_plan is not None else None)
+                _chk(L.gsv_program_compile_opts(r, C.byref(o), C.byref(h)))
+                return cls(h)
+            if feedback:
+                h = C.c_void_p()
+                src = (C.c_uint32 * len(feedback))(*[int(a) for a, _ in feedback])
+                dst = (C.c_uint32 * len(feedback))(*[int(b) for _, b in feedback])
+                _chk(L.gsv_program_compile(r, src, dst, len(feedback), C.byref(h)))
+                return cls(h)
             return cls._compile(r, False)
         finally:
             L.gsv_recorder_destroy(r)
@@ -523,9 +550,18 @@ class PlanRecorder:
     """The plan builder driven gate by gate through the C ABI (gsv_plan_recorder_*): what a host with its own two-pass
     driver uses.  Wires: 0 / 1 constants, further ids handed out by allocate_wire."""
 
-    def __init__(self):
+    def __init__(self, window_div=None):
+        """window_div = 2 | 4 (gsv_plan_recorder_create_opts): the glue programs, and every unit compiled with
+        Program.from_gates(for_plan=this recorder), exist as ONE image for half / a quarter of the LDS label window that serves every
+        layout of up to that many instances per workgroup; no other variant is compiled later."""
         self.h = C.c_void_p()
-        _chk(lib().gsv_plan_recorder_create(C.byref(self.h)))
+        if window_div is None:
+            _chk(lib().gsv_plan_recorder_create(C.byref(self.h)))
+        else:
+            if int(window_div) not in (1, 2, 4):
+                raise ValueError("window_div must be 1, 2 or 4")
+            o = _PlanRecorderOpts(C.sizeof(_PlanRecorderOpts), int(window_div), None)
+            _chk(lib().gsv_plan_recorder_create_opts(C.byref(o), C.byref(self.h)))
         self.programs = []
         self.n_inputs = 0
 

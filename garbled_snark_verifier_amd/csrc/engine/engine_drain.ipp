@@ -203,7 +203,7 @@ static void destroy_pair(PairState* ps) {
 static int wait_calls_done(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, bool* window_done, hipStream_t launch_stream = nullptr) {
   if (!launch_stream) launch_stream = s->e->stream;  // the stream the running window was launched on
   const Schedule::Window& win = s->sched.windows[w];
-  const uint32_t n_wg = uint32_t((s->n_inst + s->ni - 1) / s->ni);
+  const uint32_t n_wg = uint32_t(s->launch_groups());  // workgroups that count a call done (one per instance under BLAKE3)
   const auto t0 = std::chrono::steady_clock::now();
   bool reported = false;
   // Host-side deadline, progress based like the device's watchdog (kernels.hip) and longer than it: the device gives up after

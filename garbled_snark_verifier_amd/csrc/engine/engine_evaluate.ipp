@@ -254,7 +254,7 @@ int gsv_program_step_stats(const gsv_program* p, uint32_t* out6) {
 }
 int gsv_session_instances_per_workgroup(const gsv_session* s, int* n) {
   if (!s || !n) return fail(GSV_ERR_INVALID, "null argument");
-  *n = int(s->ni);
+  *n = int(s->launch_ni());
   return GSV_OK;
 }
 int gsv_session_last_kernel_ms(gsv_session* s, double* ms) {

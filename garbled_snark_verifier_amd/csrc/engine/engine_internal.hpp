@@ -209,7 +209,12 @@ struct gsv_session {
   void *W = nullptr, *VB = nullptr, *CT = nullptr, *delta = nullptr, *out = nullptr, *out_bits = nullptr, *in_bits = nullptr, *step_clock = nullptr, *ct_stage = nullptr, *ct_gate = nullptr;
   size_t ct_gate_bytes = 0;  // capacity of ct_gate and of every buffer of ct_gate_more (ensure_ct_gate)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  uint32_t ni = 1;  // instances per workgroup of this session's launches
+  int hasher = 0;  // 0 AesNiHasher, 1 Blake3Hasher (gsv_session_set_hasher: any time between passes)
+  uint32_t ni = 1;  // instances per workgroup the session was laid out for (chosen at creation: program variants, schedule)
+  // ... and of its LAUNCHES: gsvk_launch_batch runs BLAKE3 (one gate per lane, no multi-lane form) at one instance per workgroup whatever
+  // the layout, and the hasher may change after creation.  Everything that counts workgroups or indexes by blockIdx.x asks here.
+  uint32_t launch_ni() const { return hasher == 1 ? 1u : ni; }
+  size_t launch_groups() const { return (n_inst + launch_ni() - 1) / launch_ni(); }  // grid.x of a launch = instance groups
   // plan sessions: `facade` stands in for the program (slots = wire-file stride, inputs / outputs in the global region)
   const gsv_plan* plan = nullptr;
   Program facade;
@@ -251,7 +256,6 @@ struct gsv_session {
   const Program& call_prog(size_t k) const { return plan->calls[k].prog->variant(ni); }
   uint32_t first_input_slot() const { return plan ? global_base : SLOT_FIRST_INPUT; }
   bool ran = false, last_eval = false, garbled = false;
-  int hasher = 0;  // 0 AesNiHasher, 1 Blake3Hasher
   std::vector<uint64_t> ct_uploaded;  // per instance: records supplied by gsv_session_upload_ciphertexts
   struct gsv_drain* drain = nullptr;   // streaming drain: copy streams, pinned buffers, per-instance MAC states (created on first use)
   std::vector<void*> ct_gate_more;     // further gate-order buffers of the drain pipeline (ct_gate is the first)

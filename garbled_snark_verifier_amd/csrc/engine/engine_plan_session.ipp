@@ -221,13 +221,15 @@ static int install_schedule(gsv_session* s, const gsv_plan_session_opts& o, int 
     // the device exactly what a violated dispatch-order assumption looks like (a dependency that never completes).  Never for the safe schedule.
     if (!s->safe_mode && getenv("GSV_FAULT_WITHHOLD_DEP") && atoi(getenv("GSV_FAULT_WITHHOLD_DEP")) == 1)
       for (size_t k = 0; k < n; ++k) if (cds[k].n_deps) { deps[cds[k].dep_off] = s->flag_stride - 2; break; }
-    const size_t n_wg = (n_instances + s->ni - 1) / s->ni;
+    // one flag row per instance: the rows are indexed by blockIdx.x, and a session switched to BLAKE3 after its creation launches one
+    // workgroup per instance whatever s->ni says (gsv_session::launch_ni) — flag_stride * 4 bytes per instance
+    const size_t n_rows = n_instances;
     int rc;
     if ((rc = up(&s->d_calls, cds.data(), cds.size() * sizeof(dev::CallDesc))) || (rc = up(&s->d_copy_src, csrc.data(), csrc.size() * 4)) || (rc = up(&s->d_copy_dst, cdst.data(), cdst.size() * 4)) ||
         (rc = up(&s->d_deps, deps.data(), deps.size() * 4)))
       return rc;
-    HIPCHK(hipMalloc(&s->d_flags, n_wg * size_t(s->flag_stride) * 4 + 64));
-    HIPCHK(hipMemset(s->d_flags, 0, n_wg * size_t(s->flag_stride) * 4 + 64));
+    HIPCHK(hipMalloc(&s->d_flags, n_rows * size_t(s->flag_stride) * 4 + 64));
+    HIPCHK(hipMemset(s->d_flags, 0, n_rows * size_t(s->flag_stride) * 4 + 64));
     HIPCHK(hipMalloc(&s->d_error, 64));
     HIPCHK(hipMemset(s->d_error, 0, 64));
     if ((rc = up(&s->plan_out_slots, f.output_slots.data(), f.output_slots.size() * 4))) return rc;
@@ -406,7 +408,7 @@ static int launch(gsv_session* s, uint64_t gate_id_base, bool eval, uint64_t rep
   ka.hasher = uint32_t(s->hasher);
   ka.and_terms = g.and_terms; ka.any_four_wire = g.and_terms == 4;
   ka.step_clock = static_cast<unsigned long long*>(s->step_clock);
-  ka.instances_per_wg = s->ni;
+  ka.instances_per_wg = s->launch_ni();
   if (const char* dg = getenv("GSV_DIAG")) ka.diag = uint32_t(atoi(dg));  // timing experiments (libgsv_engine_diag.so only): outputs are wrong when set
   HIPCHK(hipEventRecord(s->ev0, s->e->stream));
   if (ka.n_steps) {
@@ -450,7 +452,7 @@ static int launch_plan_window(gsv_session* s, size_t w, uint64_t gate_id_base, b
   ka.delta = static_cast<const uint4*>(s->delta); ka.te = static_cast<const uint32_t*>(s->e->te);
   ka.ct_stride = s->ct_stride(); ka.gid_base = gate_id_base; ka.n_gates = 0; ka.n_ct = 0;
   ka.n_steps = 0; ka.n_slots = f.n_slots; ka.replays = 1; ka.rep_base = 0; ka.ct_cap_replays = 1;
-  ka.n_instances = uint32_t(s->n_inst); ka.hasher = uint32_t(s->hasher); ka.instances_per_wg = s->ni;
+  ka.n_instances = uint32_t(s->n_inst); ka.hasher = uint32_t(s->hasher); ka.instances_per_wg = s->launch_ni();
   for (uint32_t k = win.call0; k < win.call1 && !ka.any_four_wire; ++k) ka.any_four_wire = s->call_prog(k).and_terms == 4;
   if (const char* dg = getenv("GSV_DIAG")) ka.diag = uint32_t(atoi(dg));  // timing experiments (libgsv_engine_diag.so only): outputs are wrong when set
   int lrc = gsvk_launch_batch(&ka, uint32_t(s->n_inst), win.call1 - win.call0, eval ? 1 : 0, stream);
@@ -466,7 +468,7 @@ static int check_plan_error(gsv_session* s) {
     // which calls of the last window have not finished everywhere, and where the host's position stood (diagnostics)
     std::string open_calls;
     if (s->host_done && !s->sched.windows.empty()) {
-      const uint32_t n_wg = uint32_t((s->n_inst + s->ni - 1) / s->ni);
+      const uint32_t n_wg = uint32_t(s->launch_groups());
       const Schedule::Window& win = s->sched.windows.back();
       int shown = 0;
       for (uint32_t k = win.call0; k < win.call1 && shown < 12; ++k)

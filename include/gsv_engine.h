@@ -407,7 +407,8 @@ int gsv_session_sync(gsv_session* s);
 /* 1, 2 or 4: how many instances share a workgroup (= a CU) in this session's launches.  Chosen at creation: 2 once the
  * session holds more instances than the device has CUs, 4 once it holds more than twice as many (each instance then works
  * with half / a quarter of the LDS label window; the program variant for that share is compiled on first use, or the plan was
- * built for it: GSV_PLAN_WINDOW_DIV), else 1; GSV_INSTANCES_PER_WG=1|2|4 overrides.  Results do not depend on it. */
+ * built for it: GSV_PLAN_WINDOW_DIV), else 1; GSV_INSTANCES_PER_WG=1|2|4 overrides.  Results do not depend on it.
+ * With GSV_HASHER_BLAKE3 set the launches run one instance per workgroup whatever was chosen at creation, and this returns 1. */
 int gsv_session_instances_per_workgroup(const gsv_session* s, int* n);
 /* seconds of device time of the last garble/evaluate launch (HIP events on the engine stream) */
 int gsv_session_last_kernel_ms(gsv_session* s, double* ms);
