@@ -113,7 +113,7 @@ class _Gate(C.Structure):
 EXPORTS = [
     "gsv_last_error", "gsv_recorder_create", "gsv_recorder_destroy", "gsv_recorder_allocate_wire", "gsv_recorder_declare_input",
     "gsv_recorder_push_gates", "gsv_recorder_declare_outputs", "gsv_recorder_record_circuit", "gsv_recorder_counts", "gsv_program_compile", "gsv_program_destroy",
-    "gsv_program_get_info", "gsv_engine_create", "gsv_engine_destroy", "gsv_deferred_release_count", "gsv_session_fallback_count", "gsv_plan_build_file_pair", "gsv_plan_call_record_form", "gsv_labels_from_seed", "gsv_session_create", "gsv_session_destroy",
+    "gsv_program_get_info", "gsv_engine_create", "gsv_engine_destroy", "gsv_deferred_release_count", "gsv_session_fallback_count", "gsv_plan_build_file_pair", "gsv_plan_build_file_div", "gsv_plan_from_circuit_div", "gsv_plan_call_record_form", "gsv_labels_from_seed", "gsv_session_create", "gsv_session_destroy",
     "gsv_session_set_garble_inputs", "gsv_session_garble", "gsv_session_set_evaluate_inputs", "gsv_session_upload_ciphertexts",
     "gsv_session_evaluate", "gsv_session_set_hasher", "gsv_session_sync", "gsv_session_last_kernel_ms", "gsv_session_read_outputs", "gsv_session_read_ciphertexts",
     "gsv_session_ciphertext_hash", "gsv_cbcmac_update", "gsv_cbcmac_update_many", "gsv_commit_labels",
@@ -179,6 +179,7 @@ def lib():
         L.gsv_commit_labels.argtypes = [u8p, C.c_uint64, u8p]
         L.gsv_cbcmac_update_many.argtypes = [u8p, C.POINTER(C.c_void_p), C.c_size_t, C.c_uint64]
         L.gsv_plan_from_circuit.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
+        L.gsv_plan_from_circuit_div.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(vp)]
         L.gsv_plan_io.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.gsv_plan_recorder_create.argtypes = [C.POINTER(vp)]
         L.gsv_plan_recorder_create_opts.argtypes = [vp, C.POINTER(vp)]  # (opts: any structure laid out as gsv_plan_recorder_opts)
@@ -206,6 +207,7 @@ def lib():
         L.gsv_plan_save.argtypes = [vp, C.c_char_p]
         L.gsv_plan_load.argtypes = [C.c_char_p, vp, C.POINTER(vp)]
         L.gsv_plan_build_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p]
+        L.gsv_plan_build_file_div.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32]
         L.gsv_session_instances_per_workgroup.argtypes = [vp, C.POINTER(C.c_int)]
         L.gsv_session_enable_step_clock.argtypes = [vp]
         L.gsv_session_read_step_clock.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -417,44 +419,17 @@ class Plan:
         div = int(window_div) if window_div else (2 if half_window else 1)
         if div not in (1, 2, 4):
             raise ValueError("window_div must be 1, 2 or 4")
-        saved = {k: os.environ.get(k) for k in ("GSV_PLAN_WINDOW_DIV", "GSV_PLAN_HALF_WINDOW")}
-        if div > 1:
-            os.environ["GSV_PLAN_WINDOW_DIV"] = str(div)
-            os.environ.pop("GSV_PLAN_HALF_WINDOW", None)
-        try:
-            _chk(lib().gsv_plan_from_circuit(spec.encode(), ",".join(units).encode(), C.byref(self.h)))
-        finally:
-            if div > 1:
-                for k, v in saved.items():
-                    if v is None:
-                        os.environ.pop(k, None)
-                    else:
-                        os.environ[k] = v
-        g, c, k = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _chk(lib().gsv_plan_counts(self.h, C.byref(g), C.byref(c), C.byref(k)))
-        n_in, n_out = C.c_uint64(), C.c_uint64()
-        _chk(lib().gsv_plan_io(self.h, C.byref(n_in), C.byref(n_out)))
-        self.n_inputs, self.n_outputs = n_in.value, n_out.value
-        self.info = {"n_inputs": n_in.value, "n_outputs": n_out.value, "n_gates": g.value, "n_ciphertexts": c.value, "n_calls": k.value, "n_steps": 0}
+        _chk(lib().gsv_plan_from_circuit_div(spec.encode(), ",".join(units).encode(), div if div > 1 else 0, C.byref(self.h)))  # 0: as GSV_PLAN_WINDOW_DIV / GSV_PLAN_HALF_WINDOW say
+        self._read_info()
         return self
 
     @staticmethod
     def build_file(spec, units, path, window_div=4):
-        """Build the plan of a built-in circuit straight into the plan file `path` (gsv_plan_build_file): every program is written
+        """Build the plan of a built-in circuit straight into the plan file `path` (gsv_plan_build_file_div): every program is written
         by the worker that compiled it and dropped from memory.  Load it with Plan.load(path, engine)."""
         if int(window_div) not in (1, 2, 4):
             raise ValueError("window_div must be 1, 2 or 4 (one image per program; 1 = full LDS window, one instance per workgroup only)")
-        saved = {k: os.environ.get(k) for k in ("GSV_PLAN_WINDOW_DIV", "GSV_PLAN_HALF_WINDOW")}
-        os.environ["GSV_PLAN_WINDOW_DIV"] = str(int(window_div))
-        os.environ.pop("GSV_PLAN_HALF_WINDOW", None)
-        try:
-            _chk(lib().gsv_plan_build_file(spec.encode(), ",".join(units).encode(), os.fsencode(path)))
-        finally:
-            for k, v in saved.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
+        _chk(lib().gsv_plan_build_file_div(spec.encode(), ",".join(units).encode(), os.fsencode(path), int(window_div)))
 
     @staticmethod
     def build_file_pair(spec, units_a, path_a, window_div_a, path_b, window_div_b, units_b=None):

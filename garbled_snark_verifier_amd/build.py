@@ -171,7 +171,7 @@ def build(force=False, verbose=False, diag=False, variant=None, defines=()):
     """diag=True builds libgsv_engine_diag.so instead: the same library with the kernel's timing ablations compiled in
     (-DGSV_DIAG_BUILD; GSV_DIAG=<bits> then takes effect, see kernel_api.h) — load it with GSV_ENGINE_SO for experiments."""
     if os.environ.get("GSV_ENGINE_SO") and not diag:  # experiments: load a differently built library
-        return os.environ["GSV_ENGINE_SO"]
+        return os.environ.get("GSV_ENGINE_SO")
     out = OUT.replace(".so", "_diag.so") if diag else OUT
     if variant:  # kernel A/B experiments: libgsv_engine_<variant>.so built with extra -D flags, loaded through GSV_ENGINE_SO
         out = OUT.replace(".so", "_%s.so" % variant)

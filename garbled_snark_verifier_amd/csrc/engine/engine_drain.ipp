@@ -36,8 +36,8 @@ struct gsv_drain {
   // One chain per worker while there is a core per instance: a chain alone advances at ~1.1e8 blocks/s, one of four interleaved at
   // ~0.75e8 — sixteen instances (BASELINE config 5 on one GPU) hashed four to a worker took 40 s for 34.8 s of garbling, their
   // sixteen chains one per core take 27 s.  More instances than cores: four (AES-NI) or sixteen (VAES, >= 128 instances) per worker.
-  static int group_for(size_t n_inst) {
-    if (const char* e = getenv("GSV_DRAIN_GROUP")) { const int v = atoi(e); if (v == 1 || v == 4 || v == 16) return v; }
+  static int group_for(size_t n_inst, int forced) {  // forced: GSV_DRAIN_GROUP, 0 = not set
+    if (forced) return forced;
     if (n_inst <= usable_cores()) return 1;
     return CbcMacHost::have_vaes() && n_inst >= 128 ? 16 : 4;
   }
@@ -61,8 +61,7 @@ static void destroy_drain(gsv_drain* d) { delete d; }
 static int ensure_drain(gsv_session* s, size_t T, uint64_t seg_records, int group) {
   // records per chunk: 16 MiB by default — measured on the MI355X box (tools/d2h_bw.py) a D2H copy stream moves 39-48 GB/s in 4 MiB
   // pieces and 54-57 GB/s from 16 MiB up; the buffers are page-locked once per session, not per call as in round 1
-  const uint64_t chunk_mb = getenv("GSV_DRAIN_CHUNK_MB") ? std::max(1, atoi(getenv("GSV_DRAIN_CHUNK_MB"))) : 16;
-  const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(seg_records, 1), (chunk_mb << 20) / 16);
+  const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(seg_records, 1), (s->pass.drain_chunk_mb << 20) / 16);
   if (s->drain && s->drain->workers.size() >= T && s->drain->chunk == chunk && s->drain->group == group) return GSV_OK;
   std::vector<CbcMacHost> keep;
   if (s->drain) keep = s->drain->macs;
@@ -74,11 +73,11 @@ static int ensure_drain(gsv_session* s, size_t T, uint64_t seg_records, int grou
   d.group = group;
   // Copy sets in flight at once.  Round 3, whole Miller-loop pass at 64 instances (tools/e2e_plan_drain.py, profiles/r03_e2e/): 1 set
   // 48 GB/s, 2-4 sets 50 GB/s, 6 sets 40 GB/s, 12 sets 41 GB/s — the link is full with two or three 16 MiB copies queued.
-  const int n_copy_streams = getenv("GSV_DRAIN_COPIES") ? std::max(1, atoi(getenv("GSV_DRAIN_COPIES"))) : 3;
+  const int n_copy_streams = s->pass.drain_copies;
   bool ok = true;
   for (int k = 0; k < n_copy_streams && ok; ++k) {
     hipStream_t st;
-    ok = create_side_stream(&st) == hipSuccess;
+    ok = create_side_stream(&st, s->kn.side_stream_priority) == hipSuccess;
     if (ok) { d.copy_streams.push_back(st); d.copy_gate.idle.push_back(st); }
   }
   d.workers.resize(T);
@@ -146,7 +145,7 @@ static int ensure_pair(gsv_session* s) {
     // Three quarters of the CUs garble (two AES blocks per AND), a quarter evaluates (one).  The mask bits alternate in blocks of eight,
     // 3 : 1: whichever way the runtime maps bits to XCDs / shader engines, every XCD keeps CUs of both launches.  GSV_PAIR_CU_MASK=0, or a
     // runtime that refuses the masks, falls back to the probed unmasked stream below.
-    if (!(getenv("GSV_PAIR_CU_MASK") && atoi(getenv("GSV_PAIR_CU_MASK")) == 0)) {
+    if (s->pass.pair_cu_mask) {
       hipDeviceProp_t prop;
       if (hipGetDeviceProperties(&prop, s->e->device) == hipSuccess && prop.multiProcessorCount >= 32) {
         const uint32_t n_cu = uint32_t(prop.multiProcessorCount), words = (n_cu + 31) / 32;
@@ -156,7 +155,7 @@ static int ensure_pair(gsv_session* s) {
         if (hipExtStreamCreateWithCUMask(&g, words, gm.data()) == hipSuccess && hipExtStreamCreateWithCUMask(&e2, words, em.data()) == hipSuccess &&
             hipEventCreateWithFlags(&ps->ready, hipEventDisableTiming) == hipSuccess) {
           ps->gstream = g; ps->stream = e2;
-          if (getenv("GSV_DRAIN_DEBUG")) std::fprintf(stderr, "garble -> evaluate: CU-masked streams, %u CUs garble, %u evaluate\n", n_cu - n_cu / 4, n_cu / 4);
+          if (s->pass.drain_debug) std::fprintf(stderr, "garble -> evaluate: CU-masked streams, %u CUs garble, %u evaluate\n", n_cu - n_cu / 4, n_cu / 4);
         } else {
           (void)hipGetLastError();
           if (g) (void)hipStreamDestroy(g);
@@ -176,7 +175,7 @@ static int ensure_pair(gsv_session* s) {
                             hipStreamSynchronize(s->e->stream) == hipSuccess && hipMemcpy(result, word, 8, hipMemcpyDeviceToHost) == hipSuccess;
         if (!probed || result[1] == 1u || attempt == 7) ps->stream = cand;
         else rejected.push_back(cand);
-        if (getenv("GSV_DRAIN_DEBUG")) std::fprintf(stderr, "garble -> evaluate: candidate stream %d %s\n", attempt, !probed ? "could not be probed" : result[1] == 1u ? "overlaps the engine's stream" : "queues behind the engine's stream");
+        if (s->pass.drain_debug) std::fprintf(stderr, "garble -> evaluate: candidate stream %d %s\n", attempt, !probed ? "could not be probed" : result[1] == 1u ? "overlaps the engine's stream" : "queues behind the engine's stream");
       }
       for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
       if (!ps->stream) return fail(GSV_ERR_DEVICE, "cannot create the evaluator's stream");
@@ -209,9 +208,7 @@ static int wait_calls_done(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, b
   // Host-side deadline, progress based like the device's watchdog (kernels.hip) and longer than it: the device gives up after
   // GSV_DEP_WAIT_SECONDS (default 60) without a completed call of an instance group and then ENDS its launch, which the stream query below
   // sees; this deadline covers the device that never comes back at all (no counter of the window has moved for twice that time + 30 s).
-  double dev_secs = 60.0;
-  if (const char* ev = getenv("GSV_DEP_WAIT_SECONDS")) { char* end = nullptr; const double v = std::strtod(ev, &end); if (end != ev && v > 0) dev_secs = std::min(v, 86400.0); }
-  const double deadline = 2.0 * dev_secs + 30.0;
+  const double deadline = 2.0 * s->pass.dep_wait_seconds + 30.0;
   uint64_t last_sum = ~0ull;
   auto last_move = t0;
   uint32_t polls = 0;
@@ -234,7 +231,7 @@ static int wait_calls_done(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, b
       else if (std::chrono::duration<double>(now - last_move).count() > deadline)
         return fail(GSV_ERR_DEVICE, "no call of the running window has completed for " + std::to_string(int(deadline)) + " s and its launch has not ended: giving up on the device");
     }
-    if (!reported && getenv("GSV_DRAIN_DEBUG") && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 3.0) {
+    if (!reported && s->pass.drain_debug && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 3.0) {
       reported = true;
       std::string msg;
       for (uint32_t k = win.call0; k < win.call1; ++k)
@@ -263,7 +260,7 @@ static int ensure_ct_gate(gsv_session* s, size_t bytes) {
   return GSV_OK;
 }
 static int ensure_aux(gsv_session* s) {
-  if (!s->aux_stream) HIPCHK(create_side_stream(&s->aux_stream));
+  if (!s->aux_stream) HIPCHK(create_side_stream(&s->aux_stream, s->kn.side_stream_priority));
   if (!s->host_done) return fail(GSV_ERR_INVALID, "internal: a plan session without completion counters");  // (allocated with its call descriptors)
   return GSV_OK;
 }
@@ -284,7 +281,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   const size_t n_inst = s->drain_instances ? std::min(s->drain_instances, s->n_inst) : s->n_inst;
   const bool want_drain = sink.any();
   const bool want_mac = sink.hashes != nullptr;
-  const size_t GROUP = size_t(gsv_drain::group_for(n_inst));
+  const size_t GROUP = size_t(gsv_drain::group_for(n_inst, s->pass.drain_group));
   const size_t n_groups = (n_inst + GROUP - 1) / GROUP;
   // a worker MACs GROUP streams side by side at ~3e8 blocks/s (four chains, AES-NI) or ~1e9 (sixteen, VAES): a dozen / four of them keep
   // up with the PCIe link, 32 leave room for slow cores without page-locking more than 4 GB (16 GB) of chunk buffers
@@ -338,7 +335,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
       const size_t buf_bytes = n_inst * size_t(seg_records) * 16;
       // up to eight buffers, within half of the free memory and 32 GB (allocating device memory takes time too: ~25 GB/s)
       want = std::min<size_t>(std::min<size_t>(8, 1 + size_t(double(free_b) * 0.5 / double(buf_bytes))), std::max<size_t>(2, size_t(32e9 / double(buf_bytes))));
-      if (const char* e = getenv("GSV_DRAIN_DEPTH")) want = size_t(std::max(1, atoi(e)));
+      if (s->pass.drain_depth) want = s->pass.drain_depth;
     }
     while (1 + s->ct_gate_more.size() < want) {
       void* q = nullptr;
@@ -413,7 +410,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   if (want_drain) for (size_t t = 0; t < T; ++t) workers.emplace_back(worker_main, t);
   // GSV_DRAIN_STATS=1: where the host thread of the pipeline waits (for a free gate-order buffer = the host side is the slower stage;
   // for the kernel + gather = the device is), printed once per call
-  const bool stats = getenv("GSV_DRAIN_STATS") != nullptr;
+  const bool stats = s->pass.drain_stats;
   double t_wait_drain = 0, t_wait_device = 0, t_gather = 0;
   uint64_t drained_records = 0;
   const auto t_begin = std::chrono::steady_clock::now();
@@ -638,12 +635,12 @@ static int garble_streaming_range(gsv_session* s, uint64_t gate_id_base, size_t 
   if (ev) { frc = fall_back_to_safe_schedule(ev); if (frc) return fail(GSV_ERR_DEVICE, first_error + "; the evaluator's fall-back to the safe schedule failed: " + g_err); }
   if (!whole || sink.fn || ev)
     return fail(GSV_ERR_DEVICE, first_error + "; the session now runs the safe schedule (one call per launch): repeat the pass from gsv_session_set_garble_inputs");
-  if (getenv("GSV_DRAIN_DEBUG") || getenv("GSV_PLAN_DEBUG")) std::fprintf(stderr, "plan session: %s -- repeating the pass on the safe schedule (one call per launch)\n", first_error.c_str());
+  if (s->pass.drain_debug || s->pass.plan_debug) std::fprintf(stderr, "plan session: %s -- repeating the pass on the safe schedule (one call per launch)\n", first_error.c_str());
   return garble_streaming_pass(s, gate_id_base, 0, s->plan->calls.size(), sink, n_threads, nullptr);
 }
 static DrainSink mac_file_sink(uint8_t* hashes, const char* dir, uint64_t first_index) { DrainSink k; k.hashes = hashes; k.dir = dir; k.first_index = first_index; return k; }
 int gsv_session_garble_streaming(gsv_session* s, uint64_t gate_id_base, const char* dir, uint64_t first_index, int n_threads, uint8_t* hashes) {
-  PassGuard pass_guard;  // destroys requested while this pass runs wait for its end (deferred release)
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   if (!s) return fail(GSV_ERR_INVALID, "null argument");
   if (dir && !hashes) return fail(GSV_ERR_INVALID, "null hash buffer");
   return garble_streaming_range(s, gate_id_base, 0, s->plan ? s->plan->calls.size() : 1, mac_file_sink(hashes, dir, first_index), n_threads);
@@ -659,7 +656,7 @@ static int check_slice(gsv_session* s, uint64_t first_call, uint64_t n_calls) {
   return GSV_OK;
 }
 int gsv_session_garble_streaming_calls(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* dir, uint64_t first_index, int n_threads, uint8_t* hashes) {
-  PassGuard pass_guard;  // destroys requested while this pass runs wait for its end (deferred release)
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   int rc = check_slice(s, first_call, n_calls);
   if (rc) return rc;
   if (dir && !hashes) return fail(GSV_ERR_INVALID, "null hash buffer");
@@ -669,7 +666,7 @@ int gsv_session_garble_streaming_calls(gsv_session* s, uint64_t gate_id_base, ui
 }
 // The generic CiphertextHandler: every drained run of records is handed to `sink` (gate order, per instance in stream order).
 int gsv_session_garble_streaming_sink(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, gsv_ct_sink_fn sink, void* user, int n_threads, uint8_t* hashes) {
-  PassGuard pass_guard;  // destroys requested while this pass runs wait for its end (deferred release)
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   if (!s || !sink) return fail(GSV_ERR_INVALID, "null argument");
   DrainSink k;
   k.hashes = hashes; k.fn = sink; k.user = user;
@@ -684,8 +681,9 @@ int gsv_session_garble_streaming_sink(gsv_session* s, uint64_t gate_id_base, uin
 // Garble and evaluate side by side on the device (examples/groth16_garble.rs:171-230: the garbler thread feeds the evaluator thread
 // through a channel; here window k of the garbler's device block is evaluated while window k+1 is garbled).
 int gsv_session_garble_evaluate(gsv_session* gs, gsv_session* es, uint64_t gate_id_base, int n_threads, uint8_t* hashes) {
-  PassGuard pass_guard;  // destroys requested while this pass runs wait for its end (deferred release)
+  PassGuard pass_guard(gs);  // destroys requested while this pass runs wait for its end (deferred release)
   if (!gs || !es || gs == es) return fail(GSV_ERR_INVALID, "null / identical sessions");
+  es->pass = gs->pass;
   if (!gs->plan || gs->plan != es->plan || gs->e != es->e || gs->n_inst != es->n_inst || gs->ni != es->ni || gs->hasher != es->hasher)
     return fail(GSV_ERR_INVALID, "garbler and evaluator must be plan sessions of the same plan, engine, instance count and hasher");
   if (gs->plan_retain || es->plan_retain) return fail(GSV_ERR_INVALID, "gsv_session_garble_evaluate is for sessions that do not retain the stream (retain_stream = 0)");

@@ -1,6 +1,7 @@
 // Part of engine.cpp: evaluation (resident stream and streaming sources) and the remaining small entry points.
 int gsv_session_evaluate(gsv_session* s, uint64_t gate_id_base) {
   if (!s) return fail(GSV_ERR_INVALID, "null session");
+  s->pass = knobs::Pass();  // this pass's knobs
   // EvaluateMode panics with "Ciphertext source exhausted at gate .." when the source runs dry (evaluate_mode.rs:139-142).
   const uint64_t need = s->prog().n_ct * s->replays;
   if (s->ct_cap != s->replays || (s->plan && !s->plan_retain)) return fail(GSV_ERR_INVALID, "evaluate needs the whole ciphertext stream resident (ct_capacity_replays == replays)");
@@ -158,7 +159,7 @@ static int evaluate_streaming_impl(gsv_session* s, uint64_t gate_id_base, const 
   const std::string first_error = g_err;
   if (fall_back_to_safe_schedule(s)) return fail(GSV_ERR_DEVICE, first_error + "; the fall-back to the safe schedule failed too: " + g_err);
   if (!rereadable) return fail(GSV_ERR_DEVICE, first_error + "; the session now runs the safe schedule (one call per launch): repeat the pass from gsv_session_set_evaluate_inputs");
-  if (getenv("GSV_DRAIN_DEBUG") || getenv("GSV_PLAN_DEBUG")) std::fprintf(stderr, "plan session: %s -- repeating the evaluation on the safe schedule (one call per launch)\n", first_error.c_str());
+  if (s->pass.drain_debug || s->pass.plan_debug) std::fprintf(stderr, "plan session: %s -- repeating the evaluation on the safe schedule (one call per launch)\n", first_error.c_str());
   return evaluate_streaming_pass(s, gate_id_base, read, hashes);
 }
 // FileSource: instance i reads <dir>/gc_<indexes[i]>.bin (indexes == NULL: first_index + i)
@@ -181,16 +182,16 @@ static int evaluate_from_files(gsv_session* s, uint64_t gate_id_base, const char
   }, hashes, /*rereadable=*/true);
 }
 int gsv_session_evaluate_streaming(gsv_session* s, uint64_t gate_id_base, const char* dir, uint64_t first_index, uint8_t* hashes) {
-  PassGuard pass_guard;  // destroys requested while this pass runs wait for its end (deferred release)
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   return evaluate_from_files(s, gate_id_base, dir, nullptr, first_index, hashes);
 }
 int gsv_session_evaluate_streaming_indexed(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint8_t* hashes) {
-  PassGuard pass_guard;  // destroys requested while this pass runs wait for its end (deferred release)
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   if (!indexes) return fail(GSV_ERR_INVALID, "null index list");
   return evaluate_from_files(s, gate_id_base, dir, indexes, 0, hashes);
 }
 int gsv_session_evaluate_streaming_source(gsv_session* s, uint64_t gate_id_base, gsv_ct_source_fn source, void* user, uint8_t* hashes) {
-  PassGuard pass_guard;  // destroys requested while this pass runs wait for its end (deferred release)
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   if (!s || !source) return fail(GSV_ERR_INVALID, "null argument");
   return evaluate_streaming_impl(s, gate_id_base, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t n) -> int { return source(user, i, first, dst, n); }, hashes);
 }

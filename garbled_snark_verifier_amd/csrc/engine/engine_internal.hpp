@@ -28,6 +28,7 @@
 #include "../gadgets/circuits.hpp"
 #include "host_crypto.hpp"
 #include "kernel_api.h"
+#include "knobs.hpp"
 #include "plan_builder.hpp"
 #include "schedule.hpp"
 #include "program.hpp"
@@ -84,9 +85,9 @@ struct ReleaseGate {
 };
 ReleaseGate& release_gate() { static ReleaseGate g; return g; }
 // First local of every streaming entry point: declared before anything else so that it is destroyed LAST — a session destroyed from
-// its own pass's callback is still alive while the entry point uses it.
+// its own pass's callback is still alive while the entry point uses it.  Also reads this pass's knobs into s->pass (s may be null).
 struct PassGuard {
-  PassGuard() { ReleaseGate& g = release_gate(); std::lock_guard<std::recursive_mutex> lk(g.mu); ++g.active; }
+  explicit PassGuard(gsv_session* s);  // (below gsv_session)
   ~PassGuard() {
     ReleaseGate& g = release_gate();
     std::lock_guard<std::recursive_mutex> lk(g.mu);
@@ -113,10 +114,9 @@ void release_or_defer(std::function<void()> fn) {
 // had created before).  Streams of another priority level come from another pool of hardware queues, so these ask for the highest.
 // (Not for the evaluator of a garble -> evaluate pair: two long launches on queues of DIFFERENT priority, whichever way round, took
 // 46.5 s for the verifier instead of 42.9 s on equal terms — ensure_pair probes for a stream of the same priority that overlaps.)
-static hipError_t create_side_stream(hipStream_t* st) {
+static hipError_t create_side_stream(hipStream_t* st, bool highest_priority) {
   int least = 0, greatest = 0;
-  const char* off = getenv("GSV_SIDE_STREAM_PRIORITY");
-  if ((off && off[0] == '0') || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || greatest == least) return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
+  if (!highest_priority || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || greatest == least) return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
   return hipStreamCreateWithPriority(st, hipStreamNonBlocking, greatest);
 }
 
@@ -210,6 +210,7 @@ struct gsv_session {
   size_t ct_gate_bytes = 0;  // capacity of ct_gate and of every buffer of ct_gate_more (ensure_ct_gate)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   int hasher = 0;  // 0 AesNiHasher, 1 Blake3Hasher (gsv_session_set_hasher: any time between passes)
+  knobs::Session kn; knobs::Pass pass;  // knobs.hpp: read when the session was created / at the top of the garble or evaluate entry point that runs (PassGuard, or assigned there): per pass
   uint32_t ni = 1;  // instances per workgroup the session was laid out for (chosen at creation: program variants, schedule)
   // ... and of its LAUNCHES: gsvk_launch_batch runs BLAKE3 (one gate per lane, no multi-lane form) at one instance per workgroup whatever
   // the layout, and the hasher may change after creation.  Everything that counts workgroups or indexes by blockIdx.x asks here.
@@ -263,6 +264,7 @@ struct gsv_session {
   struct PairState* pair = nullptr;    // ... and its stream / events (created on first use)
   uint64_t ct_stride() const { return plan ? (plan_retain ? plan->n_ct : plan_max_block) : ct_cap * p->prog.n_ct; }  // n_ct does not depend on the variant
 };
+PassGuard::PassGuard(gsv_session* s) { if (s) s->pass = knobs::Pass(); ReleaseGate& g = release_gate(); std::lock_guard<std::recursive_mutex> lk(g.mu); ++g.active; }
 
 // Failure paths release whatever was allocated so far through the public destroy functions (a failed hipMalloc on a
 // multi-GB session must not leave the GPU full).

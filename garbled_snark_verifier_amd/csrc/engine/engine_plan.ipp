@@ -52,11 +52,11 @@ int gsv_plan_finish(gsv_plan* p, uint32_t n_inputs, const uint32_t* output_globa
 // Record one of the built-in restated circuits under the two-pass driver with the named components (comma separated,
 // e.g. "fq12::mul_montgomery,fq12::square_montgomery") turned into calls of separately compiled programs; everything
 // between them is compiled as glue programs (plan_builder.hpp).
-static int plan_window_div(uint32_t* window_div) {
-  *window_div = 1;
-  if (getenv("GSV_PLAN_HALF_WINDOW") && atoi(getenv("GSV_PLAN_HALF_WINDOW")) != 0) *window_div = 2;
-  if (const char* e = getenv("GSV_PLAN_WINDOW_DIV")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) *window_div = uint32_t(v); else return fail(GSV_ERR_INVALID, "GSV_PLAN_WINDOW_DIV must be 1, 2 or 4"); }
-  return GSV_OK;
+// window_div as the entry points take it: 1, 2, 4, or 0 = as GSV_PLAN_WINDOW_DIV / GSV_PLAN_HALF_WINDOW say (kn.window_div, itself 0 for a bad value)
+static int resolve_window_div(uint32_t* window_div, const knobs::PlanBuild& kn) {
+  const bool from_env = *window_div == 0;
+  if (from_env) *window_div = kn.window_div;
+  return *window_div == 1 || *window_div == 2 || *window_div == 4 ? GSV_OK : fail(GSV_ERR_INVALID, from_env ? "GSV_PLAN_WINDOW_DIV must be 1, 2 or 4" : "window_div must be 0, 1, 2 or 4");
 }
 // A dual build (gsv_plan_build_file_pair): the second image of every program — compiled from the same recording for 1 / window_div of the
 // LDS window, handed to `sink` — and the second plan.
@@ -66,8 +66,8 @@ struct DualBuild {
   std::function<void(Program&)> sink;
   gsv_plan** out = nullptr;
 };
-// sink: see PlanUnitCache::sink (gsv_plan_build_file); empty = the programs stay in memory.  window_div_override: 0 = GSV_PLAN_WINDOW_DIV.
-static int plan_from_circuit_impl(const char* spec, const char* units_csv, const std::function<void(Program&)>& sink, gsv_plan** out, uint32_t window_div_override = 0,
+// sink: see PlanUnitCache::sink (gsv_plan_build_file); empty = the programs stay in memory.  window_div: 1, 2 or 4 (resolve_window_div).
+static int plan_from_circuit_impl(const char* spec, const char* units_csv, const std::function<void(Program&)>& sink, gsv_plan** out, uint32_t window_div, const knobs::PlanBuild& kn,
                                   const DualBuild* dual = nullptr) {
   if (!spec || !units_csv || !out) return fail(GSV_ERR_INVALID, "null argument");
   GSV_TRY
@@ -84,15 +84,11 @@ static int plan_from_circuit_impl(const char* spec, const char* units_csv, const
   const bool two_recorders = dual && dual->units_csv && split_csv(dual->units_csv) != names;
   NamedCircuit nc = make_circuit(spec);
   PlanRecordMode mode(names);
-  CompileOptions opt;
-  if (const char* e = getenv("GSV_FUSE")) opt.fuse = atoi(e) != 0;
-  // GSV_PLAN_WINDOW_DIV=2|4: compile every program once, for half / a quarter of the LDS window; the same image then serves every
+  CompileOptions opt = kn.opt;
+  // window_div 2|4: compile every program once, for half / a quarter of the LDS window; the same image then serves every
   // layout of up to that many instances per workgroup and the recorded traces are not kept (less host memory and no second
   // compilation for plans with hundreds of programs, at a smaller window when sessions have few instances).
   // GSV_PLAN_HALF_WINDOW=1 is the older spelling of GSV_PLAN_WINDOW_DIV=2.
-  uint32_t window_div = 1;
-  if (window_div_override) window_div = window_div_override;
-  else { int rc = plan_window_div(&window_div); if (rc) return rc; }
   if (dual) {
     if (!sink || !dual->sink || !dual->out) return fail(GSV_ERR_INVALID, "internal: a dual build writes both plans to files");
     CompileOptions ob = opt;
@@ -105,9 +101,8 @@ static int plan_from_circuit_impl(const char* spec, const char* units_csv, const
   const bool single_image = window_div > 1 || bool(sink);
   mode.cache()->sink = sink;
   if (single_image) opt.lds_slots = std::min<uint32_t>(opt.lds_slots, LDS_WINDOW_SLOTS / window_div);
-  mode.compile_in_background(opt, single_image);  // units are compiled while the driver records the rest of the circuit
+  mode.compile_in_background(opt, single_image, kn.compile_threads);  // units are compiled while the driver records the rest of the circuit
   std::vector<uint32_t> in_ssa, out_ssa;
-  const bool dbg = getenv("GSV_PLAN_DEBUG") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
   size_t n_recorders = 0;
@@ -123,22 +118,22 @@ static int plan_from_circuit_impl(const char* spec, const char* units_csv, const
     walk_b = std::thread([&] {
       try {
         size_t nr = 0;
-        record_plan(*mode_b, nc.n_inputs, nc.fn, std::vector<NamedCircuit::Warmup>(), in_ssa_b, out_ssa_b, &nr);
+        record_plan(*mode_b, nc.n_inputs, nc.fn, std::vector<NamedCircuit::Warmup>(), in_ssa_b, out_ssa_b, kn, &nr);
       } catch (...) { walk_b_err = std::current_exception(); }
     });
   }
   struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } walk_b_joiner{walk_b};
-  record_plan(mode, nc.n_inputs, nc.fn, nc.warmups, in_ssa, out_ssa, &n_recorders);
+  record_plan(mode, nc.n_inputs, nc.fn, nc.warmups, in_ssa, out_ssa, kn, &n_recorders);
   if (walk_b.joinable()) walk_b.join();
   if (walk_b_err) std::rethrow_exception(walk_b_err);
-  if (dbg) std::fprintf(stderr, "plan: recorded at %.1f s (%zu units, %zu glue classes, %zu warm-ups on %zu threads)\n", since(), mode.units.size(), mode.glue_classes.size(), nc.warmups.size(), n_recorders);
+  if (kn.debug) std::fprintf(stderr, "plan: recorded at %.1f s (%zu units, %zu glue classes, %zu warm-ups on %zu threads)\n", since(), mode.units.size(), mode.glue_classes.size(), nc.warmups.size(), n_recorders);
   mode.wait_for_compilations();
-  if (dbg) std::fprintf(stderr, "plan: background compilations finished at %.1f s\n", since());
-  BuiltPlan bp = finish_plan(mode, in_ssa, out_ssa, opt, dual && !two_recorders ? 2 : 0);
+  if (kn.debug) std::fprintf(stderr, "plan: background compilations finished at %.1f s\n", since());
+  BuiltPlan bp = finish_plan(mode, in_ssa, out_ssa, opt, kn, dual && !two_recorders ? 2 : 0);
   BuiltPlan bp_second;
-  if (two_recorders) bp_second = finish_plan(*mode_b, in_ssa_b, out_ssa_b, opt, 1);
-  if (dbg) std::fprintf(stderr, "plan: all programs compiled at %.1f s\n", since());
-  if (dbg) {  // per program: how often it is called, its size and shape (latency-bound programs carry four-wire records)
+  if (two_recorders) bp_second = finish_plan(*mode_b, in_ssa_b, out_ssa_b, opt, kn, 1);
+  if (kn.debug) std::fprintf(stderr, "plan: all programs compiled at %.1f s\n", since());
+  if (kn.debug) {  // per program: how often it is called, its size and shape (latency-bound programs carry four-wire records)
     std::vector<size_t> n_calls(bp.programs.size(), 0);
     for (const BuiltPlan::Call& c : bp.calls) if (c.program >= 0) n_calls[size_t(c.program)]++;
     for (size_t k = 0; k < bp.programs.size(); ++k) {
@@ -179,7 +174,14 @@ static int plan_from_circuit_impl(const char* spec, const char* units_csv, const
   return GSV_OK;
   GSV_CATCH
 }
-int gsv_plan_from_circuit(const char* spec, const char* units_csv, gsv_plan** out) { return plan_from_circuit_impl(spec, units_csv, nullptr, out); }
+int gsv_plan_from_circuit_div(const char* spec, const char* units_csv, uint32_t window_div, gsv_plan** out) {
+  GSV_TRY
+  const knobs::PlanBuild kn;
+  { int rc = resolve_window_div(&window_div, kn); if (rc) return rc; }
+  return plan_from_circuit_impl(spec, units_csv, nullptr, out, window_div, kn);
+  GSV_CATCH
+}
+int gsv_plan_from_circuit(const char* spec, const char* units_csv, gsv_plan** out) { return gsv_plan_from_circuit_div(spec, units_csv, 0, out); }
 int gsv_plan_io(const gsv_plan* p, uint64_t* n_inputs, uint64_t* n_outputs) {
   if (!p || !p->finished) return fail(GSV_ERR_INVALID, "plan not finished");
   if (n_inputs) *n_inputs = p->n_inputs;
@@ -298,10 +300,10 @@ class PlanFileWriter {
 using namespace gsv_plan_file;
 
 // ---- background compilation (gsv_program_compile_opts) -------------------------------------------------------------------------------
-// One pool for the process, created on first use: GSV_COMPILE_THREADS workers (default: the hardware's, at most 16).  submit() blocks while
+// One pool for the process, created on first use with that call's `threads` (knobs::compile_threads).  submit() blocks while
 // as many jobs as workers are queued, which bounds the traces and compiler temporaries in flight.
-static CompilePool& abi_compile_pool() {
-  static CompilePool pool(plan_compile_threads());
+static CompilePool& abi_compile_pool(size_t threads) {
+  static CompilePool pool(threads);
   return pool;
 }
 // Waits for a program's background compilation (no-op otherwise) and returns its status.
@@ -436,14 +438,14 @@ int gsv_plan_recorder_finish(gsv_plan_recorder* r, const uint64_t* output_wires,
   if (!r || !out || (!output_wires && n_outputs)) return fail(GSV_ERR_INVALID, "null argument");
   if (r->finished) return fail(GSV_ERR_INVALID, "plan recorder already finished");
   GSV_TRY
+  const knobs::PlanBuild kn;
   std::vector<uint32_t> out_ssa;
   for (size_t i = 0; i < n_outputs; ++i) out_ssa.push_back(r->mode.current(output_wires[i]));
-  CompileOptions opt;
-  if (const char* e = getenv("GSV_FUSE")) opt.fuse = atoi(e) != 0;
+  CompileOptions opt = kn.opt;
   if (r->single_image) opt.lds_slots = std::min<uint32_t>(opt.lds_slots, LDS_WINDOW_SLOTS / r->window_div);
   r->wait_for_compilations();
   for (const gsv_program* q : r->externals) { int rc = program_ready(q); if (rc) return rc; }
-  BuiltPlan bp = finish_plan(r->mode, r->inputs, out_ssa, opt);
+  BuiltPlan bp = finish_plan(r->mode, r->inputs, out_ssa, opt, kn);
   r->finished = true;
   std::unique_ptr<gsv_plan> plan(new gsv_plan());
   for (size_t k = 0; k < bp.programs.size(); ++k) {
@@ -484,6 +486,8 @@ static int compile_impl(gsv_recorder* r, const uint32_t* fb_out_idx, const uint3
   if (!r->outputs_declared) return fail(GSV_ERR_INVALID, "outputs not declared");
   if (o && o->struct_size != sizeof(gsv_compile_opts)) return fail(GSV_ERR_INVALID, "gsv_compile_opts.struct_size does not match this library");
   GSV_TRY
+  CompileOptions opt = knobs::compile_options(knobs::Scope::Program);
+  const size_t pool_threads = knobs::compile_threads();
   gsv_plan_recorder* const pr = o ? o->for_plan : nullptr;
   uint32_t window_div = o ? o->window_div : 0;
   if (window_div != 0 && window_div != 1 && window_div != 2 && window_div != 4) return fail(GSV_ERR_INVALID, "window_div must be 0, 1, 2 or 4");
@@ -499,13 +503,6 @@ static int compile_impl(gsv_recorder* r, const uint32_t* fb_out_idx, const uint3
   auto fb = std::make_shared<std::vector<std::pair<uint32_t, uint32_t>>>();
   for (size_t i = 0; i < n_feedback; ++i) fb->push_back({fb_out_idx[i], fb_in_idx[i]});
   std::unique_ptr<gsv_program> p(new gsv_program());
-  CompileOptions opt;
-  if (const char* e = getenv("GSV_LDS_LIFETIME")) opt.lds_max_lifetime = uint32_t(atoi(e));  // tuning knobs (defaults are the measured best)
-  if (const char* e = getenv("GSV_FUSE")) opt.fuse = atoi(e) != 0;
-  if (const char* e = getenv("GSV_FUSE_DUP")) opt.fuse_dup_fanout = uint32_t(atoi(e));
-  if (const char* e = getenv("GSV_ORDER_BY_READER")) opt.order_by_reader = atoi(e) != 0;
-  if (const char* e = getenv("GSV_HBM_ARENA")) opt.hbm_arena_factor = uint32_t(atoi(e));
-  if (const char* e = getenv("GSV_LDS_SLOTS")) opt.lds_slots = std::min<uint32_t>(uint32_t(atoi(e)), LDS_WINDOW_SLOTS);
   if (window_div > 1 || (pr && pr->single_image)) opt.lds_slots = std::min<uint32_t>(opt.lds_slots, LDS_WINDOW_SLOTS / window_div);
   p->window_div = window_div;
   p->has_decl = true;
@@ -532,7 +529,7 @@ static int compile_impl(gsv_recorder* r, const uint32_t* fb_out_idx, const uint3
   if (pr) { std::lock_guard<std::mutex> lk0(g_recorder_link_mu); std::lock_guard<std::mutex> lk(pr->mu); pr->compiled_for.push_back(q); q->for_recorder = pr; }
   if (o && o->background) {
     q->compiling = true;
-    abi_compile_pool().submit([q, work] {
+    abi_compile_pool(pool_threads).submit([q, work] {
       auto res = work();
       { std::lock_guard<std::mutex> lk(q->cmu); q->compile_rc = res.first; q->compile_err = res.second; q->compiling = false; }
       q->ccv.notify_all();
@@ -592,7 +589,7 @@ int gsv_plan_save(const gsv_plan* p, const char* path) {
 }
 // Build a plan and write it to `path` without ever holding it: every program is appended to the file by the worker that compiled
 // it and its records are dropped (the verifier's plan is 41 GB of records; built in memory it peaks at ~54 GB of host RSS).
-// Load the file with gsv_plan_load (with an engine: streamed to the device).  One image per program: GSV_PLAN_WINDOW_DIV=2|4.
+// Load the file with gsv_plan_load (with an engine: streamed to the device).  One image per program, for 1 / window_div of the LDS window.
 static std::function<void(Program&)> spill_to(PlanFileWriter& w, uint32_t window_div) {
   return [&w, window_div](Program& g) {
     g.file_off = w.append_program(g, window_div);
@@ -610,20 +607,21 @@ static int finish_built_file(PlanFileWriter& w, const gsv_plan* plan) {
   }
   return w.finish(plan, off, index);
 }
-int gsv_plan_build_file(const char* spec, const char* units_csv, const char* path) {
+int gsv_plan_build_file_div(const char* spec, const char* units_csv, const char* path, uint32_t window_div) {
   if (!spec || !units_csv || !path) return fail(GSV_ERR_INVALID, "null argument");
   GSV_TRY
-  uint32_t window_div = 1;
-  { int rc = plan_window_div(&window_div); if (rc) return rc; }
+  const knobs::PlanBuild kn;
+  { int rc = resolve_window_div(&window_div, kn); if (rc) return rc; }
   PlanFileWriter w;
   { int rc = w.open_file(path); if (rc) return rc; }
   gsv_plan* plan = nullptr;
-  int rc = plan_from_circuit_impl(spec, units_csv, spill_to(w, window_div), &plan, window_div);
+  int rc = plan_from_circuit_impl(spec, units_csv, spill_to(w, window_div), &plan, window_div, kn);
   if (rc) return rc;
   struct PlanOwner { gsv_plan* p; ~PlanOwner() { gsv_plan_destroy(p); } } po{plan};
   return finish_built_file(w, plan);
   GSV_CATCH
 }
+int gsv_plan_build_file(const char* spec, const char* units_csv, const char* path) { return gsv_plan_build_file_div(spec, units_csv, path, 0); }
 // TWO plan files from ONE recording of the circuit: every program is compiled twice — for 1 / window_div_a and for 1 / window_div_b of the
 // LDS label window — by the worker that takes it off the recorder, and appended to both files.  A deployment that serves large batches
 // (four instances per workgroup: window_div 4) AND small ones (full window: window_div 1) builds both plans for the price of one
@@ -635,13 +633,14 @@ int gsv_plan_build_file_pair(const char* spec, const char* units_csv_a, const ch
   for (uint32_t d : {window_div_a, window_div_b}) if (d != 1 && d != 2 && d != 4) return fail(GSV_ERR_INVALID, "window_div must be 1, 2 or 4");
   if (std::string(path_a) == path_b) return fail(GSV_ERR_INVALID, "the two plan files must differ");
   GSV_TRY
+  const knobs::PlanBuild kn;
   PlanFileWriter wa, wb;
   { int rc = wa.open_file(path_a); if (rc) return rc; }
   { int rc = wb.open_file(path_b); if (rc) return rc; }
   gsv_plan *plan_a = nullptr, *plan_b = nullptr;
   DualBuild dual;
   dual.units_csv = units_csv_b; dual.window_div = window_div_b; dual.sink = spill_to(wb, window_div_b); dual.out = &plan_b;
-  int rc = plan_from_circuit_impl(spec, units_csv, spill_to(wa, window_div_a), &plan_a, window_div_a, &dual);
+  int rc = plan_from_circuit_impl(spec, units_csv, spill_to(wa, window_div_a), &plan_a, window_div_a, kn, &dual);
   if (rc) return rc;
   struct PlanOwner { gsv_plan* p; ~PlanOwner() { gsv_plan_destroy(p); } } oa{plan_a}, ob{plan_b};
   rc = finish_built_file(wa, plan_a);

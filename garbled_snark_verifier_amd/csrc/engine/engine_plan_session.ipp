@@ -7,7 +7,7 @@ int gsv_session_create_plan_ex(gsv_engine* e, const gsv_plan* plan, size_t n_ins
 }
 // The call-level schedule of a plan session (schedule.hpp) for `n_wg` workgroups per call on a device with `n_cus` CUs.
 static int install_schedule(gsv_session* s, const gsv_plan_session_opts& o, int n_cus, size_t free_b);
-static Schedule make_schedule(const gsv_plan* plan, uint32_t ni, size_t n_instances, int n_cus, size_t free_bytes, const gsv_plan_session_opts& o, uint64_t* max_call_ct) {
+static Schedule make_schedule(const gsv_plan* plan, uint32_t ni, size_t n_instances, int n_cus, size_t free_bytes, const gsv_plan_session_opts& o, const knobs::Sched& kn, uint64_t* max_call_ct) {
   std::vector<SchedCall> calls(plan->calls.size());
   uint64_t max_block = 0;
   uint32_t max_slots = 0;
@@ -25,7 +25,7 @@ static Schedule make_schedule(const gsv_plan* plan, uint32_t ni, size_t n_instan
   const size_t n_wg = (n_instances + ni - 1) / ni;
   // calls side by side: as many as it takes to give every CU a workgroup (GSV_PLAN_CONCURRENCY / opts override)
   uint32_t conc = o.max_concurrent_calls ? o.max_concurrent_calls : uint32_t(std::max<size_t>(1, size_t(n_cus) / std::max<size_t>(1, n_wg)));
-  if (!o.max_concurrent_calls) if (const char* ev = getenv("GSV_PLAN_CONCURRENCY")) conc = uint32_t(std::max(1, atoi(ev)));
+  if (!o.max_concurrent_calls && kn.plan_concurrency) conc = kn.plan_concurrency;
   // a session that drains its stream leaves a few CUs to the gather kernels that bring finished segments into gate order beside the
   // running window (a workgroup of the garbling kernel takes a whole CU, also while it waits for a dependency)
   if (!o.max_concurrent_calls && o.retain_stream != 1 && conc > 1 && n_wg * size_t(conc) + 16 > size_t(n_cus)) conc = uint32_t(std::max<size_t>(1, (size_t(n_cus) - std::min<size_t>(16, size_t(n_cus) / 2)) / n_wg));
@@ -55,7 +55,7 @@ static Schedule make_schedule(const gsv_plan* plan, uint32_t ni, size_t n_instan
   // gate-order buffers of that size would take more than a tenth of the free memory; never smaller than the largest call.
   {
     uint64_t sg = o.drain_segment_records ? o.drain_segment_records : std::min<uint64_t>(uint64_t(double(free_bytes) * 0.1 / (3.0 * 16.0) / double(std::max<size_t>(1, n_instances))), 1ull << 26);
-    if (const char* ev = getenv("GSV_DRAIN_SEGMENT_RECORDS")) if (!o.drain_segment_records) sg = uint64_t(std::max(1ll, atoll(ev)));
+    if (kn.drain_segment_records && !o.drain_segment_records) sg = kn.drain_segment_records;
     sp.segment_ct = std::min<uint64_t>(std::max<uint64_t>(sg, max_block), sp.max_window_ct);
   }
   // Ciphertext ring (schedule.hpp), retain_stream = GSV_STREAM_RING or GSV_CT_RING=1 in the environment: a session that does not
@@ -66,10 +66,10 @@ static Schedule make_schedule(const gsv_plan* plan, uint32_t ni, size_t n_instan
   // 32.9 s vs 32.5-33.4 s for sixteen), and a ring makes the running launch WAIT for the host — it must never share a hardware queue
   // with the side streams (create_side_stream).  Not with an explicit window_ct_records (the caller sizes the launches: garble ||
   // evaluate pairs, tests), not for sequential sessions, and not when the whole stream fits the ring anyway.
-  const bool ring_wanted = o.retain_stream == GSV_STREAM_RING || (o.retain_stream == 0 && getenv("GSV_CT_RING") && atoi(getenv("GSV_CT_RING")) == 1);
+  const bool ring_wanted = o.retain_stream == GSV_STREAM_RING || (o.retain_stream == 0 && kn.ct_ring);
   if (ring_wanted && !o.window_ct_records && conc > 1) {
     uint64_t ring = std::max<uint64_t>(3 * sp.segment_ct, 2 * sp.segment_ct + max_block);
-    if (const char* ev = getenv("GSV_CT_RING_RECORDS")) ring = std::max<uint64_t>(uint64_t(std::max(1ll, atoll(ev))), 2 * sp.segment_ct + max_block);  // tests: small rings on small circuits
+    if (kn.ct_ring_records) ring = std::max<uint64_t>(kn.ct_ring_records, 2 * sp.segment_ct + max_block);  // tests: small rings on small circuits
     if (ring < plan->n_ct && ring <= sp.max_window_ct) { sp.ring_ct = ring; sp.max_window_ct = ~0ull; }
   }
   sp.max_window_calls = std::min<uint32_t>(o.max_window_calls ? o.max_window_calls : 32768u, 65535u);
@@ -78,7 +78,7 @@ static Schedule make_schedule(const gsv_plan* plan, uint32_t ni, size_t n_instan
     const std::string err = verify_ring_bounds(calls, sc);
     if (!err.empty()) gsv_panic("plan schedule: " + err);
   }
-  if (getenv("GSV_PLAN_DEBUG") || getenv("GSV_VERIFY_SCHEDULE")) {
+  if (kn.verify) {
     const std::string err = verify_schedule(calls, plan->n_globals, plan->outputs, sc);
     if (!err.empty()) gsv_panic("internal: plan schedule violates a hazard: " + err);
     std::fprintf(stderr, "plan schedule: %zu calls, %zu windows, <= %u calls in flight (width %u), scratch ring %llu slots, depth %llu of %llu steps, %zu dependencies\n", calls.size(),
@@ -101,7 +101,7 @@ int gsv_session_create_plan_opts(gsv_engine* e, const gsv_plan* plan, size_t n_i
   {
     uint32_t servable = 4;
     for (const auto& c : plan->calls) if (!c.prog->src) servable = std::min(servable, c.prog->window_div);
-    s->ni = choose_instances_per_wg(n_instances, prop.multiProcessorCount, servable);
+    s->ni = choose_instances_per_wg(n_instances, prop.multiProcessorCount, servable, s->kn.instances_per_wg);
   }
   s->call_dev.resize(plan->calls.size());
   if (s->ni > 1) {  // the plan's programs are independent: compile their missing window variants in parallel
@@ -109,7 +109,7 @@ int gsv_session_create_plan_opts(gsv_engine* e, const gsv_plan* plan, size_t n_i
     std::vector<gsv_program*> todo;
     for (const auto& c : plan->calls) if (std::find(todo.begin(), todo.end(), c.prog) == todo.end()) todo.push_back(c.prog);
     const uint32_t ni = s->ni;
-    parallel_for_programs(todo.size(), [&](size_t i) { std::lock_guard<std::mutex> lk(todo[i]->mu); compile_window_variant(todo[i], ni); });
+    parallel_for_programs(todo.size(), knobs::compile_threads(), [&](size_t i) { std::lock_guard<std::mutex> lk(todo[i]->mu); compile_window_variant(todo[i], ni); });
     GSV_CATCH
   }
   for (size_t k = 0; k < plan->calls.size(); ++k) {
@@ -148,8 +148,9 @@ static int install_schedule(gsv_session* s, const gsv_plan_session_opts& o, int 
   const gsv_plan* plan = s->plan;
   const size_t n_instances = s->n_inst;
   uint64_t max_call_ct = 0;
+  const knobs::Sched kn;
   GSV_TRY
-  s->sched = make_schedule(plan, s->ni, n_instances, n_cus, free_b, o, &max_call_ct);
+  s->sched = make_schedule(plan, s->ni, n_instances, n_cus, free_b, o, kn, &max_call_ct);
   GSV_CATCH
   const Schedule& sc = s->sched;
   const uint32_t scratch = uint32_t((std::max<uint64_t>(sc.scratch_slots, SLOT_FIRST_INPUT) + 7) / 8 * 8);
@@ -219,7 +220,7 @@ static int install_schedule(gsv_session* s, const gsv_plan_session_opts& o, int 
     }
     // GSV_FAULT_WITHHOLD_DEP=1 (tests): the first dependency of the first call that has one is pointed at the slot nobody writes — on
     // the device exactly what a violated dispatch-order assumption looks like (a dependency that never completes).  Never for the safe schedule.
-    if (!s->safe_mode && getenv("GSV_FAULT_WITHHOLD_DEP") && atoi(getenv("GSV_FAULT_WITHHOLD_DEP")) == 1)
+    if (!s->safe_mode && kn.fault_withhold_dep)
       for (size_t k = 0; k < n; ++k) if (cds[k].n_deps) { deps[cds[k].dep_off] = s->flag_stride - 2; break; }
     // one flag row per instance: the rows are indexed by blockIdx.x, and a session switched to BLAKE3 after its creation launches one
     // workgroup per instance whatever s->ni says (gsv_session::launch_ni) — flag_stride * 4 bytes per instance
@@ -409,7 +410,7 @@ static int launch(gsv_session* s, uint64_t gate_id_base, bool eval, uint64_t rep
   ka.and_terms = g.and_terms; ka.any_four_wire = g.and_terms == 4;
   ka.step_clock = static_cast<unsigned long long*>(s->step_clock);
   ka.instances_per_wg = s->launch_ni();
-  if (const char* dg = getenv("GSV_DIAG")) ka.diag = uint32_t(atoi(dg));  // timing experiments (libgsv_engine_diag.so only): outputs are wrong when set
+  ka.diag = s->pass.diag;
   HIPCHK(hipEventRecord(s->ev0, s->e->stream));
   if (ka.n_steps) {
     int lrc = gsvk_launch_program(&ka, uint32_t(s->n_inst), eval ? 1 : 0, s->e->stream);
@@ -442,19 +443,14 @@ static int launch_plan_window(gsv_session* s, size_t w, uint64_t gate_id_base, b
     __atomic_thread_fence(__ATOMIC_RELEASE);
   }
   ka.flag_stride = s->flag_stride; ka.epoch = ++s->epoch;
-  {
-    // dependency watchdog (kernels.hip): seconds without ANY completed call of the instance group before a wait gives up
-    double secs = 60.0;
-    if (const char* ev = getenv("GSV_DEP_WAIT_SECONDS")) { char* end = nullptr; const double v = std::strtod(ev, &end); if (end != ev && v > 0) secs = v; }
-    ka.wait_ticks = (unsigned long long)(std::min(secs, 86400.0) * 1e8);
-  }
+  ka.wait_ticks = (unsigned long long)(s->pass.dep_wait_seconds * 1e8);  // dependency watchdog (kernels.hip): seconds without ANY completed call of the instance group before a wait gives up
   ka.W = static_cast<uint4*>(s->W); ka.VB = static_cast<uint8_t*>(s->VB); ka.CT = static_cast<uint4*>(ct_block);
   ka.delta = static_cast<const uint4*>(s->delta); ka.te = static_cast<const uint32_t*>(s->e->te);
   ka.ct_stride = s->ct_stride(); ka.gid_base = gate_id_base; ka.n_gates = 0; ka.n_ct = 0;
   ka.n_steps = 0; ka.n_slots = f.n_slots; ka.replays = 1; ka.rep_base = 0; ka.ct_cap_replays = 1;
   ka.n_instances = uint32_t(s->n_inst); ka.hasher = uint32_t(s->hasher); ka.instances_per_wg = s->launch_ni();
   for (uint32_t k = win.call0; k < win.call1 && !ka.any_four_wire; ++k) ka.any_four_wire = s->call_prog(k).and_terms == 4;
-  if (const char* dg = getenv("GSV_DIAG")) ka.diag = uint32_t(atoi(dg));  // timing experiments (libgsv_engine_diag.so only): outputs are wrong when set
+  ka.diag = s->pass.diag;
   int lrc = gsvk_launch_batch(&ka, uint32_t(s->n_inst), win.call1 - win.call0, eval ? 1 : 0, stream);
   if (lrc != 0) return fail(GSV_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipError_t(lrc)));
   return GSV_OK;
@@ -538,6 +534,7 @@ static int launch_plan(gsv_session* s, uint64_t gate_id_base, bool eval) {
 
 int gsv_session_garble(gsv_session* s, uint64_t gate_id_base) {
   if (!s) return fail(GSV_ERR_INVALID, "null session");
+  s->pass = knobs::Pass();  // this pass's knobs
   int rc = launch(s, gate_id_base, false);
   if (rc == GSV_OK) s->garbled = true;
   return rc;

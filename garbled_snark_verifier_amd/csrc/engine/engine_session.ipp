@@ -13,10 +13,9 @@ static void compile_window_variant(gsv_program* p, uint32_t ni) {
   p->variants[ni] = std::move(q);
 }
 // Instances per workgroup of a session: as many (1, 2, 4) as keep every CU busy — the latency-bound narrow steps then cost their fixed
-// time once for all of them (kernels.hip) — limited to what the programs can serve; GSV_INSTANCES_PER_WG=1|2|4 overrides.
-static uint32_t choose_instances_per_wg(size_t n_instances, int n_cus, uint32_t max_servable) {
-  uint32_t ni = n_instances > 2 * size_t(n_cus) ? 4u : n_instances > size_t(n_cus) ? 2u : 1u;
-  if (const char* ev = getenv("GSV_INSTANCES_PER_WG")) { int v = atoi(ev); if (v == 1 || v == 2 || v == 4) ni = uint32_t(v); }
+// time once for all of them (kernels.hip) — limited to what the programs can serve; `forced` (GSV_INSTANCES_PER_WG=1|2|4, 0 = not set) overrides.
+static uint32_t choose_instances_per_wg(size_t n_instances, int n_cus, uint32_t max_servable, uint32_t forced) {
+  uint32_t ni = forced ? forced : n_instances > 2 * size_t(n_cus) ? 4u : n_instances > size_t(n_cus) ? 2u : 1u;
   while (ni > 1 && (ni > max_servable || ni > n_instances)) ni /= 2;
   return ni;
 }
@@ -73,7 +72,7 @@ int gsv_session_create(gsv_engine* e, const gsv_program* cp, size_t n_instances,
   {
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, e->device));
-    s->ni = choose_instances_per_wg(n_instances, prop.multiProcessorCount, p->src ? 4u : p->window_div);
+    s->ni = choose_instances_per_wg(n_instances, prop.multiProcessorCount, p->src ? 4u : p->window_div, s->kn.instances_per_wg);
   }
   int rc = upload_program(e, p, s->ni, &s->dp);
   if (rc) return rc;

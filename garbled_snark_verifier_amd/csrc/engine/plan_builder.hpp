@@ -28,6 +28,7 @@
 #include <string>
 #include <unordered_map>
 
+#include "knobs.hpp"
 #include "program.hpp"
 
 namespace gsv {
@@ -44,12 +45,6 @@ struct PlanUnit {  // one compiled (component key, output liveness) pair
   std::unique_ptr<Program> compiled;  // set by the background compiler (PlanRecordMode::compile_in_background) before finish_plan
   std::unique_ptr<Program> compiled_b;  // ... and the SECOND image of a dual build (PlanUnitCache::dual): the same trace compiled with bg_opt_b
 };
-
-inline size_t plan_compile_threads() {  // GSV_COMPILE_THREADS, default: the hardware's, at most 16
-  size_t nt = std::thread::hardware_concurrency();
-  if (const char* ev = getenv("GSV_COMPILE_THREADS")) nt = size_t(std::max(1, atoi(ev)));
-  return std::min<size_t>(nt ? nt : 1, 16);
-}
 
 // A small bounded worker pool: unit programs are compiled while the driver keeps recording (the recording is serial, a
 // compilation takes about as long as recording the unit).  submit() blocks while as many jobs as threads are pending, which bounds the
@@ -167,9 +162,9 @@ class PlanRecordMode final : public CircuitMode, public UnitHook {
 
   // Compile every unit as soon as it has been recorded, on a worker pool, with the options finish_plan will be given.
   // drop_traces: free a unit's trace once its program exists (no other variant of the program will be compiled).
-  void compile_in_background(const CompileOptions& opt, bool drop_traces) {
+  void compile_in_background(const CompileOptions& opt, bool drop_traces, size_t threads = knobs::compile_threads()) {
     cache_->bg_opt = opt; cache_->bg_drop = drop_traces;
-    cache_->pool.reset(new CompilePool(plan_compile_threads()));
+    cache_->pool.reset(new CompilePool(threads));
   }
   void wait_for_compilations() { if (cache_->pool) cache_->pool->wait(); }
 
@@ -416,14 +411,14 @@ class PlanRecordMode final : public CircuitMode, public UnitHook {
   uint64_t n_gates_ = 0;
 };
 
-// The recording itself: the two-pass driver walks (n_inputs, fn) on this thread while up to a quarter of the compile threads
-// (GSV_PLAN_WARMUP_THREADS, 0 = none) run the circuit's warm-up mini-circuits, each under a recorder of its own that shares `mode`'s
+// The recording itself: the two-pass driver walks (n_inputs, fn) on this thread while kn.warmup_threads threads (a quarter of the compile
+// threads; 0 = none) run the circuit's warm-up mini-circuits, each under a recorder of its own that shares `mode`'s
 // unit cache: a unit the warm-ups reach first is recorded (and sent to the compile pool) by them, the driver waits for one that is
 // still being recorded and records what the warm-ups do not cover.  The plan is the same with or without them.
 // Warmup: anything with .n_inputs and .fn (NamedCircuit::Warmup).  in_ssa / out_ssa: the circuit's inputs / outputs for finish_plan.
 template <class Warmup>
 inline void record_plan(PlanRecordMode& mode, size_t n_inputs, const CircuitFn& fn, const std::vector<Warmup>& warmups, std::vector<uint32_t>& in_ssa,
-                        std::vector<uint32_t>& out_ssa, size_t* n_recorders_out = nullptr) {
+                        std::vector<uint32_t>& out_ssa, const knobs::PlanBuild& kn = knobs::PlanBuild(), size_t* n_recorders_out = nullptr) {
   std::atomic<size_t> next{0};
   const size_t n = warmups.size();
   struct Crew {
@@ -433,9 +428,7 @@ inline void record_plan(PlanRecordMode& mode, size_t n_inputs, const CircuitFn& 
   } crew{{}, next, n};
   std::mutex err_mu;
   std::exception_ptr err;
-  size_t nrec = std::max<size_t>(1, plan_compile_threads() / 4);
-  if (const char* e = getenv("GSV_PLAN_WARMUP_THREADS")) nrec = size_t(std::max(0, atoi(e)));
-  nrec = std::min(nrec, n);
+  const size_t nrec = std::min(kn.warmup_threads, n);
   if (n_recorders_out) *n_recorders_out = nrec;
   for (size_t t = 0; t < nrec; ++t)
     crew.th.emplace_back([&] {
@@ -463,11 +456,11 @@ inline void record_plan(PlanRecordMode& mode, size_t n_inputs, const CircuitFn& 
 }
 
 // The finished plan in host form: programs (units first, then one per glue segment) and calls over global wire ids.
-// Runs fn(0 .. n-1) on up to GSV_COMPILE_THREADS (default: the hardware's, at most 16) threads; the first exception is rethrown.
+// Runs fn(0 .. n-1) on up to `threads` threads (knobs::compile_threads); the first exception is rethrown.
 // Programs of a plan are compiled independently of each other (the Miller loop alone has ~190 of them).
 template <class Fn>
-inline void parallel_for_programs(size_t n, Fn&& fn) {
-  const size_t nt = std::min<size_t>(plan_compile_threads(), n);
+inline void parallel_for_programs(size_t n, size_t threads, Fn&& fn) {
+  const size_t nt = std::min<size_t>(threads, n);
   if (nt <= 1) { for (size_t i = 0; i < n; ++i) fn(i); return; }
   std::atomic<size_t> next{0};
   std::exception_ptr err;
@@ -502,7 +495,7 @@ struct BuiltPlan {
 // inputs / outputs: global SSA ids of the circuit's inputs / outputs as PlanRecordMode handed them out.
 // which (dual builds, PlanUnitCache::dual): 0 = the first plan's images (or a plain build), 1 = the SECOND plan's images (compiled_b,
 // bg_opt_b, sink_b — they land in BuiltPlan::programs), 2 = both plans from this one recorder (programs and programs_b).
-inline BuiltPlan finish_plan(PlanRecordMode& m, const std::vector<uint32_t>& inputs, const std::vector<uint32_t>& outputs, const CompileOptions& opt = CompileOptions(), int which = 0) {
+inline BuiltPlan finish_plan(PlanRecordMode& m, const std::vector<uint32_t>& inputs, const std::vector<uint32_t>& outputs, const CompileOptions& opt, const knobs::PlanBuild& kn = knobs::PlanBuild(), int which = 0) {
   m.close_glue();
   m.wait_for_compilations();
   BuiltPlan bp;
@@ -554,14 +547,7 @@ inline BuiltPlan finish_plan(PlanRecordMode& m, const std::vector<uint32_t>& inp
   // that only runs sequential sessions — max_concurrent_calls = 1, where reuse distance buys nothing — builds its plan with
   // GSV_PLAN_ID_SLACK=0 and gets the smallest wire file).
   std::deque<uint32_t> free_ids;
-  size_t id_slack = 262144;
-  if (const char* ev = getenv("GSV_PLAN_ID_SLACK")) {
-    char* end = nullptr;
-    const long long v = std::strtoll(ev, &end, 10);
-    if (end == ev || *end != 0 || v < 0 || v > (1ll << 28)) gsv_panic("GSV_PLAN_ID_SLACK must be an integer in [0, 2^28]");
-    id_slack = size_t(v);
-  }
-  auto alloc_global = [&]() -> uint32_t { if (free_ids.size() > id_slack) { uint32_t g = free_ids.front(); free_ids.pop_front(); return g; } return next_global++; };
+  auto alloc_global = [&]() -> uint32_t { if (free_ids.size() > kn.id_slack) { uint32_t g = free_ids.front(); free_ids.pop_front(); return g; } return next_global++; };
   // released after segment si has read its inputs; each wire once even when a call names it several times
   auto release_dead_inputs = [&](size_t si) {
     for (uint32_t w : m.segments[si].in_ssa)
@@ -650,12 +636,12 @@ inline BuiltPlan finish_plan(PlanRecordMode& m, const std::vector<uint32_t>& inp
   for (BuiltPlan::Call& c : bp.calls) for (uint32_t& g : c.out_globals) if (g < PLAN_WIRE_FALSE && (g & TRASH_FLAG)) g = next_global + (g & ~TRASH_FLAG);
   bp.n_global_ids = next_global;
   for (uint32_t w = 2; w < nw; ++w) if (crossing[w]) ++bp.n_crossing_wires;
-  if (getenv("GSV_PLAN_DEBUG")) std::fprintf(stderr, "plan: %zu segments, %u wires cross calls, %u global ids after recycling (%u inputs pinned)\n", m.segments.size(), bp.n_crossing_wires, next_global, bp.n_inputs);
+  if (kn.debug) std::fprintf(stderr, "plan: %zu segments, %u wires cross calls, %u global ids after recycling (%u inputs pinned)\n", m.segments.size(), bp.n_crossing_wires, next_global, bp.n_inputs);
   for (uint32_t w : outputs) bp.outputs.push_back(w == 0 ? PLAN_WIRE_FALSE : w == 1 ? PLAN_WIRE_TRUE : global_of[w]);
   const std::function<void(Program&)>& sink = m.cache()->sink;
   const std::function<void(Program&)>& sink_b = m.cache()->sink_b;
   const CompileOptions opt_b = m.cache()->bg_opt_b;
-  parallel_for_programs(bp.programs.size(), [&](size_t i) {
+  parallel_for_programs(bp.programs.size(), kn.compile_threads, [&](size_t i) {
     if (done[i]) return;
     if (which == 1) {
       bp.programs[i] = compile_program(bp.traces[i], bp.prog_inputs[i], bp.prog_outputs[i], {}, opt_b);

@@ -178,6 +178,7 @@ struct CompileOptions {
   // per step on average (latency-bound: fewer steps matter), two otherwise (throughput-bound: fewer label loads matter).
   uint32_t and_terms = 0;
   uint32_t narrow_width = 600;
+  bool sched_stats = false;               // print the wire-file coalescing statistics of the compiled program (GSV_SCHED_STATS)
 };
 
 // next-fit slot pool over a bitmap: consecutive allocations get ascending (mostly consecutive) slots, so the
@@ -354,10 +355,7 @@ inline FusedOps fuse_trace(const Trace& t, const std::vector<uint32_t>& inputs, 
 // feedback: pairs (output index -> input index) copied at the end of every replay (chained circuits).
 inline Program compile_program(const Trace& t, const std::vector<uint32_t>& inputs, const std::vector<uint32_t>& outputs,
                                const std::vector<std::pair<uint32_t, uint32_t>>& feedback = {}, const CompileOptions& opt_in = CompileOptions()) {
-  CompileOptions opt = opt_in;
-  if (const char* e = getenv("GSV_AND_CAP")) opt.and_cap = uint32_t(atoi(e));  // tuning knobs (the defaults are the measured best)
-  if (const char* e = getenv("GSV_XOR_CAP")) opt.xor_cap = uint32_t(atoi(e));
-  if (const char* e = getenv("GSV_LDS_SLOTS_CAP")) opt.lds_slots = std::min<uint32_t>(opt.lds_slots, uint32_t(atoi(e)));  // experiments: more instances per workgroup
+  CompileOptions opt = opt_in;  // complete as given: the environment is read by the caller's entry point (knobs.hpp), never here
   const uint32_t nw = t.n_wires;
   Program p;
   p.n_gates = t.size();
@@ -367,7 +365,6 @@ inline Program compile_program(const Trace& t, const std::vector<uint32_t>& inpu
   // 0. Fusion, and how many wires an AND input may take.  Throughput-bound programs (wide steps) keep the two-wire records: every
   // extra operand is a label load on the LDS pipe that the AES needs.  Latency-bound programs (narrow steps: ladders, inversions,
   // carry chains) take four: a free gate that only feeds ANDs then disappears as a step of its own.
-  if (const char* e = getenv("GSV_AND_TERMS")) { const int v = atoi(e); if (v == 0 || v == 2 || v == 4) opt.and_terms = uint32_t(v); }
   if (!opt.fuse) opt.and_terms = 2;
   FusedOps f = fuse_trace(t, inputs, outputs, opt, opt.and_terms == 4 ? 4u : 2u);
   p.and_terms = opt.and_terms == 4 ? 4u : 2u;
@@ -609,7 +606,7 @@ inline Program compile_program(const Trace& t, const std::vector<uint32_t>& inpu
     p.max_step_width = std::max(p.max_step_width, sd.and_cnt + sd.xor_cnt);
     if (sd.and_cnt) p.n_and_steps++;
   }
-  if (getenv("GSV_SCHED_STATS") && p.and_terms == 2) {
+  if (opt.sched_stats && p.and_terms == 2) {
     // coalescing of the wire-file accesses: distinct 128-byte lines (8 slots) per wave-wide access (64 consecutive records of a step)
     uint64_t acc[2] = {0, 0}, lines[2] = {0, 0}, lanes[2] = {0, 0};
     std::vector<uint32_t> ls;

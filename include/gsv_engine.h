@@ -195,6 +195,9 @@ int gsv_plan_load(const char* path, gsv_engine* e, gsv_plan** out);
  * ~25 GB instead of ~54 GB).  One image per program: GSV_PLAN_WINDOW_DIV=2|4 as below, or 1 = the full window, for sessions with one
  * instance per workgroup only (small batches: 3 % faster steps).  Then gsv_plan_load(path, engine). */
 int gsv_plan_build_file(const char* circuit_spec, const char* units_csv, const char* path);
+/* ... with the window share as a parameter: window_div 1, 2 or 4, or 0 = as GSV_PLAN_WINDOW_DIV / GSV_PLAN_HALF_WINDOW say (what
+ * gsv_plan_build_file passes); anything else is GSV_ERR_INVALID.  A non-zero value wins over the environment, which is not touched. */
+int gsv_plan_build_file_div(const char* circuit_spec, const char* units_csv, const char* path, uint32_t window_div);
 /* TWO plan files from ONE build (round 6): plan A = (units_csv_a, 1 / window_div_a of the LDS label window), plan B likewise (window_div 1,
  * 2 or 4; units_csv_b NULL = plan A's units).  The units the two plans share are recorded ONCE — the verifier's 182 constant line
  * functions are 3.3 B of the 3.5 B gates a build records, whichever granularity the Fq12 arithmetic around them is cut at — and compiled
@@ -215,6 +218,8 @@ int gsv_plan_build_file_pair(const char* circuit_spec, const char* units_csv_a, 
  * then serves sessions with up to that many instances per workgroup and the recorded traces are freed (the verifier plan: 50 GB
  * of host memory instead of 92); unset, programs are compiled for the full window and the other layouts on first use. */
 int gsv_plan_from_circuit(const char* spec, const char* units_csv, gsv_plan** out);
+/* ... with the window share as a parameter (window_div as for gsv_plan_build_file_div; gsv_plan_from_circuit passes 0). */
+int gsv_plan_from_circuit_div(const char* spec, const char* units_csv, uint32_t window_div, gsv_plan** out);
 
 /* ---- engine --------------------------------------------------------------------------------- */
 int gsv_engine_create(int device, gsv_engine** out); /* fails with GSV_ERR_DEVICE if no HIP device */

@@ -13,6 +13,7 @@
 
 #include "../../garbled_snark_verifier_amd/csrc/engine/gate_math.hpp"
 #include "../../garbled_snark_verifier_amd/csrc/engine/host_crypto.hpp"
+#include "../../garbled_snark_verifier_amd/csrc/engine/knobs.hpp"
 #include "../../garbled_snark_verifier_amd/csrc/engine/plan_builder.hpp"
 #include "../../garbled_snark_verifier_amd/csrc/engine/program.hpp"
 #include "../../garbled_snark_verifier_amd/csrc/engine/schedule.hpp"
@@ -46,9 +47,7 @@ int hostsim_compile(const char* spec, int chain_feedback, SimProgram** out, uint
     std::vector<std::pair<uint32_t, uint32_t>> fb;
     if (chain_feedback) for (uint32_t i = 0; i < out_ssa.size(); ++i) fb.push_back({i, i});  // output i -> input i
     auto sp = std::make_unique<SimProgram>();
-    CompileOptions opt;
-    if (const char* e = getenv("GSV_FUSE")) opt.fuse = atoi(e) != 0;  // same knob as the engine (engine.cpp)
-    if (const char* e = getenv("GSV_LDS_SLOTS")) opt.lds_slots = std::min<uint32_t>(uint32_t(atoi(e)), LDS_WINDOW_SLOTS);
+    const CompileOptions opt = knobs::compile_options(knobs::Scope::Program);  // the same knobs as gsv_program_compile
     sp->prog = compile_program(mode.trace(), in_ssa, out_ssa, fb, opt);
     const Program& g = sp->prog;
     if (info) {
@@ -188,15 +187,15 @@ int hostsim_plan_build(const char* spec, const char* units_csv, SimPlan** out, u
     }
     NamedCircuit nc = make_circuit(spec);
     PlanRecordMode mode(names);
-    CompileOptions opt;
-    if (const char* e = getenv("GSV_FUSE")) opt.fuse = atoi(e) != 0;
-    if (getenv("HOSTSIM_PLAN_BACKGROUND")) mode.compile_in_background(opt, false);  // the engine's way: units compiled on the pool while recording goes on
+    const knobs::PlanBuild kn;  // the same knobs as gsv_plan_from_circuit
+    const CompileOptions opt = kn.opt;
+    if (knobs::is_set("HOSTSIM_PLAN_BACKGROUND")) mode.compile_in_background(opt, false, kn.compile_threads);  // the engine's way: units compiled on the pool while recording goes on
     std::vector<uint32_t> in_ssa, out_ssa;
-    record_plan(mode, nc.n_inputs, nc.fn, nc.warmups, in_ssa, out_ssa);  // as gsv_plan_from_circuit: warm-up recorders beside the driver
+    record_plan(mode, nc.n_inputs, nc.fn, nc.warmups, in_ssa, out_ssa, kn);  // as gsv_plan_from_circuit: warm-up recorders beside the driver
     mode.wait_for_compilations();
     auto sp = std::make_unique<SimPlan>();
     const size_t n_units = mode.units.size();
-    sp->bp = finish_plan(mode, in_ssa, out_ssa, opt);
+    sp->bp = finish_plan(mode, in_ssa, out_ssa, opt, kn);
     if (sp->bp.n_gates != mode.n_gates()) gsv_panic("plan gate count differs from the recorded stream");
     uint32_t n_globals = sp->bp.n_inputs;
     for (auto& c : sp->bp.calls) {

@@ -7,8 +7,6 @@ completion flags or drain segments.
 Wire ids of the flat list: 0 / 1 the constants, the plan recorder's own ids for every wire the plan level sees (inputs, glue wires,
 call outputs), ids from 2^40 on for the wires inside a call.
 """
-import os
-
 import numpy as np
 
 import gate_list_ref as G
@@ -25,15 +23,8 @@ class Unit:
     def __init__(self, gsv, rec, name, terms, n_inputs, shapes):
         self.name, self.terms, self.n_inputs, self.shapes = name, terms, n_inputs, shapes
         self.gates, self.outputs, _ = S.build_layered(shapes, n_inputs=n_inputs)
-        saved = os.environ.get("GSV_AND_TERMS")
-        os.environ["GSV_AND_TERMS"] = str(terms)
-        try:
+        with S.and_terms_env(terms):
             self.prog = gsv.Program.from_gates(n_inputs, self.gates, self.outputs, for_plan=rec)
-        finally:
-            if saved is None:
-                del os.environ["GSV_AND_TERMS"]
-            else:
-                os.environ["GSV_AND_TERMS"] = saved
         self.n_outputs = len(self.outputs)
         self.n_ct = sum(1 for g in self.gates if g[3] is not None and g[0] < 8)
         self.n_dead = sum(1 for g in self.gates if g[3] is None)

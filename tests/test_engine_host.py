@@ -424,6 +424,106 @@ def test_plan_from_circuit_builds_without_a_device_and_in_both_modes():
     plan.close()
 
 
+FQ12_MIX_UNITS = ["fq12::mul_montgomery", "fq12::square_montgomery"]
+_explicit_fq12_mix = {}
+
+
+def _plan_file_digest(path):
+    if os.path.join(ROOT, "tools") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import plan_digest
+    return plan_digest.digest(path)["digest"]
+
+
+def _fq12_mix_fingerprint(tmp_path, **kw):
+    """(info, image bytes, per-call table, digest of the saved plan) of the fq12_mix plan Plan.from_circuit builds with `kw` in the
+    environment as it stands.  The first three do not depend on the window share; the saved plan (tools/plan_digest.py) does."""
+    import garbled_snark_verifier_amd as gsv
+    plan = gsv.Plan.from_circuit("fq12_mix", FQ12_MIX_UNITS, **kw)
+    path = os.path.join(str(tmp_path), "fingerprint.gsvplan")
+    plan.save(path)
+    fp = (dict(plan.info), plan.image_bytes(), plan.call_info().tobytes(), _plan_file_digest(path))
+    os.remove(path)
+    plan.close()
+    return fp
+
+
+def _explicit_fingerprint(tmp_path, div):
+    """... with window_div=div as an argument (it wins over the environment: test_explicit_window_div_wins...); built once per process."""
+    if div not in _explicit_fq12_mix:
+        _explicit_fq12_mix[div] = _fq12_mix_fingerprint(tmp_path, window_div=div)
+    return _explicit_fq12_mix[div]
+
+
+@pytest.mark.parametrize("div,env", [(4, {"GSV_PLAN_WINDOW_DIV": "4"}), (2, {"GSV_PLAN_HALF_WINDOW": "1"})])
+def test_explicit_window_div_equals_the_environment(monkeypatch, tmp_path, div, env):
+    """window_div as a parameter (gsv_plan_from_circuit_div) builds the plan that GSV_PLAN_WINDOW_DIV / GSV_PLAN_HALF_WINDOW and no argument build."""
+    for k in ("GSV_PLAN_WINDOW_DIV", "GSV_PLAN_HALF_WINDOW"):
+        monkeypatch.delenv(k, raising=False)
+    explicit = _explicit_fingerprint(tmp_path, div)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    assert _fq12_mix_fingerprint(tmp_path) == explicit
+    assert explicit[3] != _explicit_fingerprint(tmp_path, 6 - div)[3]  # (the two shares of the window are different images: the comparison can fail)
+
+
+def test_explicit_window_div_wins_and_leaves_the_environment_alone(monkeypatch, tmp_path):
+    import garbled_snark_verifier_amd as gsv
+    monkeypatch.delenv("GSV_PLAN_HALF_WINDOW", raising=False)
+    monkeypatch.delenv("GSV_PLAN_WINDOW_DIV", raising=False)
+    clean, under = os.path.join(str(tmp_path), "clean.gsvplan"), os.path.join(str(tmp_path), "under.gsvplan")
+    gsv.Plan.build_file("fq12_mix", FQ12_MIX_UNITS, clean, window_div=1)
+    div4 = _explicit_fingerprint(tmp_path, 4)
+    monkeypatch.setenv("GSV_PLAN_WINDOW_DIV", "2")
+    assert _fq12_mix_fingerprint(tmp_path, window_div=4) == div4 and div4[3] != _explicit_fingerprint(tmp_path, 2)[3]
+    gsv.Plan.build_file("fq12_mix", FQ12_MIX_UNITS, under, window_div=1)  # explicit, 1 included
+    assert _plan_file_digest(under) == _plan_file_digest(clean)
+    assert os.environ["GSV_PLAN_WINDOW_DIV"] == "2" and "GSV_PLAN_HALF_WINDOW" not in os.environ
+
+
+class _FrozenEnviron(dict):
+    """os.environ's content; any mutation raises."""
+
+    def _refuse(self, *a, **kw):
+        raise AssertionError("the package wrote the process environment")
+
+    __setitem__ = __delitem__ = pop = popitem = clear = update = setdefault = __ior__ = _refuse
+
+
+def test_the_package_does_not_write_the_environment(monkeypatch, tmp_path):
+    """Plan.from_circuit / Plan.build_file pass window_div as an argument: bench.py builds plan files on a thread beside running launches,
+    and a setenv beside the engine's getenv is a data race."""
+    import garbled_snark_verifier_amd as gsv
+    gsv.lib()
+    frozen = _FrozenEnviron(os.environ)
+    with pytest.raises(AssertionError):
+        frozen["GSV_PLAN_WINDOW_DIV"] = "4"
+    with pytest.raises(AssertionError):
+        frozen.pop("GSV_PLAN_HALF_WINDOW", None)
+    path = os.path.join(str(tmp_path), "frozen.gsvplan")
+    with monkeypatch.context() as m:  # (undone before pytest's own bookkeeping writes PYTEST_CURRENT_TEST)
+        m.setattr(os, "environ", frozen)
+        for kw in ({"window_div": 4}, {"half_window": True}):
+            plan = gsv.Plan.from_circuit("fq12_mix", FQ12_MIX_UNITS, **kw)
+            assert plan.info["n_calls"] >= 4
+            plan.close()
+        gsv.Plan.build_file("fq12_mix", FQ12_MIX_UNITS, path, window_div=4)
+        assert os.environ is frozen
+    assert os.path.getsize(path) > 0
+
+
+def test_window_div_entry_points_reject_a_bad_value(tmp_path):
+    import ctypes as C
+    import garbled_snark_verifier_amd as gsv
+    L, h = gsv.lib(), C.c_void_p()
+    units = ",".join(FQ12_MIX_UNITS).encode()
+    path = os.path.join(str(tmp_path), "bad.gsvplan")
+    GSV_ERR_INVALID = 1
+    assert L.gsv_plan_from_circuit_div(b"fq12_mix", units, 3, C.byref(h)) == GSV_ERR_INVALID and not h.value
+    assert L.gsv_plan_build_file_div(b"fq12_mix", units, os.fsencode(path), 3) == GSV_ERR_INVALID
+    assert b"window_div" in L.gsv_last_error() and not os.listdir(str(tmp_path))
+
+
 def test_step_barrier_isa_check():
     """build.check_step_barrier_isa: the step barrier of run_program_kernel is `s_waitcnt lgkmcnt(0); s_barrier` with the record
     prefetch issued right in front of it — no wait for vector memory: label stores to the HBM wire file are ordered for the

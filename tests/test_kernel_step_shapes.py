@@ -21,6 +21,7 @@ compiled step k holds exactly (a_k, x_k) gates, with the (a, x) table DERIVED fr
 Not covered on purpose: in rem_lpg the third alternative of the DUAL branch, `rem <= 2*(BT/LPG)`, sits behind the wider
 `rem <= 2*(BT/LPG2)` and cannot be taken (LPG2 < LPG); no shape is invented for it.
 """
+import contextlib
 import os
 import random
 import re
@@ -220,6 +221,14 @@ def build_layered(shapes, n_inputs=N_INPUTS):
     return gates, outputs, step_of
 
 
+@contextlib.contextmanager
+def and_terms_env(terms):
+    """GSV_AND_TERMS=terms while a program is compiled (a compile knob: read by the entry point that compiles, kept with the program)."""
+    with pytest.MonkeyPatch.context() as mp:  # saves and restores this one variable
+        mp.setenv("GSV_AND_TERMS", str(terms))
+        yield
+
+
 _built = {}
 
 
@@ -229,15 +238,8 @@ def layered_program(gsv, ni, terms):
     if key not in _built:
         shapes = program_shapes(ni, terms)
         gates, outputs, step_of = build_layered(shapes)
-        saved = os.environ.get("GSV_AND_TERMS")
-        os.environ["GSV_AND_TERMS"] = str(terms)
-        try:
+        with and_terms_env(terms):
             prog = gsv.Program.from_gates(N_INPUTS, gates, outputs)
-        finally:
-            if saved is None:
-                del os.environ["GSV_AND_TERMS"]
-            else:
-                os.environ["GSV_AND_TERMS"] = saved
         _built[key] = (gates, outputs, step_of, shapes, prog)
     return _built[key]
 

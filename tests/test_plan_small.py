@@ -332,15 +332,8 @@ def top_program(terms):
     import garbled_snark_verifier_amd as gsv
     if terms not in _top:
         gates, outputs, used = build_top(terms)
-        saved = os.environ.get("GSV_AND_TERMS")
-        os.environ["GSV_AND_TERMS"] = str(terms)
-        try:
+        with S.and_terms_env(terms):
             prog = gsv.Program.from_gates(TOP_INPUTS, gates, outputs, window_div=4)
-        finally:
-            if saved is None:
-                del os.environ["GSV_AND_TERMS"]
-            else:
-                os.environ["GSV_AND_TERMS"] = saved
         _top[terms] = (gates, outputs, used, prog)
     return _top[terms]
 
