@@ -1,6 +1,7 @@
-// Host runtime + C ABI (include/gsv_engine.h) of the MI355X garbling engine: ONE translation unit in seven files.
-// Device memory, streams and events are plain HIP runtime calls; there is NO CPU execution path for
+// Host runtime + C ABI (include/gsv_engine.h) of the MI355X garbling engine: ONE translation unit in eight files.
+// Device memory, streams and events are plain HIP runtime calls behind the owners of hip_owned.hpp; there is NO CPU execution path for
 // garble/evaluate — without a HIP device gsv_engine_create fails with GSV_ERR_DEVICE.
+//   hip_owned.hpp             move-only owners of device buffers, page-locked host buffers, streams and events: the only release calls
 //   engine_internal.hpp       error reporting, device allocation, the deferred-release gate, the objects behind the opaque handles
 //   engine_abi_record.ipp     gsv_recorder_*, gsv_program_*, gsv_engine_*, gsv_labels_from_seed
 //   engine_session.ipp        program sessions

@@ -80,12 +80,7 @@ static void unlink_from_recorder(gsv_program* p);
 static void program_destroy_now(gsv_program* p) {
   (void)program_ready(p);  // a background compilation still writes into it
   unlink_from_recorder(p);  // its plan recorder must not wait on a destroyed program (gsv_plan_recorder_finish / _destroy)
-  std::set<void*> freed;  // a half-window image loaded from a plan file is filed under both layouts
-  for (auto& kv : p->dev) {
-    (void)hipSetDevice(kv.first.first);
-    for (void* q : {kv.second.steps, kv.second.ands, kv.second.xors, kv.second.fb_src, kv.second.fb_dst, kv.second.out_slots, kv.second.ct_pos})
-      if (q && freed.insert(q).second) (void)hipFree(q);
-  }
+  for (auto& kv : p->dev) { (void)hipSetDevice(kv.first.first); kv.second.reset(); }  // each image on its own device
   delete p;
 }
 void gsv_program_destroy(gsv_program* p) {
@@ -118,23 +113,17 @@ int gsv_engine_create(int device, gsv_engine** out) {
   HIPCHK(hipSetDevice(device));
   EnginePtr e(new gsv_engine());
   e->device = device;
-  HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+  HIPCHK(e->stream.create(hipStreamNonBlocking));
   const AesTables& t = AesTables::fixed_key();
-  HIPCHK(hipMalloc(&e->te, sizeof t.te));
-  HIPCHK(hipMemcpy(e->te, t.te, sizeof t.te, hipMemcpyHostToDevice));
+  HIPCHK(e->te.alloc(sizeof t.te));
+  HIPCHK(hipMemcpy(e->te.get(), t.te, sizeof t.te, hipMemcpyHostToDevice));
   if (gsvk_upload_round_keys(t.rk) != 0) return fail(GSV_ERR_DEVICE, "round key upload failed");
   *out = e.release();
   return GSV_OK;
 }
-static void engine_destroy_now(gsv_engine* e) {
-  (void)hipSetDevice(e->device);
-  if (e->te) (void)hipFree(e->te);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
-}
 void gsv_engine_destroy(gsv_engine* e) {
   if (!e) return;
-  release_or_defer([e] { engine_destroy_now(e); });
+  release_or_defer([e] { delete e; });
 }
 uint64_t gsv_deferred_release_count(void) {
   ReleaseGate& g = release_gate();

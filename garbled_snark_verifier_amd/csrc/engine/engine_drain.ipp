@@ -18,7 +18,7 @@ struct gsv_drain {
     hipStream_t acquire() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !idle.empty(); }); hipStream_t st = idle.back(); idle.pop_back(); return st; }
     void release(hipStream_t st) { { std::lock_guard<std::mutex> lk(mu); idle.push_back(st); } cv.notify_one(); }
   } copy_gate;
-  std::vector<hipStream_t> copy_streams;
+  std::vector<Stream> copy_streams;  // (copy_gate hands them out)
   // Instances whose MAC chains one worker advances side by side: four (AES-NI, CbcMacHost::update_interleaved) or, on hosts with
   // VAES + AVX-512 and sessions with at least 128 instances (eight workers' worth), sixteen (update_interleaved16_vaes: one core
   // then MACs ~3 x as many blocks per second, so a node's GPUs need a third of the host cores for their commitments).
@@ -43,21 +43,13 @@ struct gsv_drain {
   }
   int group = 4;
   struct Worker {
-    void* pinned[2][GROUP_MAX] = {};  // two sets of pinned chunk buffers: copy set j+1 while set j is hashed
-    hipEvent_t done = nullptr;    // blocking-sync event: a worker waiting for its copies sleeps instead of spinning on a core
+    MappedHost<uint8_t> pinned[2][GROUP_MAX];  // two sets of pinned chunk buffers: copy set j+1 while set j is hashed
+    Event done;                   // blocking-sync event: a worker waiting for its copies sleeps instead of spinning on a core
   };
   std::vector<Worker> workers;
   uint64_t chunk = 0;  // records per chunk buffer
   std::vector<CbcMacHost> macs;
-  ~gsv_drain() {
-    for (Worker& w : workers) {
-      for (auto& set : w.pinned) for (void*& q : set) if (q) (void)hipHostFree(q);
-      if (w.done) (void)hipEventDestroy(w.done);
-    }
-    for (hipStream_t st : copy_streams) (void)hipStreamDestroy(st);
-  }
 };
-static void destroy_drain(gsv_drain* d) { delete d; }
 static int ensure_drain(gsv_session* s, size_t T, uint64_t seg_records, int group) {
   // records per chunk: 16 MiB by default — measured on the MI355X box (tools/d2h_bw.py) a D2H copy stream moves 39-48 GB/s in 4 MiB
   // pieces and 54-57 GB/s from 16 MiB up; the buffers are page-locked once per session, not per call as in round 1
@@ -65,8 +57,8 @@ static int ensure_drain(gsv_session* s, size_t T, uint64_t seg_records, int grou
   if (s->drain && s->drain->workers.size() >= T && s->drain->chunk == chunk && s->drain->group == group) return GSV_OK;
   std::vector<CbcMacHost> keep;
   if (s->drain) keep = s->drain->macs;
-  destroy_drain(s->drain);
-  s->drain = new gsv_drain();
+  s->drain.reset();
+  s->drain.reset(new gsv_drain());
   gsv_drain& d = *s->drain;
   d.macs = keep;
   d.chunk = chunk;
@@ -76,38 +68,38 @@ static int ensure_drain(gsv_session* s, size_t T, uint64_t seg_records, int grou
   const int n_copy_streams = s->pass.drain_copies;
   bool ok = true;
   for (int k = 0; k < n_copy_streams && ok; ++k) {
-    hipStream_t st;
-    ok = create_side_stream(&st, s->kn.side_stream_priority) == hipSuccess;
-    if (ok) { d.copy_streams.push_back(st); d.copy_gate.idle.push_back(st); }
+    Stream st;
+    ok = create_side_stream(st, s->kn.side_stream_priority) == hipSuccess;
+    if (ok) { d.copy_gate.idle.push_back(st.get()); d.copy_streams.push_back(std::move(st)); }
   }
   d.workers.resize(T);
   for (gsv_drain::Worker& w : d.workers) {
-    for (auto& set : w.pinned) for (int g = 0; g < group; ++g) ok = ok && hipHostMalloc(&set[g], chunk * 16, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&w.done, hipEventBlockingSync | hipEventDisableTiming) == hipSuccess;
+    for (auto& set : w.pinned) for (int g = 0; g < group; ++g) ok = ok && set[g].alloc(chunk * 16, hipHostMallocDefault) == hipSuccess;
+    ok = ok && w.done.create(hipEventBlockingSync | hipEventDisableTiming) == hipSuccess;
   }
-  if (!ok) { destroy_drain(s->drain); s->drain = nullptr; return fail(GSV_ERR_DEVICE, "cannot allocate the drain buffers"); }
+  if (!ok) { s->drain.reset(); return fail(GSV_ERR_DEVICE, "cannot allocate the drain buffers"); }
   return GSV_OK;
 }
 
 // Discarding form: calls [c0, c1) of a plan (or the whole program launch), ciphertexts stay in / are overwritten on the device.
 static int garble_discard(gsv_session* s, uint64_t gate_id_base, size_t c0, size_t c1) {
   HIPCHK(hipSetDevice(s->e->device));
-  HIPCHK(hipEventRecord(s->ev0, s->e->stream));
+  HIPCHK(hipEventRecord(s->ev0.get(), s->e->stream.get()));
   int rc = GSV_OK;
   if (s->plan) {
     size_t w0 = 0, w1 = 0;
-    if (c0 == 0) HIPCHK(hipMemsetAsync(s->d_error, 0, 4, s->e->stream));
-    if (s->ct_ring) __atomic_store_n(s->host_ct_pos, ~0ull, __ATOMIC_RELEASE);  // nothing reads the ciphertexts: every block of the ring is free at once
+    if (c0 == 0) HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));
+    if (s->ct_ring) __atomic_store_n(s->sd.ct_pos.get(), ~0ull, __ATOMIC_RELEASE);  // nothing reads the ciphertexts: every block of the ring is free at once
     rc = window_range(s, c0, c1, &w0, &w1);
     for (size_t w = w0; w < w1 && rc == GSV_OK; ++w) rc = launch_plan_window(s, w, gate_id_base, false);
     if (rc == GSV_OK) {
-      HIPCHK(hipEventRecord(s->ev1, s->e->stream));
+      HIPCHK(hipEventRecord(s->ev1.get(), s->e->stream.get()));
       if (c1 == s->plan->calls.size()) rc = gather_plan_outputs(s, false); else { s->ran = true; s->last_eval = false; }
     }
   } else {
     rc = launch(s, gate_id_base, false);
   }
-  if (rc == GSV_OK) { HIPCHK(hipStreamSynchronize(s->e->stream)); s->garbled = !s->plan || s->plan_retain; }
+  if (rc == GSV_OK) { HIPCHK(hipStreamSynchronize(s->e->stream.get())); s->garbled = !s->plan || s->plan_retain; }
   if (rc == GSV_OK && s->plan) rc = check_plan_error(s);
   return rc;
 }
@@ -124,13 +116,15 @@ struct DrainSink {
 // Garble -> evaluate on the device (gsv_session_garble_evaluate): the evaluator session consumes window k from the garbler's
 // program-order block while the garbler writes window k+1 into the other one of two blocks.
 struct PairState {
-  hipStream_t stream = nullptr;                           // the evaluator's launches
-  hipStream_t gstream = nullptr;                          // CU-masked pairs: the garbler's launches (else they go to the engine's stream)
-  hipEvent_t ready = nullptr;                             // engine stream -> gstream hand-over at the start of a pass
-  hipEvent_t garbled[2] = {nullptr, nullptr}, evaluated[2] = {nullptr, nullptr};
+  Stream stream;                           // the evaluator's launches
+  Stream gstream;                          // CU-masked pairs: the garbler's launches (else they go to the engine's stream)
+  Event ready;                             // engine stream -> gstream hand-over at the start of a pass
+  Event garbled[2], evaluated[2];
 };
+gsv_session::gsv_session() = default;
+gsv_session::~gsv_session() { (void)hipSetDevice(e->device); (void)hipStreamSynchronize(e->stream.get()); }  // ... then the members release, in reverse order
 static int ensure_pair(gsv_session* s) {
-  if (!s->ct_alt) DEVALLOC(&s->ct_alt, s->n_inst * size_t(s->ct_stride()) * 16, "the second ciphertext block (garble -> evaluate)");
+  if (!s->ct_alt) DEVALLOC(s->ct_alt, s->n_inst * size_t(s->ct_stride()) * 16, "the second ciphertext block (garble -> evaluate)");
   if (!s->pair) {
     std::unique_ptr<PairState> ps(new PairState());
     // The evaluator's stream: same priority as the engine's, on ANOTHER hardware queue.  Which queue a new stream lands on is the
@@ -152,55 +146,45 @@ static int ensure_pair(gsv_session* s) {
         std::vector<uint32_t> gm(words, 0), em(words, 0);
         for (uint32_t i = 0; i < n_cu; ++i) (((i / 8) % 4 == 3) ? em : gm)[i / 32] |= 1u << (i % 32);
         hipStream_t g = nullptr, e2 = nullptr;
-        if (hipExtStreamCreateWithCUMask(&g, words, gm.data()) == hipSuccess && hipExtStreamCreateWithCUMask(&e2, words, em.data()) == hipSuccess &&
-            hipEventCreateWithFlags(&ps->ready, hipEventDisableTiming) == hipSuccess) {
-          ps->gstream = g; ps->stream = e2;
+        const bool made = hipExtStreamCreateWithCUMask(&g, words, gm.data()) == hipSuccess && hipExtStreamCreateWithCUMask(&e2, words, em.data()) == hipSuccess;
+        Stream g_owner(g), e2_owner(e2);  // (released here when anything failed)
+        if (made && ps->ready.create(hipEventDisableTiming) == hipSuccess) {
+          ps->gstream = std::move(g_owner); ps->stream = std::move(e2_owner);
           if (s->pass.drain_debug) std::fprintf(stderr, "garble -> evaluate: CU-masked streams, %u CUs garble, %u evaluate\n", n_cu - n_cu / 4, n_cu / 4);
-        } else {
-          (void)hipGetLastError();
-          if (g) (void)hipStreamDestroy(g);
-          if (e2) (void)hipStreamDestroy(e2);
-        }
+        } else (void)hipGetLastError();
       }
     }
     if (!ps->stream) {
-      std::vector<hipStream_t> rejected;
-      uint32_t* const word = static_cast<uint32_t*>(s->d_error) + 4;
+      std::vector<Stream> rejected;  // (destroyed when the search ends)
+      uint32_t* const word = s->sd.d_error.as<uint32_t>() + 4;
       for (int attempt = 0; attempt < 8 && !ps->stream; ++attempt) {
-        hipStream_t cand = nullptr;
-        if (hipStreamCreateWithFlags(&cand, hipStreamNonBlocking) != hipSuccess) break;
+        Stream cand_owner;
+        if (cand_owner.create(hipStreamNonBlocking) != hipSuccess) break;
+        const hipStream_t cand = cand_owner.get();
         uint32_t result[2] = {0, 0};
-        const bool probed = hipMemsetAsync(word, 0, 8, s->e->stream) == hipSuccess && hipStreamSynchronize(s->e->stream) == hipSuccess &&
-                            gsvk_probe_overlap(word, 500000ull, s->e->stream, cand) == 0 && hipStreamSynchronize(cand) == hipSuccess &&
-                            hipStreamSynchronize(s->e->stream) == hipSuccess && hipMemcpy(result, word, 8, hipMemcpyDeviceToHost) == hipSuccess;
-        if (!probed || result[1] == 1u || attempt == 7) ps->stream = cand;
-        else rejected.push_back(cand);
+        const bool probed = hipMemsetAsync(word, 0, 8, s->e->stream.get()) == hipSuccess && hipStreamSynchronize(s->e->stream.get()) == hipSuccess &&
+                            gsvk_probe_overlap(word, 500000ull, s->e->stream.get(), cand) == 0 && hipStreamSynchronize(cand) == hipSuccess &&
+                            hipStreamSynchronize(s->e->stream.get()) == hipSuccess && hipMemcpy(result, word, 8, hipMemcpyDeviceToHost) == hipSuccess;
+        if (!probed || result[1] == 1u || attempt == 7) ps->stream = std::move(cand_owner);
+        else rejected.push_back(std::move(cand_owner));
         if (s->pass.drain_debug) std::fprintf(stderr, "garble -> evaluate: candidate stream %d %s\n", attempt, !probed ? "could not be probed" : result[1] == 1u ? "overlaps the engine's stream" : "queues behind the engine's stream");
       }
-      for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
+      rejected.clear();
       if (!ps->stream) return fail(GSV_ERR_DEVICE, "cannot create the evaluator's stream");
     }
     for (int b = 0; b < 2; ++b) {
-      HIPCHK(hipEventCreateWithFlags(&ps->garbled[b], hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&ps->evaluated[b], hipEventDisableTiming));
+      HIPCHK(ps->garbled[b].create(hipEventDisableTiming));
+      HIPCHK(ps->evaluated[b].create(hipEventDisableTiming));
     }
-    s->pair = ps.release();
+    s->pair = std::move(ps);
   }
   return GSV_OK;
-}
-static void destroy_pair(PairState* ps) {
-  if (!ps) return;
-  for (int b = 0; b < 2; ++b) { if (ps->garbled[b]) (void)hipEventDestroy(ps->garbled[b]); if (ps->evaluated[b]) (void)hipEventDestroy(ps->evaluated[b]); }
-  if (ps->stream) (void)hipStreamDestroy(ps->stream);
-  if (ps->gstream) (void)hipStreamDestroy(ps->gstream);
-  if (ps->ready) (void)hipEventDestroy(ps->ready);
-  delete ps;
 }
 
 // Follows the RUNNING window w through the completion counters its workgroups write into mapped host memory (kernels.hip, epilogue)
 // until calls [k0, k1) of the plan have completed for every instance group, or the window's launch itself has finished (*window_done).
 static int wait_calls_done(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, bool* window_done, hipStream_t launch_stream = nullptr) {
-  if (!launch_stream) launch_stream = s->e->stream;  // the stream the running window was launched on
+  if (!launch_stream) launch_stream = s->e->stream.get();  // the stream the running window was launched on
   const Schedule::Window& win = s->sched.windows[w];
   const uint32_t n_wg = uint32_t(s->launch_groups());  // workgroups that count a call done (one per instance under BLAKE3)
   const auto t0 = std::chrono::steady_clock::now();
@@ -214,7 +198,7 @@ static int wait_calls_done(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, b
   uint32_t polls = 0;
   while (!*window_done && k0 < k1) {
     bool all = true;
-    for (uint32_t k = k0; k < k1 && all; ++k) all = __atomic_load_n(s->host_done + k, __ATOMIC_ACQUIRE) == n_wg;
+    for (uint32_t k = k0; k < k1 && all; ++k) all = __atomic_load_n(s->sd.done.get() + k, __ATOMIC_ACQUIRE) == n_wg;
     if (all) break;
     const hipError_t q = hipStreamQuery(launch_stream);
     if (q == hipSuccess) { *window_done = true; break; }
@@ -225,7 +209,7 @@ static int wait_calls_done(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, b
     std::this_thread::sleep_for(std::chrono::microseconds(100));
     if ((++polls & 1023u) == 0) {  // every ~0.1 s: has any call of the window completed for another workgroup?
       uint64_t sum = 0;
-      for (uint32_t k = win.call0; k < win.call1; ++k) sum += __atomic_load_n(s->host_done + k, __ATOMIC_RELAXED);
+      for (uint32_t k = win.call0; k < win.call1; ++k) sum += __atomic_load_n(s->sd.done.get() + k, __ATOMIC_RELAXED);
       const auto now = std::chrono::steady_clock::now();
       if (sum != last_sum) { last_sum = sum; last_move = now; }
       else if (std::chrono::duration<double>(now - last_move).count() > deadline)
@@ -235,8 +219,8 @@ static int wait_calls_done(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, b
       reported = true;
       std::string msg;
       for (uint32_t k = win.call0; k < win.call1; ++k)
-        if (s->host_done[k] != n_wg) msg += " " + std::to_string(k) + "(" + std::to_string(s->host_done[k]) + "/" + std::to_string(n_wg) + (s->ct_ring ? ",need " + std::to_string(s->sched.ring_need[k]) + ",ready " + std::to_string(s->sched.seg_end[k]) : "") + ")";
-      std::fprintf(stderr, "drain debug: waiting > 3 s for calls [%u, %u) of window %zu; host position %llu; unfinished:%s\n", k0, k1, w, s->host_ct_pos ? (unsigned long long)*s->host_ct_pos : 0ull, msg.substr(0, 1500).c_str());
+        if (s->sd.done.get()[k] != n_wg) msg += " " + std::to_string(k) + "(" + std::to_string(s->sd.done.get()[k]) + "/" + std::to_string(n_wg) + (s->ct_ring ? ",need " + std::to_string(s->sched.ring_need[k]) + ",ready " + std::to_string(s->sched.seg_end[k]) : "") + ")";
+      std::fprintf(stderr, "drain debug: waiting > 3 s for calls [%u, %u) of window %zu; host position %llu; unfinished:%s\n", k0, k1, w, s->sd.ct_pos.get() ? (unsigned long long)*s->sd.ct_pos.get() : 0ull, msg.substr(0, 1500).c_str());
     }
   }
   return GSV_OK;
@@ -246,22 +230,18 @@ static int wait_calls_done(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, b
 // sample drain (gsv_session_set_drain_instances) sizes them for the sample; a later call over more instances (a full drain, or any
 // evaluate_streaming: the evaluator uploads EVERY instance's stream) must not write past them.
 static int ensure_ct_gate(gsv_session* s, size_t bytes) {
-  if (s->ct_gate && s->ct_gate_bytes >= bytes) return GSV_OK;
+  if (s->ct_gate && s->ct_gate.bytes() >= bytes) return GSV_OK;
   if (s->ct_gate || !s->ct_gate_more.empty()) {
-    HIPCHK(hipStreamSynchronize(s->e->stream));
-    if (s->aux_stream) HIPCHK(hipStreamSynchronize(s->aux_stream));
-    for (void* q : s->ct_gate_more) if (q) (void)hipFree(q);
-    s->ct_gate_more.clear();
-    if (s->ct_gate) (void)hipFree(s->ct_gate);
-    s->ct_gate = nullptr; s->ct_gate_bytes = 0;
+    HIPCHK(hipStreamSynchronize(s->e->stream.get()));
+    if (s->aux_stream) HIPCHK(hipStreamSynchronize(s->aux_stream.get()));
+    s->ct_gate_more.clear(); s->ct_gate.reset();
   }
-  DEVALLOC(&s->ct_gate, bytes, "the gate-order ciphertext buffer");
-  s->ct_gate_bytes = bytes;
+  DEVALLOC(s->ct_gate, bytes, "the gate-order ciphertext buffer");
   return GSV_OK;
 }
 static int ensure_aux(gsv_session* s) {
-  if (!s->aux_stream) HIPCHK(create_side_stream(&s->aux_stream, s->kn.side_stream_priority));
-  if (!s->host_done) return fail(GSV_ERR_INVALID, "internal: a plan session without completion counters");  // (allocated with its call descriptors)
+  if (!s->aux_stream) HIPCHK(create_side_stream(s->aux_stream, s->kn.side_stream_priority));
+  if (!s->sd.done) return fail(GSV_ERR_INVALID, "internal: a plan session without completion counters");  // (allocated with its call descriptors)
   return GSV_OK;
 }
 
@@ -296,10 +276,10 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   }
   if (ev && (s->ct_ring || ev->ct_ring)) return fail(GSV_ERR_INVALID, "garble || evaluate pairs need sessions with explicit launch windows (window_ct_records, e.g. 1 << 28): the default is one whole-pass window over a ciphertext ring");
   if (ev) { int rc = ensure_pair(s); if (rc) return rc; }
-  if (s->ct_ring) __atomic_store_n(s->host_ct_pos, (unsigned long long)(s->plan && pw0 < s->sched.windows.size() ? s->sched.windows[pw0].ct0 : 0), __ATOMIC_RELEASE);
+  if (s->ct_ring) __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(s->plan && pw0 < s->sched.windows.size() ? s->sched.windows[pw0].ct0 : 0), __ATOMIC_RELEASE);
   if (s->plan && want_drain) { int rc = ensure_aux(s); if (rc) return rc; }
-  if (s->plan && new_pass) HIPCHK(hipMemsetAsync(s->d_error, 0, 4, s->e->stream));  // a new pass starts with a clean dependency-wait flag
-  if (ev && new_pass) HIPCHK(hipMemsetAsync(ev->d_error, 0, 4, s->e->stream));
+  if (s->plan && new_pass) HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));  // a new pass starts with a clean dependency-wait flag
+  if (ev && new_pass) HIPCHK(hipMemsetAsync(ev->sd.d_error.get(), 0, 4, s->e->stream.get()));
   std::vector<CbcMacHost> no_macs;
   if (want_drain && (new_pass || s->drain->macs.size() != n_inst)) s->drain->macs.assign(n_inst, CbcMacHost());  // a new pass starts from h = 0; later slices chain
   std::vector<CbcMacHost>& macs = want_drain ? s->drain->macs : no_macs;
@@ -325,7 +305,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   // see its stream in order); a buffer is reused once every worker is done with the segment that held it.
   std::vector<void*> gate_bufs;
   if (want_drain) {
-    gate_bufs.push_back(s->ct_gate);
+    gate_bufs.push_back(s->ct_gate.get());
     size_t want = 1;
     size_t n_units = size_t((total - first + seg - 1) / seg);  // drain units of this call: segments (plans) or rings
     if (s->plan) { n_units = 0; for (size_t w = pw0; w < pw1; ++w) n_units += s->sched.windows[w].seg1 - s->sched.windows[w].seg0; }
@@ -338,11 +318,11 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
       if (s->pass.drain_depth) want = s->pass.drain_depth;
     }
     while (1 + s->ct_gate_more.size() < want) {
-      void* q = nullptr;
-      if (hipMalloc(&q, s->ct_gate_bytes) != hipSuccess) { (void)hipGetLastError(); break; }  // (every buffer of the pipeline has ct_gate's capacity)
-      s->ct_gate_more.push_back(q);
+      DevBuf q;
+      if (q.alloc(s->ct_gate.bytes()) != hipSuccess) break;  // (every buffer of the pipeline has ct_gate's capacity)
+      s->ct_gate_more.push_back(std::move(q));
     }
-    for (void* q : s->ct_gate_more) if (gate_bufs.size() < want) gate_bufs.push_back(q);
+    for (const DevBuf& q : s->ct_gate_more) if (gate_bufs.size() < want) gate_bufs.push_back(q.get());
   }
   const size_t depth = std::max<size_t>(1, gate_bufs.size());
   struct Segment { uint64_t n, base; size_t buf; };
@@ -372,10 +352,10 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
           hipStream_t st = dr.copy_gate.acquire();
           bool ok = true;
           for (size_t g = 0; g < ng && ok; ++g)
-            ok = hipMemcpyAsync(w.pinned[b][g], gate + ((i0 + g) * seg_records + off) * 16, std::min(chunk, n - off) * 16, hipMemcpyDeviceToHost, st) == hipSuccess;
+            ok = hipMemcpyAsync(w.pinned[b][g].get(), gate + ((i0 + g) * seg_records + off) * 16, std::min(chunk, n - off) * 16, hipMemcpyDeviceToHost, st) == hipSuccess;
           // many workers: sleep on the blocking-sync event (spinning workers eat the cores the MACs need); a handful of
           // workers (one instance: the whole-stream check) spin instead, a blocking wait's wake-up latency would be paid per chunk
-          ok = ok && (T > 8 ? hipEventRecord(w.done, st) == hipSuccess && hipEventSynchronize(w.done) == hipSuccess : hipStreamSynchronize(st) == hipSuccess);
+          ok = ok && (T > 8 ? hipEventRecord(w.done.get(), st) == hipSuccess && hipEventSynchronize(w.done.get()) == hipSuccess : hipStreamSynchronize(st) == hipSuccess);
           dr.copy_gate.release(st);
           return ok;
         };
@@ -386,15 +366,15 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
           if (want_mac) {
             CbcMacHost* mp[gsv_drain::GROUP_MAX];
             const uint8_t* cp[gsv_drain::GROUP_MAX];
-            for (size_t g = 0; g < ng; ++g) { mp[g] = &macs[i0 + g]; cp[g] = static_cast<const uint8_t*>(w.pinned[b][g]); }
+            for (size_t g = 0; g < ng; ++g) { mp[g] = &macs[i0 + g]; cp[g] = w.pinned[b][g].get(); }
             CbcMacHost::update_many(mp, cp, ng, m);  // sixteen / four chains per step, a ragged last group chain by chain
           }
           if (sink.dir)
             for (size_t g = 0; g < ng; ++g)
-              if (std::fwrite(w.pinned[b][g], 16, m, files[i0 + g]) != m) { err = 2; break; }
+              if (std::fwrite(w.pinned[b][g].get(), 16, m, files[i0 + g]) != m) { err = 2; break; }
           if (sink.fn && !err)
             for (size_t g = 0; g < ng; ++g)
-              if (sink.fn(sink.user, i0 + g, base + off, static_cast<const uint8_t*>(w.pinned[b][g]), m) != 0) { err = 3; break; }
+              if (sink.fn(sink.user, i0 + g, base + off, w.pinned[b][g].get(), m) != 0) { err = 3; break; }
           if (err) break;
           if (off + chunk < n && !copy(off + chunk, b ^ 1)) { err = 1; break; }
         }
@@ -439,38 +419,38 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   auto t_last_pub = std::chrono::steady_clock::now();
   double worst_gap = 0;
   s->ring_diag.clear();
-  struct BlockingEvent { hipEvent_t ev = nullptr; ~BlockingEvent() { if (ev) (void)hipEventDestroy(ev); } } device_done_owner;
-  if (want_drain && T + 1 > gsv_drain::usable_cores()) (void)hipEventCreateWithFlags(&device_done_owner.ev, hipEventBlockingSync | hipEventDisableTiming);
-  const hipEvent_t device_done = device_done_owner.ev;
+  Event device_done_owner;
+  if (want_drain && T + 1 > gsv_drain::usable_cores()) (void)device_done_owner.create(hipEventBlockingSync | hipEventDisableTiming);
+  const hipEvent_t device_done = device_done_owner.get();
   int rc = GSV_OK;
   // The stream the garbler's windows are launched on: the engine's, or — a garble || evaluate pair with CU-masked streams (ensure_pair) —
   // the pair's masked garbler stream, which first waits for whatever the engine's stream still holds (input staging, the memsets above).
-  hipStream_t gs = s->e->stream;
+  hipStream_t gs = s->e->stream.get();
   if (ev && s->pair->gstream) {
-    gs = s->pair->gstream;
-    if (hipEventRecord(s->pair->ready, s->e->stream) != hipSuccess || hipStreamWaitEvent(gs, s->pair->ready, 0) != hipSuccess) { finish_workers(); close_files(); return fail(GSV_ERR_DEVICE, "stream hand-over failed"); }
+    gs = s->pair->gstream.get();
+    if (hipEventRecord(s->pair->ready.get(), s->e->stream.get()) != hipSuccess || hipStreamWaitEvent(gs, s->pair->ready.get(), 0) != hipSuccess) { finish_workers(); close_files(); return fail(GSV_ERR_DEVICE, "stream hand-over failed"); }
   }
-  if (hipEventRecord(s->ev0, gs) != hipSuccess) { finish_workers(); close_files(); return fail(GSV_ERR_DEVICE, "hipEventRecord failed"); }
+  if (hipEventRecord(s->ev0.get(), gs) != hipSuccess) { finish_workers(); close_files(); return fail(GSV_ERR_DEVICE, "hipEventRecord failed"); }
   for (uint64_t r0 = first; r0 < total && rc == GSV_OK; r0 += seg) {
     const uint64_t r1 = std::min(total, r0 + seg);
     uint64_t n_records, base;  // per instance, in this segment; stream index of its first record
     if (s->plan) {
       const size_t w = size_t(r0);
-      void* block = s->CT;
+      void* block = s->CT.get();
       if (ev) {
         // window w goes to block w & 1; the evaluator must be done with what that block held (window w - 2)
         const int b = int(w & 1);
-        block = b ? s->ct_alt : s->CT;
-        if (w >= pw0 + 2 && hipStreamWaitEvent(gs, s->pair->evaluated[b], 0) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "hipStreamWaitEvent failed"); break; }
+        block = b ? s->ct_alt.get() : s->CT.get();
+        if (w >= pw0 + 2 && hipStreamWaitEvent(gs, s->pair->evaluated[b].get(), 0) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "hipStreamWaitEvent failed"); break; }
       }
       rc = launch_plan_window(s, w, gate_id_base, false, block, gs);
       if (rc != GSV_OK) break;
       if (ev) {
         const int b = int(w & 1);
-        if (hipEventRecord(s->pair->garbled[b], gs) != hipSuccess || hipStreamWaitEvent(s->pair->stream, s->pair->garbled[b], 0) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "event hand-over failed"); break; }
-        rc = launch_plan_window(ev, w, gate_id_base, true, block, s->pair->stream);
+        if (hipEventRecord(s->pair->garbled[b].get(), gs) != hipSuccess || hipStreamWaitEvent(s->pair->stream.get(), s->pair->garbled[b].get(), 0) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "event hand-over failed"); break; }
+        rc = launch_plan_window(ev, w, gate_id_base, true, block, s->pair->stream.get());
         if (rc != GSV_OK) break;
-        if (hipEventRecord(s->pair->evaluated[b], s->pair->stream) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "hipEventRecord failed"); break; }
+        if (hipEventRecord(s->pair->evaluated[b].get(), s->pair->stream.get()) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "hipEventRecord failed"); break; }
       }
       // The window is running.  Its segments leave the device one after the other, in stream order, each as soon as every call of it
       // has completed for every instance group: the host follows the completion flags of the running launch (a page-locked copy,
@@ -497,12 +477,12 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
           t_wait_device += secs(t0);
           wait_buffer(n_pushed);  // the gate-order buffer this segment goes to is free again
           const auto tg = std::chrono::steady_clock::now();
-          rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, seg_records, 0, block, gate_bufs[n_pushed % depth], s->aux_stream);
+          rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, seg_records, 0, block, gate_bufs[n_pushed % depth], s->aux_stream.get());
           if (rc != GSV_OK) break;
-          if (hipStreamSynchronize(s->aux_stream) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "ciphertext gather failed"); break; }
+          if (hipStreamSynchronize(s->aux_stream.get()) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "ciphertext gather failed"); break; }
           t_gather += secs(tg);
           if (s->ct_ring) {
-            __atomic_store_n(s->host_ct_pos, (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);  // the calls whose blocks overlap this segment's may write now
+            __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);  // the calls whose blocks overlap this segment's may write now
             const double gap = secs(t_last_pub);
             if (gap > worst_gap) {
               worst_gap = gap;
@@ -528,7 +508,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
       wait_buffer(n_pushed);
       n_records = (r1 - r0) * n_ct;
       base = r0 * n_ct;
-      if (gsvk_gather_segment(s->CT, s->ct_stride(), s->dp.ct_pos, n_ct, uint32_t(r1 - r0), uint32_t(n_inst), gate_bufs[n_pushed % depth], seg_records, 0, s->e->stream) != 0) {
+      if (gsvk_gather_segment(s->CT.get(), s->ct_stride(), s->dp->ct_pos.as<const uint32_t>(), n_ct, uint32_t(r1 - r0), uint32_t(n_inst), gate_bufs[n_pushed % depth], seg_records, 0, s->e->stream.get()) != 0) {
         rc = fail(GSV_ERR_DEVICE, "ciphertext gather launch failed");
         break;
       }
@@ -537,7 +517,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
       // the workers own the cores when there is one chain per core: this thread then sleeps on a blocking-sync event instead of
       // spinning in hipStreamSynchronize
       const auto t0 = std::chrono::steady_clock::now();
-      const bool ok = device_done ? hipEventRecord(device_done, s->e->stream) == hipSuccess && hipEventSynchronize(device_done) == hipSuccess : hipStreamSynchronize(s->e->stream) == hipSuccess;
+      const bool ok = device_done ? hipEventRecord(device_done, s->e->stream.get()) == hipSuccess && hipEventSynchronize(device_done) == hipSuccess : hipStreamSynchronize(s->e->stream.get()) == hipSuccess;
       if (!ok) { rc = fail(GSV_ERR_DEVICE, "kernel failed"); break; }
       t_wait_device += secs(t0);
     }
@@ -546,18 +526,18 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   }
   if (s->ct_ring && rc != GSV_OK) {
     // a failed pass: calls of the running window may still wait for room in the ring — let them run out (the results are discarded)
-    __atomic_store_n(s->host_ct_pos, ~0ull, __ATOMIC_RELEASE);
+    __atomic_store_n(s->sd.ct_pos.get(), ~0ull, __ATOMIC_RELEASE);
     (void)hipStreamSynchronize(gs);
   }
   finish_workers();
-  if (ev && hipStreamSynchronize(s->pair->stream) != hipSuccess && rc == GSV_OK) rc = fail(GSV_ERR_DEVICE, "evaluation kernel failed");
+  if (ev && hipStreamSynchronize(s->pair->stream.get()) != hipSuccess && rc == GSV_OK) rc = fail(GSV_ERR_DEVICE, "evaluation kernel failed");
   if (stats) {
     const double tot = secs(t_begin);
     std::fprintf(stderr, "drain: %.2f s for %zu instances x %llu records (%.1f GB/s), %zu MAC workers x %zu chains, %zu gate-order buffers; host thread waited %.2f s for drains, %.2f s for the device and %.2f s for the gathers of running windows\n", tot, n_inst,
                  (unsigned long long)drained_records, double(drained_records) * double(n_inst) * 16e-9 / tot, T, GROUP, depth, t_wait_drain, t_wait_device, t_gather);
   }
   if (rc == GSV_OK && s->plan) {
-    (void)hipEventRecord(s->ev1, gs);  // (every window on gs has been synchronised: the output gather on the engine's stream follows safely)
+    (void)hipEventRecord(s->ev1.get(), gs);  // (every window on gs has been synchronised: the output gather on the engine's stream follows safely)
     if (c1 == s->plan->calls.size()) {
       rc = gather_plan_outputs(s, false);
       if (rc == GSV_OK && ev) rc = gather_plan_outputs(ev, true);
@@ -593,21 +573,7 @@ static int fall_back_to_safe_schedule(gsv_session* s) {
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
   int rc = install_schedule(s, o, prop.multiProcessorCount, free_b);
-  if (rc) return rc;
-  const Program& f = s->facade;
-  if (f.n_slots > s->w_slots_cap) {
-    (void)hipFree(s->W); (void)hipFree(s->VB); s->W = s->VB = nullptr;
-    DEVALLOC(&s->W, s->n_inst * size_t(f.n_slots) * 16, "the wire files");
-    HIPCHK(hipMalloc(&s->VB, s->n_inst * size_t(f.n_slots)));
-    s->w_slots_cap = f.n_slots;
-  }
-  HIPCHK(hipMemset(s->VB, 0, s->n_inst * size_t(f.n_slots)));
-  if (s->ct_stride() > s->ct_records_cap) {
-    (void)hipFree(s->CT); s->CT = nullptr;
-    if (s->ct_alt) { (void)hipFree(s->ct_alt); s->ct_alt = nullptr; }
-    DEVALLOC(&s->CT, s->n_inst * size_t(s->ct_stride()) * 16, "the ciphertext blocks");
-    s->ct_records_cap = s->ct_stride();
-  }
+  if (rc || (rc = alloc_session_buffers(s, s->facade))) return rc;  // (W / VB / CT grow where the safe schedule needs more; VB cleared)
   ++s->n_fallbacks;
   s->dep_fault = false;
   s->garbled = false;

@@ -31,10 +31,10 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
   // are done.  (The reference's evaluator runs its finalized cases under into_par_iter: cut_and_choose/evaluator.rs:118-181.)
   const size_t T = hashes ? std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n_inst, 16), gsv_drain::usable_cores() > 1 ? gsv_drain::usable_cores() - 1 : 1)) : 0;
   const size_t NB = 2 + 2 * T;
-  struct Pinned { std::vector<void*> p; std::vector<hipEvent_t> ev; ~Pinned() { for (void* q : p) if (q) (void)hipHostFree(q); for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); } } stage;
+  std::vector<MappedHost<uint8_t>> stage(NB);  // page-locked staging buffers, and per buffer the event of the copy that last used it
+  std::vector<Event> stage_ev(NB);
   const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(seg_records, 1), CT_STAGE_RECORDS);
-  stage.p.assign(NB, nullptr); stage.ev.assign(NB, nullptr);
-  for (size_t k = 0; k < NB; ++k) { HIPCHK(hipHostMalloc(&stage.p[k], size_t(chunk) * 16, hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&stage.ev[k], hipEventDisableTiming)); }
+  for (size_t k = 0; k < NB; ++k) { HIPCHK(stage[k].alloc(size_t(chunk) * 16, hipHostMallocDefault)); HIPCHK(stage_ev[k].create(hipEventDisableTiming)); }
   std::vector<CbcMacHost> macs(n_inst);
   struct MacPool {  // declared after `stage` and `macs`: joined before either goes away
     struct Job { size_t inst; const uint8_t* p; uint64_t n; size_t buf; };
@@ -69,8 +69,8 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
     }
     ~MacPool() { finish(); }
   } pool(macs, T, NB);
-  if (s->plan) HIPCHK(hipMemsetAsync(s->d_error, 0, 4, s->e->stream));
-  HIPCHK(hipEventRecord(s->ev0, s->e->stream));
+  if (s->plan) HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));
+  HIPCHK(hipEventRecord(s->ev0.get(), s->e->stream.get()));
   int rc = GSV_OK;
   size_t b = 0;
   // `n` records per instance starting at stream index `base` -> the gate-order buffer through `st` (bounded page-locked chunks, hashed as read)
@@ -78,12 +78,12 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
     for (uint64_t off = 0; off < n; off += chunk)
       for (size_t i = 0; i < n_inst; ++i, b = (b + 1) % NB) {
         const uint64_t m = std::min(chunk, n - off);
-        if (hipEventSynchronize(stage.ev[b]) != hipSuccess) return fail(GSV_ERR_DEVICE, "event wait failed");  // the copy that last used this staging buffer has finished
+        if (hipEventSynchronize(stage_ev[b].get()) != hipSuccess) return fail(GSV_ERR_DEVICE, "event wait failed");  // the copy that last used this staging buffer has finished
         if (T) pool.wait_free(b);  // ... and so has its MAC
-        uint8_t* host = static_cast<uint8_t*>(stage.p[b]);
+        uint8_t* host = stage[b].get();
         if (read(i, base + off, host, m) != 0) return fail(GSV_ERR_EXHAUSTED, "Ciphertext source exhausted: instance " + std::to_string(i) + " ran dry at record " + std::to_string(base + off));
         if (T) pool.push(i, host, m, b);
-        if (hipMemcpyAsync(static_cast<uint8_t*>(s->ct_gate) + (i * seg_records + off) * 16, host, m * 16, hipMemcpyHostToDevice, st) != hipSuccess || hipEventRecord(stage.ev[b], st) != hipSuccess)
+        if (hipMemcpyAsync(static_cast<uint8_t*>(s->ct_gate.get()) + (i * seg_records + off) * 16, host, m * 16, hipMemcpyHostToDevice, st) != hipSuccess || hipEventRecord(stage_ev[b].get(), st) != hipSuccess)
           return fail(GSV_ERR_DEVICE, "ciphertext upload failed");
       }
     return GSV_OK;
@@ -95,7 +95,7 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
     rc = ensure_aux(s);
     for (size_t w = 0; w < s->sched.windows.size() && rc == GSV_OK; ++w) {
       const Schedule::Window& win = s->sched.windows[w];
-      __atomic_store_n(s->host_ct_pos, (unsigned long long)win.ct0, __ATOMIC_RELEASE);
+      __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)win.ct0, __ATOMIC_RELEASE);
       rc = launch_plan_window(s, w, gate_id_base, true);
       bool window_done = false;
       for (uint32_t q = win.seg0; q < win.seg1 && rc == GSV_OK; ++q) {
@@ -109,18 +109,18 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
         if (rc != GSV_OK) break;
         if (window_done) { rc = fail(GSV_ERR_DEVICE, "internal: the window finished before its ciphertexts were uploaded"); break; }
         // uploads and the scatter go through the side stream (the main stream holds the running window)
-        rc = upload(sg.ct0, sg.n_ct, s->aux_stream);
-        if (rc == GSV_OK) rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, seg_records, 1, nullptr, nullptr, s->aux_stream);
-        if (rc == GSV_OK && hipStreamSynchronize(s->aux_stream) != hipSuccess) rc = fail(GSV_ERR_DEVICE, "ciphertext scatter failed");
-        if (rc == GSV_OK) __atomic_store_n(s->host_ct_pos, (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);
+        rc = upload(sg.ct0, sg.n_ct, s->aux_stream.get());
+        if (rc == GSV_OK) rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, seg_records, 1, nullptr, nullptr, s->aux_stream.get());
+        if (rc == GSV_OK && hipStreamSynchronize(s->aux_stream.get()) != hipSuccess) rc = fail(GSV_ERR_DEVICE, "ciphertext scatter failed");
+        if (rc == GSV_OK) __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);
       }
       if (rc != GSV_OK) {
         // let the calls that still wait for ciphertexts run out (their results are discarded with the error) instead of hanging the stream
-        __atomic_store_n(s->host_ct_pos, ~0ull, __ATOMIC_RELEASE);
-        (void)hipStreamSynchronize(s->e->stream);
+        __atomic_store_n(s->sd.ct_pos.get(), ~0ull, __ATOMIC_RELEASE);
+        (void)hipStreamSynchronize(s->e->stream.get());
         break;
       }
-      if (hipStreamSynchronize(s->e->stream) != hipSuccess) rc = fail(GSV_ERR_DEVICE, "kernel failed");
+      if (hipStreamSynchronize(s->e->stream.get()) != hipSuccess) rc = fail(GSV_ERR_DEVICE, "kernel failed");
     }
   } else if (s->plan) {
     for (size_t w = 0; w < s->sched.windows.size() && rc == GSV_OK; ++w) {
@@ -128,7 +128,7 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
       for (uint32_t q = win.seg0; q < win.seg1 && rc == GSV_OK; ++q) {
         const Schedule::Segment& sg = s->sched.segments[q];
         // (the stream orders this segment's uploads behind the scatter of the previous one, which read the same buffer)
-        rc = upload(sg.ct0, sg.n_ct, s->e->stream);
+        rc = upload(sg.ct0, sg.n_ct, s->e->stream.get());
         if (rc == GSV_OK) rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, seg_records, 1, nullptr, nullptr, nullptr);
       }
       if (rc == GSV_OK) rc = launch_plan_window(s, w, gate_id_base, true);
@@ -137,15 +137,15 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
     const uint64_t n_ct = g.n_ct, total = s->replays, seg = s->ct_cap;
     for (uint64_t r0 = 0; r0 < total && rc == GSV_OK; r0 += seg) {
       const uint64_t r1 = std::min(total, r0 + seg);
-      rc = upload(r0 * n_ct, (r1 - r0) * n_ct, s->e->stream);
+      rc = upload(r0 * n_ct, (r1 - r0) * n_ct, s->e->stream.get());
       if (rc != GSV_OK) break;
-      if (gsvk_gather_segment(s->CT, s->ct_stride(), s->dp.ct_pos, n_ct, uint32_t(r1 - r0), uint32_t(n_inst), s->ct_gate, seg_records, 1, s->e->stream) != 0) { rc = fail(GSV_ERR_DEVICE, "ciphertext scatter launch failed"); break; }
+      if (gsvk_gather_segment(s->CT.get(), s->ct_stride(), s->dp->ct_pos.as<const uint32_t>(), n_ct, uint32_t(r1 - r0), uint32_t(n_inst), s->ct_gate.get(), seg_records, 1, s->e->stream.get()) != 0) { rc = fail(GSV_ERR_DEVICE, "ciphertext scatter launch failed"); break; }
       rc = launch(s, gate_id_base, true, r0, r1 - r0);
     }
   }
-  if (hipStreamSynchronize(s->e->stream) != hipSuccess && rc == GSV_OK) rc = fail(GSV_ERR_DEVICE, "kernel failed");
+  if (hipStreamSynchronize(s->e->stream.get()) != hipSuccess && rc == GSV_OK) rc = fail(GSV_ERR_DEVICE, "kernel failed");
   if (rc != GSV_OK) return rc;
-  if (s->plan) { HIPCHK(hipEventRecord(s->ev1, s->e->stream)); rc = gather_plan_outputs(s, true); if (rc) return rc; HIPCHK(hipStreamSynchronize(s->e->stream)); rc = check_plan_error(s); if (rc) return rc; }
+  if (s->plan) { HIPCHK(hipEventRecord(s->ev1.get(), s->e->stream.get())); rc = gather_plan_outputs(s, true); if (rc) return rc; HIPCHK(hipStreamSynchronize(s->e->stream.get())); rc = check_plan_error(s); if (rc) return rc; }
   pool.finish();
   if (hashes) for (size_t i = 0; i < n_inst; ++i) macs[i].digest(hashes + 16 * i);
   return GSV_OK;
@@ -205,7 +205,7 @@ int gsv_session_set_hasher(gsv_session* s, int kind) {
 int gsv_session_sync(gsv_session* s) {
   if (!s) return fail(GSV_ERR_INVALID, "null session");
   HIPCHK(hipSetDevice(s->e->device));
-  HIPCHK(hipStreamSynchronize(s->e->stream));
+  HIPCHK(hipStreamSynchronize(s->e->stream.get()));
   if (s->plan) return check_plan_error(s);
   return GSV_OK;
 }
@@ -215,16 +215,16 @@ int gsv_session_enable_step_clock(gsv_session* s) {
   HIPCHK(hipSetDevice(s->e->device));
   if (!s->step_clock) {
     const size_t bytes = (size_t(s->prog().n_steps) + 1) * sizeof(uint64_t);
-    HIPCHK(hipMalloc(&s->step_clock, bytes));
-    HIPCHK(hipMemset(s->step_clock, 0, bytes));
+    HIPCHK(s->step_clock.alloc(bytes));
+    HIPCHK(hipMemset(s->step_clock.get(), 0, bytes));
   }
   return GSV_OK;
 }
 int gsv_session_read_step_clock(gsv_session* s, uint64_t* out) {
   if (!s || !out || !s->step_clock || !s->ran) return fail(GSV_ERR_INVALID, "step clock not enabled / nothing ran");
   HIPCHK(hipSetDevice(s->e->device));
-  HIPCHK(hipStreamSynchronize(s->e->stream));
-  HIPCHK(hipMemcpy(out, s->step_clock, (size_t(s->prog().n_steps) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipStreamSynchronize(s->e->stream.get()));
+  HIPCHK(hipMemcpy(out, s->step_clock.get(), (size_t(s->prog().n_steps) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return GSV_OK;
 }
 // Diagnostics: per step {and_cnt, xor_cnt, lds_reads, hbm_reads, lds_writes, hbm_writes} decoded from the compiled records.
@@ -260,22 +260,22 @@ int gsv_session_instances_per_workgroup(const gsv_session* s, int* n) {
 }
 int gsv_session_last_kernel_ms(gsv_session* s, double* ms) {
   if (!s || !ms || !s->ran) return fail(GSV_ERR_INVALID, "no launch recorded");
-  HIPCHK(hipEventSynchronize(s->ev1));
+  HIPCHK(hipEventSynchronize(s->ev1.get()));
   float f = 0;
-  HIPCHK(hipEventElapsedTime(&f, s->ev0, s->ev1));
+  HIPCHK(hipEventElapsedTime(&f, s->ev0.get(), s->ev1.get()));
   *ms = f;
   return GSV_OK;
 }
 int gsv_session_read_outputs(gsv_session* s, uint8_t* labels, uint8_t* bits) {
   if (!s || !labels || !s->ran) return fail(GSV_ERR_INVALID, "bad argument / nothing ran");
   HIPCHK(hipSetDevice(s->e->device));
-  HIPCHK(hipStreamSynchronize(s->e->stream));
+  HIPCHK(hipStreamSynchronize(s->e->stream.get()));
   if (s->plan) { int rc = check_plan_error(s); if (rc) return rc; }
   const size_t n = s->n_inst * s->prog().output_slots.size();
-  if (n) HIPCHK(hipMemcpy(labels, s->out, n * 16, hipMemcpyDeviceToHost));
+  if (n) HIPCHK(hipMemcpy(labels, s->out.get(), n * 16, hipMemcpyDeviceToHost));
   if (bits) {
     if (!s->last_eval) return fail(GSV_ERR_INVALID, "plaintext bits exist only after evaluate");
-    if (n) HIPCHK(hipMemcpy(bits, s->out_bits, n, hipMemcpyDeviceToHost));
+    if (n) HIPCHK(hipMemcpy(bits, s->out_bits.get(), n, hipMemcpyDeviceToHost));
   }
   return GSV_OK;
 }
@@ -284,7 +284,7 @@ int gsv_session_read_ciphertexts(gsv_session* s, size_t instance, uint64_t first
   if (s->plan && !s->plan_retain) return fail(GSV_ERR_INVALID, "this plan session does not retain the ciphertext stream");
   if (first + n_records > s->ct_stride()) return fail(GSV_ERR_INVALID, "range exceeds the retained ciphertext stream");
   HIPCHK(hipSetDevice(s->e->device));
-  HIPCHK(hipStreamSynchronize(s->e->stream));
+  HIPCHK(hipStreamSynchronize(s->e->stream.get()));
   for (uint64_t off = 0; off < n_records; off += CT_STAGE_RECORDS) {
     const uint64_t n = std::min<uint64_t>(CT_STAGE_RECORDS, n_records - off);
     int rc = fetch_ciphertexts(s, instance, first + off, n, out + off * 16);
@@ -296,7 +296,7 @@ int gsv_session_ciphertext_hash(gsv_session* s, size_t instance, uint8_t hash[16
   if (!s || instance >= s->n_inst || !hash) return fail(GSV_ERR_INVALID, "bad argument");
   if (s->ct_cap != s->replays || (s->plan && !s->plan_retain)) return fail(GSV_ERR_INVALID, "the session retains only part of the stream (ct_capacity_replays < replays)");
   HIPCHK(hipSetDevice(s->e->device));
-  HIPCHK(hipStreamSynchronize(s->e->stream));
+  HIPCHK(hipStreamSynchronize(s->e->stream.get()));
   const uint64_t total = s->ct_stride();
   const uint64_t chunk = CT_STAGE_RECORDS;
   std::vector<uint8_t> buf(size_t(std::min<uint64_t>(chunk, total ? total : 1)) * 16);

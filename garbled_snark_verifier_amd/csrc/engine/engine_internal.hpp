@@ -19,13 +19,13 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <set>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../../include/gsv_engine.h"
 #include "../gadgets/circuits.hpp"
+#include "hip_owned.hpp"
 #include "host_crypto.hpp"
 #include "kernel_api.h"
 #include "knobs.hpp"
@@ -56,10 +56,9 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
   } while (0)
 
 // Large device allocations report what was asked for and what the device had left.
-static int dev_alloc(void** p, size_t bytes, const char* what) {
-  hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+static int dev_alloc(DevBuf& p, size_t bytes, const char* what) {
+  hipError_t e = p.alloc(bytes ? bytes : 16);
   if (e == hipSuccess) return GSV_OK;
-  (void)hipGetLastError();
   size_t free_b = 0, total_b = 0;
   (void)hipMemGetInfo(&free_b, &total_b);
   char msg[256];
@@ -67,12 +66,12 @@ static int dev_alloc(void** p, size_t bytes, const char* what) {
                 double(total_b) / 1e9);
   return fail(GSV_ERR_DEVICE, msg);
 }
-#define DEVALLOC(p, bytes, what) do { int _rc = dev_alloc(reinterpret_cast<void**>(p), (bytes), (what)); if (_rc) return _rc; } while (0)
+#define DEVALLOC(p, bytes, what) do { int _rc = dev_alloc((p), (bytes), (what)); if (_rc) return _rc; } while (0)
 // ---- deferred release ---------------------------------------------------------------------------------------------------------------
-// hipFree / hipStreamDestroy synchronise the device.  While a streaming pass runs that is at best a stall of whoever destroys something
+// Releasing device memory or a stream synchronises the device.  While a streaming pass runs that is at best a stall of whoever destroys something
 // and at worst a deadlock: a ring pass waits for the host's stream position, which waits for a sink / source callback — and a host that
 // drops a session, plan, program or engine FROM that callback (a Rust `Drop` inside `CiphertextHandler::handle`, Python's collector on
-// the callback thread: profiles/r05_debug/) would wait in hipFree for that very pass until the device's watchdog ends it.  The destroy
+// the callback thread: profiles/r05_debug/) would wait in the release for that very pass until the device's watchdog ends it.  The destroy
 // entry points therefore never free while a streaming pass is in flight in this process: the request is queued and runs, in order, when
 // the last pass in flight has synchronised (the handle is invalid for the host from the moment destroy returns, as always).  Outside a
 // pass a destroy runs at once, under the gate's lock: a pass that starts meanwhile waits for it instead of being stalled by it.
@@ -114,10 +113,10 @@ void release_or_defer(std::function<void()> fn) {
 // had created before).  Streams of another priority level come from another pool of hardware queues, so these ask for the highest.
 // (Not for the evaluator of a garble -> evaluate pair: two long launches on queues of DIFFERENT priority, whichever way round, took
 // 46.5 s for the verifier instead of 42.9 s on equal terms — ensure_pair probes for a stream of the same priority that overlaps.)
-static hipError_t create_side_stream(hipStream_t* st, bool highest_priority) {
+static hipError_t create_side_stream(Stream& out, bool highest_priority) {
   int least = 0, greatest = 0;
-  if (!highest_priority || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || greatest == least) return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-  return hipStreamCreateWithPriority(st, hipStreamNonBlocking, greatest);
+  if (!highest_priority || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || greatest == least) return out.create(hipStreamNonBlocking);
+  return out.create(hipStreamNonBlocking, greatest);
 }
 
 struct gsv_recorder {
@@ -127,7 +126,7 @@ struct gsv_recorder {
 };
 
 struct DevProgram {
-  void *steps = nullptr, *ands = nullptr, *xors = nullptr, *fb_src = nullptr, *fb_dst = nullptr, *out_slots = nullptr, *ct_pos = nullptr;
+  DevBuf steps, ands, xors, fb_src, fb_dst, out_slots, ct_pos;
   size_t bytes = 0;
 };
 
@@ -151,7 +150,7 @@ struct gsv_program {
   const Program& variant(uint32_t ni) const { return ni <= window_div ? prog : *variants.at(ni); }
   std::unique_ptr<ProgramSource> src;
   std::mutex mu;
-  std::map<std::pair<int, int>, DevProgram> dev;  // per (device, instances per workgroup)
+  std::map<std::pair<int, int>, std::shared_ptr<DevProgram>> dev;  // per (device, image key); sessions look at the images through plain pointers: they never keep one alive
   // gsv_program_compile_opts(background = 1): the handle exists at once, `prog` is filled by a worker of the library's compile pool.  What a
   // plan recorder needs to take a call of the program (arity, gate count) is known from the recording and kept here; everything that
   // reads `prog` goes through program_ready() first.
@@ -190,25 +189,22 @@ struct gsv_plan {
 
 struct gsv_engine {
   int device = 0;
-  hipStream_t stream = nullptr;
-  void* te = nullptr;  // device T-tables
+  Stream stream;
+  DevBuf te;  // device T-tables
+  ~gsv_engine() { (void)hipSetDevice(device); }  // ... then te, then the stream
 };
 
 struct gsv_drain;
 struct PairState;
-extern "C" {
-static void destroy_drain(gsv_drain* d);
-static void destroy_pair(PairState* ps);
-}
 struct gsv_session {
   gsv_engine* e = nullptr;
   gsv_program* p = nullptr;
-  DevProgram dp;
+  const DevProgram* dp = nullptr;  // program sessions: the program's image on this device (owned by p->dev)
   size_t n_inst = 0;
   uint64_t replays = 1, ct_cap = 1;
-  void *W = nullptr, *VB = nullptr, *CT = nullptr, *delta = nullptr, *out = nullptr, *out_bits = nullptr, *in_bits = nullptr, *step_clock = nullptr, *ct_stage = nullptr, *ct_gate = nullptr;
-  size_t ct_gate_bytes = 0;  // capacity of ct_gate and of every buffer of ct_gate_more (ensure_ct_gate)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevBuf W, VB, CT, delta, out, out_bits, in_bits, step_clock, ct_stage;
+  DevBuf ct_gate;  // its bytes() is also the capacity of every buffer of ct_gate_more (ensure_ct_gate)
+  Event ev0, ev1;
   int hasher = 0;  // 0 AesNiHasher, 1 Blake3Hasher (gsv_session_set_hasher: any time between passes)
   knobs::Session kn; knobs::Pass pass;  // knobs.hpp: read when the session was created / at the top of the garble or evaluate entry point that runs (PassGuard, or assigned there): per pass
   uint32_t ni = 1;  // instances per workgroup the session was laid out for (chosen at creation: program variants, schedule)
@@ -225,20 +221,20 @@ struct gsv_session {
   uint64_t plan_max_segment = 0;  // ... of a gate-order buffer: the largest drain SEGMENT (schedule.hpp)
   bool ct_ring = false;              // the device block is a ring of plan_max_block records (schedule.hpp, SchedParams::ring_ct)
   std::string ring_diag;  // ring mode: the longest interval between two publications of the host's position in the last pass, and where it went
-  unsigned long long* host_ct_pos = nullptr;  // ring mode: the host's stream-position counter (page-locked, mapped into the device)
-  unsigned long long* dev_ct_pos = nullptr;   // ... its device address
-  hipStream_t aux_stream = nullptr;  // gather kernels and flag polls of the drain, beside the running window
-  uint32_t* host_done = nullptr;     // per call of the plan: workgroups that have finished it in the current pass (mapped host memory, written by the device)
-  uint32_t* dev_done = nullptr;      // ... its device address
-  struct CallDev { DevProgram dp; };
-  std::vector<CallDev> call_dev;
+  Stream aux_stream;  // gather kernels and flag polls of the drain, beside the running window
+  std::vector<const DevProgram*> call_dev;  // per call of the plan: its program's image (owned by that program)
   // Call-level schedule (schedule.hpp): windows of consecutive calls; the calls of a window run as a dataflow inside ONE launch
   // (grid.y = calls), each waiting for the completion flags of the calls it depends on.  Device tables in stream order: the call
   // descriptors, the concatenated wire hand-over lists (globals -> the call's scratch region -> globals), the dependency lists
   // (window-relative call indices) and the completion flags [instance group][call] (compared with the launch epoch: never reset).
   Schedule sched;
-  void *d_calls = nullptr, *d_copy_src = nullptr, *d_copy_dst = nullptr, *d_deps = nullptr, *d_flags = nullptr, *d_error = nullptr;
-  uint32_t flag_stride = 0, epoch = 0;
+  struct ScheduleState {  // what install_schedule allocates for `sched`; drop_schedule assigns a fresh one
+    DevBuf d_calls, d_copy_src, d_copy_dst, d_deps, d_flags, d_error, plan_out_slots;
+    MappedHost<uint32_t> done;  // per call of the plan: workgroups that have finished it in the current pass (mapped host memory, written by the device)
+    MappedHost<unsigned long long> ct_pos;  // ring mode: the host's stream-position counter (page-locked, mapped into the device)
+    uint32_t flag_stride = 0;
+  } sd;
+  uint32_t epoch = 0;
   // Safe-schedule fallback (round 6): the options the session was created with, the host's last inputs (re-staged when a pass is
   // repeated) and what the big allocations hold, so that a second schedule can be installed into the same session.
   gsv_plan_session_opts opts{};
@@ -252,16 +248,17 @@ struct gsv_session {
   size_t drain_instances = 0;               // streaming calls: only the first this-many instances' streams leave the device (0 = all)
   uint64_t next_call = 0;                   // streaming slices: the call the next slice must start with
   bool unchecked_slices = false;            // benchmarks may garble slices out of order (results are then meaningless)
-  void* plan_out_slots = nullptr;
   const Program& prog() const { return plan ? facade : p->variant(ni); }
   const Program& call_prog(size_t k) const { return plan->calls[k].prog->variant(ni); }
   uint32_t first_input_slot() const { return plan ? global_base : SLOT_FIRST_INPUT; }
   bool ran = false, last_eval = false, garbled = false;
   std::vector<uint64_t> ct_uploaded;  // per instance: records supplied by gsv_session_upload_ciphertexts
-  struct gsv_drain* drain = nullptr;   // streaming drain: copy streams, pinned buffers, per-instance MAC states (created on first use)
-  std::vector<void*> ct_gate_more;     // further gate-order buffers of the drain pipeline (ct_gate is the first)
-  void* ct_alt = nullptr;              // garble -> evaluate on the device: the second program-order ciphertext block
-  struct PairState* pair = nullptr;    // ... and its stream / events (created on first use)
+  std::unique_ptr<gsv_drain> drain;    // streaming drain: copy streams, pinned buffers, per-instance MAC states (created on first use)
+  std::vector<DevBuf> ct_gate_more;    // further gate-order buffers of the drain pipeline (ct_gate is the first)
+  DevBuf ct_alt;                       // garble -> evaluate on the device: the second program-order ciphertext block
+  std::unique_ptr<PairState> pair;     // ... and its stream / events (created on first use)
+  gsv_session();   // (both in engine_drain.ipp, where gsv_drain and PairState are complete)
+  ~gsv_session();  // selects the device and synchronises the engine's stream; the members then release what they hold
   uint64_t ct_stride() const { return plan ? (plan_retain ? plan->n_ct : plan_max_block) : ct_cap * p->prog.n_ct; }  // n_ct does not depend on the variant
 };
 PassGuard::PassGuard(gsv_session* s) { if (s) s->pass = knobs::Pass(); ReleaseGate& g = release_gate(); std::lock_guard<std::recursive_mutex> lk(g.mu); ++g.active; }

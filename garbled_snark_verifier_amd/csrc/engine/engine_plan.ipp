@@ -673,18 +673,14 @@ int gsv_plan_load(const char* path, gsv_engine* e, gsv_plan** out) {
   const uint64_t* const table = reinterpret_cast<const uint64_t*>(mp.base + h.table_off);
   if (e) HIPCHK(hipSetDevice(e->device));
   const size_t bounce_bytes = 64u << 20;
-  struct Bounce {
-    void* buf[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr};
-    ~Bounce() { for (void* q : buf) if (q) (void)hipHostFree(q); for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
-  } bounce_owner;
-  void** bounce = bounce_owner.buf;
-  hipEvent_t* bounce_ev = bounce_owner.ev;
+  MappedHost<uint8_t> bounce[2];
+  Event bounce_ev[2];
   int bounce_next = 0;
   if (e)
     for (int b = 0; b < 2; ++b) {
-      HIPCHK(hipHostMalloc(&bounce[b], bounce_bytes, hipHostMallocDefault));
-      HIPCHK(hipEventCreateWithFlags(&bounce_ev[b], hipEventDisableTiming));
-      HIPCHK(hipEventRecord(bounce_ev[b], e->stream));
+      HIPCHK(bounce[b].alloc(bounce_bytes, hipHostMallocDefault));
+      HIPCHK(bounce_ev[b].create(hipEventDisableTiming));
+      HIPCHK(hipEventRecord(bounce_ev[b].get(), e->stream.get()));
     }
   struct PlanOwner { gsv_plan* p; ~PlanOwner() { if (p) gsv_plan_destroy(p); } } po{new gsv_plan()};
   gsv_plan* plan = po.p;
@@ -740,13 +736,13 @@ int gsv_plan_load(const char* path, gsv_engine* e, gsv_plan** out) {
       continue;
     }
     q->device_only = true;
-    DevProgram d;
+    auto d = std::make_shared<DevProgram>();  // filed in q->dev when it is complete
     // Records go from the file to the device through two page-locked bounce buffers (pread + async copy): the process never
     // holds more than the buffers, whatever the size of the plan (the mapping above is only dereferenced for the metadata).
-    auto up = [&](void** dst, const void* src, size_t bytes) -> int {  // same padding rule as upload_program
-      HIPCHK(hipMalloc(dst, bytes + 32));
-      HIPCHK(hipMemsetAsync(*dst, 0, bytes + 32, e->stream));
-      d.bytes += bytes;
+    auto up = [&](DevBuf& dst, const void* src, size_t bytes) -> int {  // same padding rule as upload_program
+      HIPCHK(dst.alloc(bytes + 32));
+      HIPCHK(hipMemsetAsync(dst.get(), 0, bytes + 32, e->stream.get()));
+      d->bytes += bytes;
       if (!bytes) return GSV_OK;
       if (!src) return fail(GSV_ERR_INVALID, "internal: missing source");
       size_t off = size_t(static_cast<const uint8_t*>(src) - mp.base);
@@ -754,30 +750,29 @@ int gsv_plan_load(const char* path, gsv_engine* e, gsv_plan** out) {
         const size_t nb = std::min(bounce_bytes, bytes - done_b);
         const int b = bounce_next;
         bounce_next ^= 1;
-        HIPCHK(hipEventSynchronize(bounce_ev[b]));  // the previous copy out of this buffer has finished
+        HIPCHK(hipEventSynchronize(bounce_ev[b].get()));  // the previous copy out of this buffer has finished
         size_t got = 0;
         while (got < nb) {
-          const ssize_t r = pread(mp.fd, static_cast<uint8_t*>(bounce[b]) + got, nb - got, off_t(off + done_b + got));
+          const ssize_t r = pread(mp.fd, bounce[b].get() + got, nb - got, off_t(off + done_b + got));
           if (r <= 0) return fail(GSV_ERR_INVALID, std::string(path) + ": short read");
           got += size_t(r);
         }
-        HIPCHK(hipMemcpyAsync(static_cast<uint8_t*>(*dst) + done_b, bounce[b], nb, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipEventRecord(bounce_ev[b], e->stream));
+        HIPCHK(hipMemcpyAsync(dst.as<uint8_t>() + done_b, bounce[b].get(), nb, hipMemcpyHostToDevice, e->stream.get()));
+        HIPCHK(hipEventRecord(bounce_ev[b].get(), e->stream.get()));
         done_b += nb;
       }
       return GSV_OK;
     };
     int rc = GSV_OK;
-    void** dsts[7] = {&d.steps, &d.ands, &d.xors, &d.fb_src, &d.fb_dst, &d.out_slots, &d.ct_pos};
+    DevBuf* dsts[7] = {&d->steps, &d->ands, &d->xors, &d->fb_src, &d->fb_dst, &d->out_slots, &d->ct_pos};
     const void* srcs[7] = {steps, ands, xors, nullptr, nullptr, outs, ctp};
     const size_t lens[7] = {size_t(m.n_steps) * sizeof(StepDesc), size_t(m.n_ands) * sizeof(AndRec), size_t(m.n_xors) * sizeof(XorRec), 0, 0, size_t(m.n_outputs) * 4, size_t(m.n_ct_pos) * 4};
-    for (int i = 0; i < 7 && rc == GSV_OK; ++i) rc = up(dsts[i], srcs[i], lens[i]);
-    // file it before checking rc: gsv_plan_destroy then releases whatever was allocated
-    q->dev[{e->device, 1}] = d;  // image key 1 = `prog` itself (gsv_program::image_key)
+    for (int i = 0; i < 7 && rc == GSV_OK; ++i) rc = up(*dsts[i], srcs[i], lens[i]);
     if (rc != GSV_OK) return rc;
-    q->loaded_image_bytes = d.bytes;
+    q->loaded_image_bytes = d->bytes;
+    q->dev[{e->device, 1}] = std::move(d);  // image key 1 = `prog` itself (gsv_program::image_key)
   }
-  if (e) { HIPCHK(hipStreamSynchronize(e->stream)); plan->device = e->device; }
+  if (e) { HIPCHK(hipStreamSynchronize(e->stream.get())); plan->device = e->device; }
   pos = size_t(h.calls_off);
   for (uint32_t k = 0; k < h.n_calls && !bad; ++k) {
     uint32_t hdr[4];

@@ -113,7 +113,7 @@ int gsv_session_create_plan_opts(gsv_engine* e, const gsv_plan* plan, size_t n_i
     GSV_CATCH
   }
   for (size_t k = 0; k < plan->calls.size(); ++k) {
-    int rc = upload_program(e, plan->calls[k].prog, s->ni, &s->call_dev[k].dp);
+    int rc = upload_program(e, plan->calls[k].prog, s->ni, &s->call_dev[k]);
     if (rc) return rc;
   }
   size_t free_b = 0, total_b = 0;
@@ -121,29 +121,15 @@ int gsv_session_create_plan_opts(gsv_engine* e, const gsv_plan* plan, size_t n_i
   s->opts = o;
   {
     int rc = install_schedule(s.get(), o, prop.multiProcessorCount, free_b);
-    if (rc) return rc;
+    if (rc || (rc = alloc_session_buffers(s.get(), s->facade))) return rc;
   }
-  const Program& f = s->facade;
-  s->w_slots_cap = f.n_slots;
-  s->ct_records_cap = s->ct_stride();
-  DEVALLOC(&s->W, n_instances * size_t(f.n_slots) * 16, "the wire files");
-  HIPCHK(hipMalloc(&s->VB, n_instances * size_t(f.n_slots)));
-  HIPCHK(hipMemset(s->VB, 0, n_instances * size_t(f.n_slots)));
-  const size_t ct_bytes = n_instances * size_t(s->ct_stride()) * 16;
-  DEVALLOC(&s->CT, ct_bytes, "the ciphertext blocks");
-  HIPCHK(hipMalloc(&s->delta, n_instances * 16));
-  HIPCHK(hipMalloc(&s->out, n_instances * f.output_slots.size() * 16 + 16));
-  HIPCHK(hipMalloc(&s->out_bits, n_instances * f.output_slots.size() + 16));
-  HIPCHK(hipMalloc(&s->in_bits, n_instances * f.input_slots.size() + 16));
-  HIPCHK(hipEventCreate(&s->ev0));
-  HIPCHK(hipEventCreate(&s->ev1));
   *out = s.release();
   return GSV_OK;
 }
 // Everything of a plan session that depends on its SCHEDULE: the schedule itself, the wire-file layout (scratch regions in front of the
 // global wires), the ring's position counter, the completion counters, and the device tables of the window launches (call descriptors,
 // hand-over lists, dependency lists, completion flags).  Called by gsv_session_create_plan_opts and again, with the safe options, by
-// fall_back_to_safe_schedule (after drop_schedule).
+// fall_back_to_safe_schedule (after drop_schedule).  A failure leaves what was allocated so far in s->sd: it goes with the session.
 static int install_schedule(gsv_session* s, const gsv_plan_session_opts& o, int n_cus, size_t free_b) {
   const gsv_plan* plan = s->plan;
   const size_t n_instances = s->n_inst;
@@ -159,10 +145,10 @@ static int install_schedule(gsv_session* s, const gsv_plan_session_opts& o, int 
   s->ct_ring = sc.ring_ct != 0;
   s->plan_max_block = s->ct_ring ? sc.ring_ct : sc.max_window_ct;
   s->plan_max_segment = sc.max_segment_ct;
+  gsv_session::ScheduleState& sd = s->sd;
   if (s->ct_ring) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->host_ct_pos), 64, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->dev_ct_pos), s->host_ct_pos, 0));
-    *s->host_ct_pos = 0;
+    HIPCHK(sd.ct_pos.alloc(64, hipHostMallocMapped | hipHostMallocCoherent));
+    *sd.ct_pos.get() = 0;
   }
   if (uint64_t(scratch) + plan->n_globals > 0xFFFFFFF0ull) return fail(GSV_ERR_CIRCUIT, "plan wire file too large");
   Program& f = s->facade;
@@ -172,11 +158,7 @@ static int install_schedule(gsv_session* s, const gsv_plan_session_opts& o, int 
   for (uint32_t i = 0; i < plan->n_inputs; ++i) f.input_slots.push_back(scratch + i);
   auto global_slot = [&](uint32_t w) -> uint32_t { return w == PLAN_WIRE_FALSE ? SLOT_FALSE : w == PLAN_WIRE_TRUE ? SLOT_TRUE : scratch + w; };
   for (uint32_t w : plan->outputs) f.output_slots.push_back(global_slot(w));
-  auto up = [&](void** dst, const void* src, size_t bytes) -> int {
-    HIPCHK(hipMalloc(dst, bytes + 64));
-    if (bytes) HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return GSV_OK;
-  };
+  auto up = [&](DevBuf& dst, const void* src, size_t bytes) -> int { return upload_padded(dst, src, bytes, 64, false); };
   // descriptors, wire hand-over lists and dependency lists, all in stream order
   {
     const size_t n = plan->calls.size();
@@ -184,9 +166,8 @@ static int install_schedule(gsv_session* s, const gsv_plan_session_opts& o, int 
     std::vector<uint32_t> csrc, cdst, deps;
     {
       // the device-written completion counters (one per call of the PLAN: windows enqueued back to back never share a counter), in mapped host memory
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->host_done), n * 4 + 64, hipHostMallocMapped | hipHostMallocCoherent));
-      std::memset(s->host_done, 0, n * 4 + 64);
-      HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->dev_done), s->host_done, 0));
+      HIPCHK(sd.done.alloc(n * 4 + 64, hipHostMallocMapped | hipHostMallocCoherent));
+      std::memset(sd.done.get(), 0, n * 4 + 64);
     }
     for (const Schedule::Window& w : sc.windows) {
       for (uint32_t k = w.call0; k < w.call1; ++k) {
@@ -195,10 +176,10 @@ static int install_schedule(gsv_session* s, const gsv_plan_session_opts& o, int 
         const uint32_t base = sc.scratch_base[k];
         dev::CallDesc& d = cds[k];
         std::memset(&d, 0, sizeof d);
-        d.steps = s->call_dev[k].dp.steps; d.ands = s->call_dev[k].dp.ands; d.xors = s->call_dev[k].dp.xors;
+        d.steps = s->call_dev[k]->steps.get(); d.ands = s->call_dev[k]->ands.get(); d.xors = s->call_dev[k]->xors.get();
         d.gid_off = c.gid_off; d.ct_off = s->plan_retain ? c.ct_off : s->ct_ring ? sc.ring_off[k] : c.ct_off - w.ct0;
-        if (s->ct_ring) { d.ct_need = sc.ring_need[k]; d.ct_ready = sc.seg_end[k]; d.ct_pos = s->dev_ct_pos; }
-        d.done_host = s->dev_done + k;
+        if (s->ct_ring) { d.ct_need = sc.ring_need[k]; d.ct_ready = sc.seg_end[k]; d.ct_pos = sd.ct_pos.dev(); }
+        d.done_host = sd.done.dev() + k;
         d.w_base = base; d.n_steps = g.n_steps; d.and_terms = g.and_terms;
         d.pre_off = uint32_t(csrc.size());
         if (base != 0)  // the call's own copies of the constant labels (FALSE, TRUE, the all-zero label) in front of its scratch region
@@ -216,35 +197,29 @@ static int install_schedule(gsv_session* s, const gsv_plan_session_opts& o, int 
         d.n_deps = uint32_t(deps.size()) - d.dep_off;
         if (csrc.size() > 0xFFFFFF00ull) return fail(GSV_ERR_CIRCUIT, "plan hand-over lists too large");
       }
-      s->flag_stride = std::max<uint32_t>(s->flag_stride, w.call1 - w.call0 + 2);  // + a slot nobody writes (fault injection below) + the group's progress counter (kernels.hip, watchdog)
+      sd.flag_stride = std::max<uint32_t>(sd.flag_stride, w.call1 - w.call0 + 2);  // + a slot nobody writes (fault injection below) + the group's progress counter (kernels.hip, watchdog)
     }
     // GSV_FAULT_WITHHOLD_DEP=1 (tests): the first dependency of the first call that has one is pointed at the slot nobody writes — on
     // the device exactly what a violated dispatch-order assumption looks like (a dependency that never completes).  Never for the safe schedule.
     if (!s->safe_mode && kn.fault_withhold_dep)
-      for (size_t k = 0; k < n; ++k) if (cds[k].n_deps) { deps[cds[k].dep_off] = s->flag_stride - 2; break; }
+      for (size_t k = 0; k < n; ++k) if (cds[k].n_deps) { deps[cds[k].dep_off] = sd.flag_stride - 2; break; }
     // one flag row per instance: the rows are indexed by blockIdx.x, and a session switched to BLAKE3 after its creation launches one
     // workgroup per instance whatever s->ni says (gsv_session::launch_ni) — flag_stride * 4 bytes per instance
     const size_t n_rows = n_instances;
     int rc;
-    if ((rc = up(&s->d_calls, cds.data(), cds.size() * sizeof(dev::CallDesc))) || (rc = up(&s->d_copy_src, csrc.data(), csrc.size() * 4)) || (rc = up(&s->d_copy_dst, cdst.data(), cdst.size() * 4)) ||
-        (rc = up(&s->d_deps, deps.data(), deps.size() * 4)))
+    if ((rc = up(sd.d_calls, cds.data(), cds.size() * sizeof(dev::CallDesc))) || (rc = up(sd.d_copy_src, csrc.data(), csrc.size() * 4)) || (rc = up(sd.d_copy_dst, cdst.data(), cdst.size() * 4)) ||
+        (rc = up(sd.d_deps, deps.data(), deps.size() * 4)))
       return rc;
-    HIPCHK(hipMalloc(&s->d_flags, n_rows * size_t(s->flag_stride) * 4 + 64));
-    HIPCHK(hipMemset(s->d_flags, 0, n_rows * size_t(s->flag_stride) * 4 + 64));
-    HIPCHK(hipMalloc(&s->d_error, 64));
-    HIPCHK(hipMemset(s->d_error, 0, 64));
-    if ((rc = up(&s->plan_out_slots, f.output_slots.data(), f.output_slots.size() * 4))) return rc;
+    HIPCHK(sd.d_flags.alloc(n_rows * size_t(sd.flag_stride) * 4 + 64));
+    HIPCHK(hipMemset(sd.d_flags.get(), 0, sd.d_flags.bytes()));
+    HIPCHK(sd.d_error.alloc(64));
+    HIPCHK(hipMemset(sd.d_error.get(), 0, 64));
+    if ((rc = up(sd.plan_out_slots, f.output_slots.data(), f.output_slots.size() * 4))) return rc;
   }
   return GSV_OK;
 }
 // the schedule-dependent state of a session, released (the caller has synchronised the device's streams)
-static void drop_schedule(gsv_session* s) {
-  for (void** q : {&s->d_calls, &s->d_copy_src, &s->d_copy_dst, &s->d_deps, &s->d_flags, &s->d_error, &s->plan_out_slots}) { if (*q) (void)hipFree(*q); *q = nullptr; }
-  if (s->host_done) (void)hipHostFree(s->host_done);
-  if (s->host_ct_pos) (void)hipHostFree(s->host_ct_pos);
-  s->host_done = nullptr; s->dev_done = nullptr; s->host_ct_pos = nullptr; s->dev_ct_pos = nullptr;
-  s->flag_stride = 0; s->next_call = 0;
-}
+static void drop_schedule(gsv_session* s) { s->sd = gsv_session::ScheduleState(); s->next_call = 0; }
 int gsv_session_plan_schedule_info(const gsv_session* s, gsv_plan_schedule_info* info) {
   if (!s || !s->plan || !info) return fail(GSV_ERR_INVALID, "null argument / not a plan session");
   const Schedule& sc = s->sched;
@@ -282,8 +257,8 @@ static int stage_labels(gsv_session* s, const uint8_t* consts, const uint8_t* in
   if (s->plan) {  // constants at slots 0..2, inputs at the head of the global region: two strided copies
     std::vector<uint8_t> host(s->n_inst * 48, 0);
     for (size_t i = 0; i < s->n_inst; ++i) std::memcpy(&host[i * 48], consts + 32 * i, 32);
-    HIPCHK(hipMemcpy2D(s->W, size_t(g.n_slots) * 16, host.data(), 48, 48, s->n_inst, hipMemcpyHostToDevice));
-    if (n_in) HIPCHK(hipMemcpy2D(static_cast<uint8_t*>(s->W) + size_t(s->global_base) * 16, size_t(g.n_slots) * 16, inputs, n_in * 16, n_in * 16, s->n_inst, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy2D(s->W.get(), size_t(g.n_slots) * 16, host.data(), 48, 48, s->n_inst, hipMemcpyHostToDevice));
+    if (n_in) HIPCHK(hipMemcpy2D(static_cast<uint8_t*>(s->W.get()) + size_t(s->global_base) * 16, size_t(g.n_slots) * 16, inputs, n_in * 16, n_in * 16, s->n_inst, hipMemcpyHostToDevice));
     return GSV_OK;
   }
   const size_t row = (SLOT_FIRST_INPUT + n_in) * 16;
@@ -292,7 +267,7 @@ static int stage_labels(gsv_session* s, const uint8_t* consts, const uint8_t* in
     std::memcpy(&host[i * row], consts + 32 * i, 32);
     if (n_in) std::memcpy(&host[i * row + SLOT_FIRST_INPUT * 16], inputs + i * n_in * 16, n_in * 16);
   }
-  HIPCHK(hipMemcpy2D(s->W, size_t(g.n_slots) * 16, host.data(), row, row, s->n_inst, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy2D(s->W.get(), size_t(g.n_slots) * 16, host.data(), row, row, s->n_inst, hipMemcpyHostToDevice));
   return GSV_OK;
 }
 
@@ -309,7 +284,7 @@ static void stash_inputs(gsv_session* s, int kind, const uint8_t* delta, const u
 }
 static int set_garble_inputs_impl(gsv_session* s, const uint8_t* delta, const uint8_t* const_label0, const uint8_t* input_label0) {
   HIPCHK(hipSetDevice(s->e->device));
-  HIPCHK(hipMemcpy(s->delta, delta, s->n_inst * 16, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(s->delta.get(), delta, s->n_inst * 16, hipMemcpyHostToDevice));
   return stage_labels(s, const_label0, input_label0);
 }
 int gsv_session_set_garble_inputs(gsv_session* s, const uint8_t* delta, const uint8_t* const_label0, const uint8_t* input_label0) {
@@ -330,15 +305,15 @@ static int set_evaluate_inputs_impl(gsv_session* s, const uint8_t* const_active,
   const Program& g = s->prog();
   const size_t n_in = g.input_slots.size();
   // plaintext bits: constants FALSE=0 / TRUE=1 (evaluate_mode.rs:104-121), then the input bits
-  HIPCHK(hipMemset(s->VB, 0, s->n_inst * size_t(g.n_slots)));
+  HIPCHK(hipMemset(s->VB.get(), 0, s->n_inst * size_t(g.n_slots)));
   std::vector<uint8_t> two(s->n_inst * 2);
   for (size_t i = 0; i < s->n_inst; ++i) { two[2 * i] = 0; two[2 * i + 1] = 1; }
-  HIPCHK(hipMemcpy2D(s->VB, g.n_slots, two.data(), 2, 2, s->n_inst, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy2D(s->VB.get(), g.n_slots, two.data(), 2, 2, s->n_inst, hipMemcpyHostToDevice));
   if (n_in) {
     std::vector<uint8_t> nb(s->n_inst * n_in);
     for (size_t i = 0; i < nb.size(); ++i) nb[i] = input_bits[i] ? 1 : 0;
-    HIPCHK(hipMemcpy(s->in_bits, nb.data(), nb.size(), hipMemcpyHostToDevice));
-    if (gsvk_scatter_bits(s->VB, g.n_slots, s->first_input_slot(), s->in_bits, uint32_t(n_in), uint32_t(s->n_inst), nullptr) != 0) return fail(GSV_ERR_DEVICE, "scatter_bits launch failed");
+    HIPCHK(hipMemcpy(s->in_bits.get(), nb.data(), nb.size(), hipMemcpyHostToDevice));
+    if (gsvk_scatter_bits(s->VB.get(), g.n_slots, s->first_input_slot(), s->in_bits.get(), uint32_t(n_in), uint32_t(s->n_inst), nullptr) != 0) return fail(GSV_ERR_DEVICE, "scatter_bits launch failed");
     HIPCHK(hipDeviceSynchronize());
   }
   return GSV_OK;
@@ -348,19 +323,19 @@ static int set_evaluate_inputs_impl(gsv_session* s, const uint8_t* const_active,
 // and a gather / scatter kernel.
 static const uint64_t CT_STAGE_RECORDS = 1ull << 20;  // 16 MiB
 static int ensure_ct_stage(gsv_session* s) {
-  if (!s->ct_stage) HIPCHK(hipMalloc(&s->ct_stage, CT_STAGE_RECORDS * 16));
+  if (!s->ct_stage) HIPCHK(s->ct_stage.alloc(CT_STAGE_RECORDS * 16));
   return GSV_OK;
 }
 // stage[0..n) <-> gate-order records [first, first+n) of one instance's stream.  Program sessions: one permutation per replay
 // block; plan sessions: one per call block.
 static int permute_range(gsv_session* s, size_t instance, uint64_t first, uint64_t n, int scatter) {
-  uint8_t* stream = static_cast<uint8_t*>(s->CT) + instance * s->ct_stride() * 16;
-  if (!s->plan) return gsvk_permute_ciphertexts(stream, s->dp.ct_pos, s->prog().n_ct, first, n, s->ct_stage, scatter, s->e->stream);
+  uint8_t* stream = static_cast<uint8_t*>(s->CT.get()) + instance * s->ct_stride() * 16;
+  if (!s->plan) return gsvk_permute_ciphertexts(stream, s->dp->ct_pos.as<const uint32_t>(), s->prog().n_ct, first, n, s->ct_stage.get(), scatter, s->e->stream.get());
   for (size_t k = 0; k < s->plan->calls.size(); ++k) {
     const uint64_t b0 = s->plan->calls[k].ct_off, b1 = b0 + s->call_prog(k).n_ct;
     const uint64_t lo = std::max(first, b0), hi = std::min(first + n, b1);
     if (lo >= hi) continue;
-    int rc = gsvk_permute_ciphertexts(stream + b0 * 16, s->call_dev[k].dp.ct_pos, b1 - b0, lo - b0, hi - lo, static_cast<uint8_t*>(s->ct_stage) + (lo - first) * 16, scatter, s->e->stream);
+    int rc = gsvk_permute_ciphertexts(stream + b0 * 16, s->call_dev[k]->ct_pos.as<const uint32_t>(), b1 - b0, lo - b0, hi - lo, static_cast<uint8_t*>(s->ct_stage.get()) + (lo - first) * 16, scatter, s->e->stream.get());
     if (rc) return rc;
   }
   return 0;
@@ -370,8 +345,8 @@ static int fetch_ciphertexts(gsv_session* s, size_t instance, uint64_t first, ui
   int rc = ensure_ct_stage(s);
   if (rc) return rc;
   if (permute_range(s, instance, first, n, 0) != 0) return fail(GSV_ERR_DEVICE, "ciphertext gather launch failed");
-  HIPCHK(hipMemcpyAsync(out, s->ct_stage, n * 16, hipMemcpyDeviceToHost, s->e->stream));
-  HIPCHK(hipStreamSynchronize(s->e->stream));
+  HIPCHK(hipMemcpyAsync(out, s->ct_stage.get(), n * 16, hipMemcpyDeviceToHost, s->e->stream.get()));
+  HIPCHK(hipStreamSynchronize(s->e->stream.get()));
   return GSV_OK;
 }
 
@@ -384,42 +359,46 @@ int gsv_session_upload_ciphertexts(gsv_session* s, size_t instance, const uint8_
   if (rc) return rc;
   for (uint64_t off = 0; off < n_records; off += CT_STAGE_RECORDS) {
     const uint64_t n = std::min<uint64_t>(CT_STAGE_RECORDS, n_records - off);
-    HIPCHK(hipMemcpyAsync(s->ct_stage, cts + off * 16, n * 16, hipMemcpyHostToDevice, s->e->stream));
+    HIPCHK(hipMemcpyAsync(s->ct_stage.get(), cts + off * 16, n * 16, hipMemcpyHostToDevice, s->e->stream.get()));
     if (permute_range(s, instance, off, n, 1) != 0) return fail(GSV_ERR_DEVICE, "ciphertext scatter launch failed");
-    HIPCHK(hipStreamSynchronize(s->e->stream));
+    HIPCHK(hipStreamSynchronize(s->e->stream.get()));
   }
   s->ct_uploaded[instance] = n_records;
   return GSV_OK;
 }
 
 static int launch_plan(gsv_session* s, uint64_t gate_id_base, bool eval);
+// What every launch of a session passes to the kernels, whatever it runs: the per-instance buffers (ciphertexts into / from `ct_block`), the layout, the hasher.
+static dev::KernelArgs session_kernel_args(const gsv_session* s, void* ct_block, uint64_t gate_id_base) {
+  dev::KernelArgs ka{};
+  ka.W = s->W.as<uint4>(); ka.VB = s->VB.as<uint8_t>(); ka.CT = static_cast<uint4*>(ct_block);
+  ka.delta = s->delta.as<const uint4>(); ka.te = s->e->te.as<const uint32_t>();
+  ka.ct_stride = s->ct_stride(); ka.gid_base = gate_id_base; ka.n_slots = s->prog().n_slots;
+  ka.n_instances = uint32_t(s->n_inst); ka.hasher = uint32_t(s->hasher); ka.instances_per_wg = s->launch_ni();
+  ka.diag = s->pass.diag;
+  return ka;
+}
 static int launch(gsv_session* s, uint64_t gate_id_base, bool eval, uint64_t rep_base = 0, uint64_t n_replays = 0) {
   if (s->plan) return launch_plan(s, gate_id_base, eval);
   const Program& g = s->prog();
   HIPCHK(hipSetDevice(s->e->device));
-  dev::KernelArgs ka{};
-  ka.steps = s->dp.steps; ka.ands = s->dp.ands; ka.xors = s->dp.xors;
-  ka.W = static_cast<uint4*>(s->W); ka.VB = static_cast<uint8_t*>(s->VB); ka.CT = static_cast<uint4*>(s->CT);
-  ka.delta = static_cast<const uint4*>(s->delta); ka.te = static_cast<const uint32_t*>(s->e->te);
-  ka.fb_src = static_cast<const uint32_t*>(s->dp.fb_src); ka.fb_dst = static_cast<const uint32_t*>(s->dp.fb_dst);
-  ka.ct_stride = s->ct_stride(); ka.gid_base = gate_id_base; ka.n_gates = g.n_gates; ka.n_ct = g.n_ct;
-  ka.n_steps = g.n_steps; ka.n_slots = g.n_slots; ka.replays = uint32_t(n_replays ? n_replays : s->replays); ka.rep_base = uint32_t(rep_base); ka.ct_cap_replays = uint32_t(s->ct_cap);
+  dev::KernelArgs ka = session_kernel_args(s, s->CT.get(), gate_id_base);
+  ka.steps = s->dp->steps.get(); ka.ands = s->dp->ands.get(); ka.xors = s->dp->xors.get();
+  ka.fb_src = s->dp->fb_src.as<const uint32_t>(); ka.fb_dst = s->dp->fb_dst.as<const uint32_t>();
+  ka.n_gates = g.n_gates; ka.n_ct = g.n_ct;
+  ka.n_steps = g.n_steps; ka.replays = uint32_t(n_replays ? n_replays : s->replays); ka.rep_base = uint32_t(rep_base); ka.ct_cap_replays = uint32_t(s->ct_cap);
   ka.n_fb = uint32_t(g.fb_src_slot.size()); ka.fb_stage_base = g.fb_stage_base;
-  ka.n_instances = uint32_t(s->n_inst);
-  ka.hasher = uint32_t(s->hasher);
   ka.and_terms = g.and_terms; ka.any_four_wire = g.and_terms == 4;
-  ka.step_clock = static_cast<unsigned long long*>(s->step_clock);
-  ka.instances_per_wg = s->launch_ni();
-  ka.diag = s->pass.diag;
-  HIPCHK(hipEventRecord(s->ev0, s->e->stream));
+  ka.step_clock = s->step_clock.as<unsigned long long>();
+  HIPCHK(hipEventRecord(s->ev0.get(), s->e->stream.get()));
   if (ka.n_steps) {
-    int lrc = gsvk_launch_program(&ka, uint32_t(s->n_inst), eval ? 1 : 0, s->e->stream);
+    int lrc = gsvk_launch_program(&ka, uint32_t(s->n_inst), eval ? 1 : 0, s->e->stream.get());
     if (lrc != 0) return fail(GSV_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipError_t(lrc)));
   }
-  HIPCHK(hipEventRecord(s->ev1, s->e->stream));
+  HIPCHK(hipEventRecord(s->ev1.get(), s->e->stream.get()));
   if (!g.output_slots.empty()) {
-    if (gsvk_gather_outputs(s->W, s->VB, g.n_slots, static_cast<const uint32_t*>(s->dp.out_slots), uint32_t(g.output_slots.size()),
-                            uint32_t(s->n_inst), s->out, eval ? s->out_bits : nullptr, s->e->stream) != 0)
+    if (gsvk_gather_outputs(s->W.get(), s->VB.get(), g.n_slots, s->dp->out_slots.as<const uint32_t>(), uint32_t(g.output_slots.size()),
+                            uint32_t(s->n_inst), s->out.get(), eval ? s->out_bits.get() : nullptr, s->e->stream.get()) != 0)
       return fail(GSV_ERR_DEVICE, "gather launch failed");
   }
   s->ran = true; s->last_eval = eval;
@@ -430,27 +409,22 @@ static int launch(gsv_session* s, uint64_t gate_id_base, bool eval, uint64_t rep
 // and publishes its outputs (kernels.hip).  A sequential schedule (one call in flight) is the same launch with each call depending on
 // its predecessor: the instance groups still drift apart instead of meeting at a launch boundary after every call.
 static int launch_plan_window(gsv_session* s, size_t w, uint64_t gate_id_base, bool eval, void* ct_block = nullptr, hipStream_t stream = nullptr) {
-  const Program& f = s->facade;
-  if (!ct_block) ct_block = s->CT;       // (garble -> evaluate: the garbler's current block, for both sessions)
-  if (!stream) stream = s->e->stream;
+  const gsv_session::ScheduleState& sd = s->sd;
+  if (!ct_block) ct_block = s->CT.get();       // (garble -> evaluate: the garbler's current block, for both sessions)
+  if (!stream) stream = s->e->stream.get();
   const Schedule::Window& win = s->sched.windows[w];
-  dev::KernelArgs ka{};
-  ka.calls = static_cast<const dev::CallDesc*>(s->d_calls) + win.call0;
-  ka.copy_src = static_cast<const uint32_t*>(s->d_copy_src); ka.copy_dst = static_cast<const uint32_t*>(s->d_copy_dst);
-  ka.deps = static_cast<const uint32_t*>(s->d_deps); ka.flags = static_cast<uint32_t*>(s->d_flags); ka.error = static_cast<uint32_t*>(s->d_error);
-  if (s->host_done) {  // (the counters of THIS window's calls: its launch of the previous pass has long finished — every pass ends synchronised)
-    std::memset(s->host_done + win.call0, 0, size_t(win.call1 - win.call0) * 4);
+  dev::KernelArgs ka = session_kernel_args(s, ct_block, gate_id_base);
+  ka.calls = sd.d_calls.as<const dev::CallDesc>() + win.call0;
+  ka.copy_src = sd.d_copy_src.as<const uint32_t>(); ka.copy_dst = sd.d_copy_dst.as<const uint32_t>();
+  ka.deps = sd.d_deps.as<const uint32_t>(); ka.flags = sd.d_flags.as<uint32_t>(); ka.error = sd.d_error.as<uint32_t>();
+  if (sd.done) {  // (the counters of THIS window's calls: its launch of the previous pass has long finished — every pass ends synchronised)
+    std::memset(sd.done.get() + win.call0, 0, size_t(win.call1 - win.call0) * 4);
     __atomic_thread_fence(__ATOMIC_RELEASE);
   }
-  ka.flag_stride = s->flag_stride; ka.epoch = ++s->epoch;
+  ka.flag_stride = sd.flag_stride; ka.epoch = ++s->epoch;
   ka.wait_ticks = (unsigned long long)(s->pass.dep_wait_seconds * 1e8);  // dependency watchdog (kernels.hip): seconds without ANY completed call of the instance group before a wait gives up
-  ka.W = static_cast<uint4*>(s->W); ka.VB = static_cast<uint8_t*>(s->VB); ka.CT = static_cast<uint4*>(ct_block);
-  ka.delta = static_cast<const uint4*>(s->delta); ka.te = static_cast<const uint32_t*>(s->e->te);
-  ka.ct_stride = s->ct_stride(); ka.gid_base = gate_id_base; ka.n_gates = 0; ka.n_ct = 0;
-  ka.n_steps = 0; ka.n_slots = f.n_slots; ka.replays = 1; ka.rep_base = 0; ka.ct_cap_replays = 1;
-  ka.n_instances = uint32_t(s->n_inst); ka.hasher = uint32_t(s->hasher); ka.instances_per_wg = s->launch_ni();
+  ka.replays = 1; ka.ct_cap_replays = 1;  // (n_gates, n_ct, n_steps, rep_base: 0 — the calls' descriptors carry their own)
   for (uint32_t k = win.call0; k < win.call1 && !ka.any_four_wire; ++k) ka.any_four_wire = s->call_prog(k).and_terms == 4;
-  ka.diag = s->pass.diag;
   int lrc = gsvk_launch_batch(&ka, uint32_t(s->n_inst), win.call1 - win.call0, eval ? 1 : 0, stream);
   if (lrc != 0) return fail(GSV_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipError_t(lrc)));
   return GSV_OK;
@@ -458,19 +432,19 @@ static int launch_plan_window(gsv_session* s, size_t w, uint64_t gate_id_base, b
 // after a synchronisation: did a dependency wait give up?
 static int check_plan_error(gsv_session* s) {
   uint32_t ew[16] = {0};
-  HIPCHK(hipMemcpy(ew, s->d_error, 64, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ew, s->sd.d_error.get(), 64, hipMemcpyDeviceToHost));
   const uint32_t err = ew[0];
   if (err == 2) {
     // which calls of the last window have not finished everywhere, and where the host's position stood (diagnostics)
     std::string open_calls;
-    if (s->host_done && !s->sched.windows.empty()) {
+    if (s->sd.done.get() && !s->sched.windows.empty()) {
       const uint32_t n_wg = uint32_t(s->launch_groups());
       const Schedule::Window& win = s->sched.windows.back();
       int shown = 0;
       for (uint32_t k = win.call0; k < win.call1 && shown < 12; ++k)
-        if (s->host_done[k] != n_wg) { open_calls += " " + std::to_string(k) + "(" + std::to_string(s->host_done[k]) + "/" + std::to_string(n_wg) + ", need " + std::to_string(s->sched.ring_need[k]) + ")"; ++shown; }
+        if (s->sd.done.get()[k] != n_wg) { open_calls += " " + std::to_string(k) + "(" + std::to_string(s->sd.done.get()[k]) + "/" + std::to_string(n_wg) + ", need " + std::to_string(s->sched.ring_need[k]) + ")"; ++shown; }
     }
-    return fail(GSV_ERR_DEVICE, "a call waited for the host's stream position (ciphertext ring) and saw it stand still at " + std::to_string(s->host_ct_pos ? *s->host_ct_pos : 0) +
+    return fail(GSV_ERR_DEVICE, "a call waited for the host's stream position (ciphertext ring) and saw it stand still at " + std::to_string(s->sd.ct_pos.get() ? *s->sd.ct_pos.get() : 0) +
                                     "; unfinished calls:" + open_calls + "; the call that gave up: " + std::to_string(ew[8]) + " of the window (instance group " + std::to_string(ew[9]) + "), it wanted position " +
                                     std::to_string((uint64_t(ew[11]) << 32) | ew[10]) + ", saw " + std::to_string((uint64_t(ew[13]) << 32) | ew[12]) + " unchanged for " +
                                     std::to_string(double((uint64_t(ew[15]) << 32) | ew[14]) * 1e-8) + " s" + (s->ring_diag.empty() ? "" : "; host: " + s->ring_diag) + "; results are invalid");
@@ -483,16 +457,16 @@ static int check_plan_error(gsv_session* s) {
 // relative to `gate_ct0` (the stream index of the buffer's first record) <-> the window's device block.
 static int permute_plan_calls(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, uint64_t gate_ct0, uint64_t gate_stride, int scatter, void* ct_block, void* gate_buf, hipStream_t stream) {
   const Schedule::Window& win = s->sched.windows[w];
-  if (!ct_block) ct_block = s->CT;
-  if (!gate_buf) gate_buf = s->ct_gate;
-  if (!stream) stream = s->e->stream;
+  if (!ct_block) ct_block = s->CT.get();
+  if (!gate_buf) gate_buf = s->ct_gate.get();
+  if (!stream) stream = s->e->stream.get();
   for (uint32_t k = k0; k < k1; ++k) {
     const Program& cp = s->call_prog(k);
     if (!cp.n_ct) continue;
     const uint64_t rel = s->plan->calls[k].ct_off - win.ct0;
     uint8_t* block = static_cast<uint8_t*>(ct_block) + (s->plan_retain ? s->plan->calls[k].ct_off : s->ct_ring ? s->sched.ring_off[k] : rel) * 16;
     const size_t n_gather = (!scatter && s->drain_instances) ? std::min(s->drain_instances, s->n_inst) : s->n_inst;  // gsv_session_set_drain_instances
-    if (gsvk_gather_segment(block, s->ct_stride(), s->call_dev[k].dp.ct_pos, cp.n_ct, 1, uint32_t(n_gather), static_cast<uint8_t*>(gate_buf) + (s->plan->calls[k].ct_off - gate_ct0) * 16, gate_stride, scatter, stream) != 0)
+    if (gsvk_gather_segment(block, s->ct_stride(), s->call_dev[k]->ct_pos.as<const uint32_t>(), cp.n_ct, 1, uint32_t(n_gather), static_cast<uint8_t*>(gate_buf) + (s->plan->calls[k].ct_off - gate_ct0) * 16, gate_stride, scatter, stream) != 0)
       return fail(GSV_ERR_DEVICE, scatter ? "ciphertext scatter launch failed" : "ciphertext gather launch failed");
   }
   return GSV_OK;
@@ -513,8 +487,8 @@ static int window_range(const gsv_session* s, size_t c0, size_t c1, size_t* w0, 
 static int gather_plan_outputs(gsv_session* s, bool eval) {
   const Program& f = s->facade;
   if (!f.output_slots.empty()) {
-    if (gsvk_gather_outputs(s->W, s->VB, f.n_slots, static_cast<const uint32_t*>(s->plan_out_slots), uint32_t(f.output_slots.size()), uint32_t(s->n_inst), s->out,
-                            eval ? s->out_bits : nullptr, s->e->stream) != 0) return fail(GSV_ERR_DEVICE, "gather launch failed");
+    if (gsvk_gather_outputs(s->W.get(), s->VB.get(), f.n_slots, s->sd.plan_out_slots.as<const uint32_t>(), uint32_t(f.output_slots.size()), uint32_t(s->n_inst), s->out.get(),
+                            eval ? s->out_bits.get() : nullptr, s->e->stream.get()) != 0) return fail(GSV_ERR_DEVICE, "gather launch failed");
   }
   s->ran = true; s->last_eval = eval;
   return GSV_OK;
@@ -522,13 +496,13 @@ static int gather_plan_outputs(gsv_session* s, bool eval) {
 static int launch_plan(gsv_session* s, uint64_t gate_id_base, bool eval) {
   if (!s->plan_retain) return fail(GSV_ERR_INVALID, "this plan session keeps one window of ciphertexts only: use gsv_session_garble_streaming");
   HIPCHK(hipSetDevice(s->e->device));
-  HIPCHK(hipMemsetAsync(s->d_error, 0, 4, s->e->stream));  // every pass starts with a clean dependency-wait flag
-  HIPCHK(hipEventRecord(s->ev0, s->e->stream));
+  HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));  // every pass starts with a clean dependency-wait flag
+  HIPCHK(hipEventRecord(s->ev0.get(), s->e->stream.get()));
   for (size_t w = 0; w < s->sched.windows.size(); ++w) {
     int rc = launch_plan_window(s, w, gate_id_base, eval);
     if (rc) return rc;
   }
-  HIPCHK(hipEventRecord(s->ev1, s->e->stream));
+  HIPCHK(hipEventRecord(s->ev1.get(), s->e->stream.get()));
   return gather_plan_outputs(s, eval);
 }
 

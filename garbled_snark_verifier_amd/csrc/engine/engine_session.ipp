@@ -19,13 +19,20 @@ static uint32_t choose_instances_per_wg(size_t n_instances, int n_cus, uint32_t 
   while (ni > 1 && (ni > max_servable || ni > n_instances)) ni /= 2;
   return ni;
 }
-static int upload_program(gsv_engine* e, gsv_program* p, uint32_t ni, DevProgram* out) {
+// One device buffer of `bytes` + `pad` bytes holding `src` — `zeroed`: the padding too (without, it is never read).
+static int upload_padded(DevBuf& dst, const void* src, size_t bytes, size_t pad, bool zeroed) {
+  HIPCHK(dst.alloc(bytes + pad));
+  if (zeroed) HIPCHK(hipMemset(dst.get(), 0, bytes + pad));
+  if (bytes) HIPCHK(hipMemcpy(dst.get(), src, bytes, hipMemcpyHostToDevice));
+  return GSV_OK;
+}
+static int upload_program(gsv_engine* e, gsv_program* p, uint32_t ni, const DevProgram** out) {
   std::lock_guard<std::mutex> lk(p->mu);
   // one image per compiled variant: a program compiled for a share of the window serves every layout up to it from ONE copy in HBM
   // (the verifier plan's images are 41 GB)
   const int key = int(p->image_key(ni));
   auto it = p->dev.find({e->device, key});
-  if (it != p->dev.end()) { *out = it->second; return GSV_OK; }
+  if (it != p->dev.end()) { *out = it->second.get(); return GSV_OK; }
   // a program loaded by gsv_plan_load(path, engine) has no host copy of its records: there is nothing to upload to another device
   if (p->prog.spilled) return fail(GSV_ERR_INVALID, "this program's records were written to a plan file and dropped (gsv_plan_build_file / a plan recorder with a plan file): load the file with gsv_plan_load");
   if (p->device_only) return fail(GSV_ERR_INVALID, "this program was loaded straight into another device's memory (gsv_plan_load with an engine): it has no image for device " + std::to_string(e->device));
@@ -34,26 +41,46 @@ static int upload_program(gsv_engine* e, gsv_program* p, uint32_t ni, DevProgram
     compile_window_variant(p, ni);
     GSV_CATCH
   }
-  DevProgram d;
+  auto d = std::make_shared<DevProgram>();  // filed in p->dev when it is complete: a failed upload releases what it allocated
   const Program& g = p->variant(ni);
-  auto up = [&](void** dst, const void* src, size_t bytes) -> int {
-    // +32 bytes of zero padding: the kernel's record prefetch reads 24 bytes wherever a lane's record starts
-    HIPCHK(hipMalloc(dst, bytes + 32));
-    HIPCHK(hipMemset(*dst, 0, bytes + 32));
-    if (bytes) HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    d.bytes += bytes;
-    return GSV_OK;
+  auto up = [&](DevBuf& dst, const void* src, size_t bytes) -> int {
+    d->bytes += bytes;
+    return upload_padded(dst, src, bytes, 32, true);  // 32 bytes of zero padding: the kernel's record prefetch reads 24 bytes wherever a lane's record starts
   };
   int rc;
-  if ((rc = up(&d.steps, g.steps.data(), g.steps.size() * sizeof(StepDesc)))) return rc;
-  if ((rc = up(&d.ands, g.ands.data(), g.ands.size() * sizeof(AndRec)))) return rc;
-  if ((rc = up(&d.xors, g.xors.data(), g.xors.size() * sizeof(XorRec)))) return rc;
-  if ((rc = up(&d.fb_src, g.fb_src_slot.data(), g.fb_src_slot.size() * 4))) return rc;
-  if ((rc = up(&d.fb_dst, g.fb_dst_slot.data(), g.fb_dst_slot.size() * 4))) return rc;
-  if ((rc = up(&d.out_slots, g.output_slots.data(), g.output_slots.size() * 4))) return rc;
-  if ((rc = up(&d.ct_pos, g.ct_pos.data(), g.ct_pos.size() * 4))) return rc;
-  p->dev[{e->device, key}] = d;
-  *out = d;
+  if ((rc = up(d->steps, g.steps.data(), g.steps.size() * sizeof(StepDesc))) || (rc = up(d->ands, g.ands.data(), g.ands.size() * sizeof(AndRec))) ||
+      (rc = up(d->xors, g.xors.data(), g.xors.size() * sizeof(XorRec))) || (rc = up(d->fb_src, g.fb_src_slot.data(), g.fb_src_slot.size() * 4)) ||
+      (rc = up(d->fb_dst, g.fb_dst_slot.data(), g.fb_dst_slot.size() * 4)) || (rc = up(d->out_slots, g.output_slots.data(), g.output_slots.size() * 4)) ||
+      (rc = up(d->ct_pos, g.ct_pos.data(), g.ct_pos.size() * 4)))
+    return rc;
+  *out = d.get();
+  p->dev[{e->device, key}] = std::move(d);
+  return GSV_OK;
+}
+// The per-instance buffers and the two timing events of a session whose wire file and outputs are those of `g` (the program, or a plan
+// session's facade).  Called again after a second schedule was installed (fall_back_to_safe_schedule): the wire files and the
+// ciphertext block are then re-allocated only where the new schedule needs more, the rest exists.  VB is cleared either way.
+static int alloc_session_buffers(gsv_session* s, const Program& g) {
+  const size_t n = s->n_inst;
+  if (!s->W || g.n_slots > s->w_slots_cap) {
+    s->W.reset(); s->VB.reset();
+    DEVALLOC(s->W, n * size_t(g.n_slots) * 16, "the wire files");
+    HIPCHK(s->VB.alloc(n * size_t(g.n_slots)));
+    s->w_slots_cap = g.n_slots;
+  }
+  HIPCHK(hipMemset(s->VB.get(), 0, n * size_t(g.n_slots)));
+  if (!s->CT || s->ct_stride() > s->ct_records_cap) {
+    s->CT.reset(); s->ct_alt.reset();
+    DEVALLOC(s->CT, n * size_t(s->ct_stride()) * 16, "the ciphertext blocks");
+    s->ct_records_cap = s->ct_stride();
+  }
+  if (s->delta) return GSV_OK;
+  HIPCHK(s->delta.alloc(n * 16));
+  HIPCHK(s->out.alloc(n * g.output_slots.size() * 16 + 16));
+  HIPCHK(s->out_bits.alloc(n * g.output_slots.size() + 16));
+  HIPCHK(s->in_bits.alloc(n * g.input_slots.size() + 16));
+  HIPCHK(s->ev0.create());
+  HIPCHK(s->ev1.create());
   return GSV_OK;
 }
 
@@ -75,40 +102,11 @@ int gsv_session_create(gsv_engine* e, const gsv_program* cp, size_t n_instances,
     s->ni = choose_instances_per_wg(n_instances, prop.multiProcessorCount, p->src ? 4u : p->window_div, s->kn.instances_per_wg);
   }
   int rc = upload_program(e, p, s->ni, &s->dp);
-  if (rc) return rc;
-  const Program& g = s->prog();
-  DEVALLOC(&s->W, n_instances * size_t(g.n_slots) * 16, "the wire files");
-  HIPCHK(hipMalloc(&s->VB, n_instances * size_t(g.n_slots)));
-  HIPCHK(hipMemset(s->VB, 0, n_instances * size_t(g.n_slots)));
-  size_t ct_bytes = n_instances * size_t(s->ct_stride()) * 16;
-  DEVALLOC(&s->CT, ct_bytes, "the ciphertext blocks");
-  HIPCHK(hipMalloc(&s->delta, n_instances * 16));
-  HIPCHK(hipMalloc(&s->out, n_instances * g.output_slots.size() * 16 + 16));
-  HIPCHK(hipMalloc(&s->out_bits, n_instances * g.output_slots.size() + 16));
-  HIPCHK(hipMalloc(&s->in_bits, n_instances * g.input_slots.size() + 16));
-  HIPCHK(hipEventCreate(&s->ev0));
-  HIPCHK(hipEventCreate(&s->ev1));
+  if (rc || (rc = alloc_session_buffers(s.get(), s->prog()))) return rc;
   *out = s.release();
   return GSV_OK;
 }
-static void session_destroy_now(gsv_session* s) {
-  (void)hipSetDevice(s->e->device);
-  (void)hipStreamSynchronize(s->e->stream);
-  for (void* q : {s->W, s->VB, s->CT, s->delta, s->out, s->out_bits, s->in_bits, s->step_clock, s->ct_stage, s->ct_gate}) if (q) (void)hipFree(q);
-  for (void* q : {s->d_calls, s->d_copy_src, s->d_copy_dst, s->d_deps, s->d_flags, s->d_error}) if (q) (void)hipFree(q);
-  if (s->plan_out_slots) (void)hipFree(s->plan_out_slots);
-  for (void* q : s->ct_gate_more) if (q) (void)hipFree(q);
-  if (s->aux_stream) (void)hipStreamDestroy(s->aux_stream);
-  if (s->host_done) (void)hipHostFree(s->host_done);
-  if (s->host_ct_pos) (void)hipHostFree(s->host_ct_pos);
-  destroy_drain(s->drain);
-  destroy_pair(s->pair);
-  if (s->ct_alt) (void)hipFree(s->ct_alt);
-  if (s->ev0) (void)hipEventDestroy(s->ev0);
-  if (s->ev1) (void)hipEventDestroy(s->ev1);
-  delete s;
-}
 void gsv_session_destroy(gsv_session* s) {
   if (!s) return;
-  release_or_defer([s] { session_destroy_now(s); });
+  release_or_defer([s] { delete s; });  // ~gsv_session (engine_drain.ipp)
 }
