@@ -143,6 +143,10 @@ extern "C" {
     pub fn gsv_session_fallback_count(s: *const GsvSession, n: *mut u64) -> c_int;
     pub fn gsv_plan_build_file_pair(circuit_spec: *const c_char, units_csv_a: *const c_char, path_a: *const c_char, window_div_a: u32, units_csv_b: *const c_char, path_b: *const c_char, window_div_b: u32) -> c_int;
     pub fn gsv_plan_call_record_form(p: *const GsvPlan, call: u64, and_terms: *mut u32) -> c_int;
+    // BLAKE3 commitments: computed on the device beside (or instead of) the CBC-MAC; `blake3::Hasher` verifies the digests
+    pub fn gsv_session_garble_streaming_commit(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, dir: *const c_char, first_index: u64, n_threads: c_int, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int;
+    pub fn gsv_blake3_file(path: *const c_char, out: *mut u8) -> c_int;
+    pub fn gsv_engine_blake3_streams(e: *mut GsvEngine, data: *const u8, n_streams: u64, records_per_stream: u64, segment_records: *const u64, n_segments: u64, digests: *mut u8) -> c_int;
 }
 
 pub fn chk(rc: c_int) {

@@ -22,7 +22,7 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["GsvError", "lib", "Program", "Engine", "Session", "CircuitBuilder", "StreamingResult", "labels_from_seed", "GATE_NAMES", "cbcmac", "cbcmac_many",
-           "write_gc_file", "read_gc_file", "gc_file_name"]
+           "write_gc_file", "read_gc_file", "gc_file_name", "blake3", "blake3_file", "blake3_streams", "Blake3"]
 
 GATE_NAMES = ["And", "Nand", "Nimp", "Imp", "Ncimp", "Cimp", "Nor", "Or", "Xor", "Xnor", "Not"]
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -123,6 +123,8 @@ EXPORTS = [
     "gsv_session_create_plan_opts", "gsv_session_plan_schedule_info", "gsv_session_plan_window", "gsv_session_set_unchecked_slices",
     "gsv_session_garble_streaming_sink", "gsv_session_garble_evaluate", "gsv_session_evaluate_streaming_indexed", "gsv_session_evaluate_streaming_source",
     "gsv_recorder_allocate_wires", "gsv_plan_recorder_allocate_wires", "gsv_program_compile_opts", "gsv_program_wait", "gsv_plan_recorder_create_opts", "gsv_session_set_drain_instances",
+    "gsv_session_garble_streaming_commit", "gsv_blake3_create", "gsv_blake3_destroy", "gsv_blake3_update", "gsv_blake3_absorb_subtree", "gsv_blake3_finalize", "gsv_blake3_file",
+    "gsv_engine_blake3_streams", "gsv_engine_blake3_streams_seconds",
 ]
 
 # CiphertextHandler / CiphertextSource as host callbacks (include/gsv_engine.h: gsv_ct_sink_fn, gsv_ct_source_fn)
@@ -221,6 +223,16 @@ def lib():
         L.gsv_session_garble_evaluate.argtypes = [vp, vp, C.c_uint64, C.c_int, u8p]
         L.gsv_session_evaluate_streaming_indexed.argtypes = [vp, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64), u8p]
         L.gsv_session_evaluate_streaming_source.argtypes = [vp, C.c_uint64, CT_SOURCE_FN, vp, u8p]
+        L.gsv_session_garble_streaming_commit.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int, u8p, u8p]
+        L.gsv_blake3_create.argtypes = [C.POINTER(vp)]
+        L.gsv_blake3_destroy.argtypes = [vp]
+        L.gsv_blake3_destroy.restype = None
+        L.gsv_blake3_update.argtypes = [vp, u8p, C.c_uint64]
+        L.gsv_blake3_absorb_subtree.argtypes = [vp, u8p, C.c_uint32]
+        L.gsv_blake3_finalize.argtypes = [vp, u8p]
+        L.gsv_blake3_file.argtypes = [C.c_char_p, u8p]
+        L.gsv_engine_blake3_streams.argtypes = [vp, u8p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64, u8p]
+        L.gsv_engine_blake3_streams_seconds.argtypes = [vp, C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -265,6 +277,63 @@ def cbcmac_many(streams, states=None):
     ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
     _chk(lib().gsv_cbcmac_update_many(_p(st), ptrs, len(arrs), n))
     return [bytes(st[i]) for i in range(len(arrs))]
+
+
+class Blake3:
+    """The host's incremental BLAKE3 (plain hash mode, 32-byte digest): update(bytes) any number of times, digest().  absorb_subtree(cv, k)
+    takes the next 2^k chunks as the chaining value of their subtree — how a stream hashed on the device is finished."""
+
+    def __init__(self):
+        self.h = C.c_void_p()
+        _chk(lib().gsv_blake3_create(C.byref(self.h)))
+
+    def update(self, data):
+        a = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else _u8(data).reshape(-1)
+        _chk(lib().gsv_blake3_update(self.h, _p(a) if a.size else None, a.size))
+        return self
+
+    def absorb_subtree(self, chaining_value, log2_chunks):
+        _chk(lib().gsv_blake3_absorb_subtree(self.h, _p(np.frombuffer(bytes(chaining_value), np.uint8)), int(log2_chunks)))
+        return self
+
+    def digest(self):
+        out = np.zeros(32, np.uint8)
+        _chk(lib().gsv_blake3_finalize(self.h, _p(out)))
+        return out.tobytes()
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.gsv_blake3_destroy(self.h)
+            self.h = None
+
+
+def blake3(data):
+    """BLAKE3 (plain hash mode, 32 bytes) of a byte string / uint8 array: the commitment of a ciphertext stream given as gc-file bytes."""
+    return Blake3().update(data).digest()
+
+
+def blake3_file(path):
+    """BLAKE3 of a file's bytes (a gc_<i>.bin: what the evaluator compares with the garbler's BLAKE3 commitment)."""
+    out = np.zeros(32, np.uint8)
+    _chk(lib().gsv_blake3_file(os.fsencode(path), _p(out)))
+    return out.tobytes()
+
+
+def blake3_streams(engine, array, segments, with_seconds=False):
+    """BLAKE3 of n equally long streams on the device: `array` is [n_streams, records, 16] uint8, `segments` the record counts in which
+    the streams are fed to the drain's chunk / reduce / carry kernels (they add up to `records`).  Returns n_streams 32-byte digests;
+    with_seconds=True: (digests, device seconds from the first hash kernel to the last)."""
+    a = _u8(array)
+    assert a.ndim == 3 and a.shape[2] == 16, a.shape
+    seg = (C.c_uint64 * max(1, len(segments)))(*[int(x) for x in segments])
+    out = np.zeros((a.shape[0], 32), np.uint8)
+    _chk(lib().gsv_engine_blake3_streams(engine.h, _p(a) if a.size else None, a.shape[0], a.shape[1], seg, len(segments), _p(out)))
+    digests = [bytes(out[i]) for i in range(a.shape[0])]
+    if not with_seconds:
+        return digests
+    s = C.c_double()
+    _chk(lib().gsv_engine_blake3_streams_seconds(engine.h, C.byref(s)))
+    return digests, s.value
 
 
 def cbcmac_chains_per_step():
@@ -593,6 +662,13 @@ class PlanRecorder:
             pass
 
 
+def _check_commitment(commitment, discard):
+    if commitment not in ("cbcmac", "blake3", "both"):
+        raise ValueError("commitment must be 'cbcmac', 'blake3' or 'both'")
+    if discard and commitment != "cbcmac":
+        raise ValueError("discard=True drops the ciphertexts: it cannot be combined with commitment=%r" % commitment)
+
+
 class Session:
     """A batch of instances on one program (gsv_session) or, with a Plan, on a sequence of component programs."""
 
@@ -629,10 +705,28 @@ class Session:
     def garble(self, gate_id_base=0):
         _chk(lib().gsv_session_garble(self.h, gate_id_base))
 
-    def garble_streaming(self, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False):
+    def _garble_commit(self, commitment, gate_id_base, first_call, n_calls, directory, first_index, threads):
+        """commitment "blake3" | "both" (gsv_session_garble_streaming_commit): BLAKE3 digests are computed on the device and reported by the
+        call that ends the pass (None before); "both" returns (CBC-MACs, digests)."""
+        if commitment not in ("blake3", "both"):
+            raise ValueError("commitment must be 'cbcmac', 'blake3' or 'both'")
+        n = getattr(self, "n_drain", self.n)
+        macs = np.zeros((self.n, 16), np.uint8) if commitment == "both" else None
+        dig = np.zeros((n, 32), np.uint8)
+        ends_pass = (first_call == 0 and n_calls == 0) or not isinstance(self.program, Plan) or first_call + n_calls == self.schedule_info()["n_calls"]  # (else the engine leaves `dig` alone)
+        with _gc_paused():
+            _chk(lib().gsv_session_garble_streaming_commit(self.h, gate_id_base, first_call, n_calls, directory.encode() if directory else None, first_index, threads, _p(macs), _p(dig)))
+        digests = [bytes(dig[i]) for i in range(n)] if ends_pass else None
+        return ([bytes(macs[i]) for i in range(self.n)], digests) if commitment == "both" else digests
+
+    def garble_streaming(self, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False, commitment="cbcmac"):
         """Garble all replays while the host drains the stream segment by segment: returns the per-instance ciphertext
         hashes (CBC-MAC, gate order) and, with `directory`, writes gc_<first_index+i>.bin files.  discard=True: garble
-        only, the ciphertexts are dropped."""
+        only, the ciphertexts are dropped.  commitment="blake3": 32-byte BLAKE3 digests of the streams instead, computed on the
+        device (nothing of the stream is copied out unless `directory` is given); "both": (CBC-MACs, BLAKE3 digests)."""
+        _check_commitment(commitment, discard)
+        if commitment != "cbcmac":
+            return self._garble_commit(commitment, gate_id_base, 0, 0, directory, first_index, threads)
         if discard:
             with _gc_paused():
                 _chk(lib().gsv_session_garble_streaming(self.h, gate_id_base, None, 0, 0, None))
@@ -642,10 +736,16 @@ class Session:
             _chk(lib().gsv_session_garble_streaming(self.h, gate_id_base, directory.encode() if directory else None, first_index, threads, _p(out)))
         return [bytes(out[i]) for i in range(self.n)]
 
-    def garble_calls(self, first_call, n_calls, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False):
+    def garble_calls(self, first_call, n_calls, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False, commitment="cbcmac"):
         """Plan sessions: garble calls [first_call, first_call + n_calls) only (a slice of the plan).  Wires, gate ids and the
         CBC-MAC states continue from the previous slice; first_call == 0 starts a new pass.  Returns the MAC states after the
-        slice (the commitments once the last slice has run), or None with discard=True."""
+        slice (the commitments once the last slice has run), or None with discard=True.  commitment="blake3" / "both" as for
+        garble_streaming: the BLAKE3 state chains from slice to slice too, the digests are None until the slice that ends the pass."""
+        _check_commitment(commitment, discard)
+        if commitment != "cbcmac":
+            if first_call == 0 and n_calls == 0:
+                raise ValueError("an empty slice")  # (0, 0 means the whole pass to the C entry point)
+            return self._garble_commit(commitment, gate_id_base, first_call, n_calls, directory, first_index, threads)
         if discard:
             with _gc_paused():
                 _chk(lib().gsv_session_garble_streaming_calls(self.h, gate_id_base, first_call, n_calls, None, 0, 0, None))

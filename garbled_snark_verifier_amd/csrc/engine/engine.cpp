@@ -1,4 +1,4 @@
-// Host runtime + C ABI (include/gsv_engine.h) of the MI355X garbling engine: ONE translation unit in eight files.
+// Host runtime + C ABI (include/gsv_engine.h) of the MI355X garbling engine: ONE translation unit in nine files.
 // Device memory, streams and events are plain HIP runtime calls behind the owners of hip_owned.hpp; there is NO CPU execution path for
 // garble/evaluate — without a HIP device gsv_engine_create fails with GSV_ERR_DEVICE.
 //   hip_owned.hpp             move-only owners of device buffers, page-locked host buffers, streams and events: the only release calls
@@ -7,6 +7,7 @@
 //   engine_session.ipp        program sessions
 //   engine_plan.ipp           gsv_plan_*: built-in builder (single / dual), plan files, background compilation, plan recorder
 //   engine_plan_session.ipp   plan sessions: schedule + device tables, inputs, window launches
+//   engine_blake3.ipp         BLAKE3 commitments: gsv_blake3_*, the device tree hash of segmented streams
 //   engine_drain.ipp          streaming garbler: drain pipeline, garble || evaluate, safe-schedule fallback
 //   engine_evaluate.ipp       evaluation, read-back, CBC-MAC helpers
 // (The parts share file-local helpers and are included in this order inside one extern "C" block; build.py's dependency scan covers them.)
@@ -18,6 +19,7 @@ extern "C" {
 #include "engine_session.ipp"
 #include "engine_plan.ipp"
 #include "engine_plan_session.ipp"
+#include "engine_blake3.ipp"
 #include "engine_drain.ipp"
 #include "engine_evaluate.ipp"
 

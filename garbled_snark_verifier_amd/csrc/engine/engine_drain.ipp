@@ -104,14 +104,17 @@ static int garble_discard(gsv_session* s, uint64_t gate_id_base, size_t c0, size
   return rc;
 }
 
-// Where a drained stream goes (any combination): the per-instance CBC-MAC (AESAccumulatingHash), gc_<index>.bin files, a host callback.
+// Where a drained stream goes (any combination): the per-instance CBC-MAC (AESAccumulatingHash), gc_<index>.bin files, a host callback,
+// the per-instance BLAKE3 tree hash on the device (engine_blake3.ipp) — the one destination for which no ciphertext leaves the device.
 struct DrainSink {
   uint8_t* hashes = nullptr;           // n_inst x 16: the MAC states after this call
   const char* dir = nullptr;           // gc_<index>.bin, index = indexes ? indexes[i] : first_index + i
   uint64_t first_index = 0;
   gsv_ct_sink_fn fn = nullptr;         // CiphertextHandler::handle over a run of records of one instance
   void* user = nullptr;
-  bool any() const { return hashes || dir || fn; }
+  uint8_t* b3 = nullptr;               // n_inst x 32: the BLAKE3 digests, written by the call that ends the pass
+  bool host() const { return hashes || dir || fn; }  // the stream is copied to the host
+  bool any() const { return host() || b3; }
 };
 // Garble -> evaluate on the device (gsv_session_garble_evaluate): the evaluator session consumes window k from the garbler's
 // program-order block while the garbler writes window k+1 into the other one of two blocks.
@@ -259,7 +262,9 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   const bool new_pass = s->plan ? c0 == 0 : true;
   // the instances whose streams leave the device: all of them, or the first drain_instances (every instance is garbled either way)
   const size_t n_inst = s->drain_instances ? std::min(s->drain_instances, s->n_inst) : s->n_inst;
-  const bool want_drain = sink.any();
+  const bool want_drain = sink.any();    // finished segments are brought into gate order ...
+  const bool want_host = sink.host();    // ... and copied out by the workers
+  const bool want_b3 = sink.b3 != nullptr;
   const bool want_mac = sink.hashes != nullptr;
   const size_t GROUP = size_t(gsv_drain::group_for(n_inst, s->pass.drain_group));
   const size_t n_groups = (n_inst + GROUP - 1) / GROUP;
@@ -271,8 +276,20 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   const uint64_t seg_records = seg * n_ct;  // per instance
   if (want_drain) {
     if (seg_records) { int grc = ensure_ct_gate(s, n_inst * size_t(seg_records) * 16); if (grc) return grc; }
-    int rc = ensure_drain(s, T, seg_records, int(GROUP));
+    int rc = want_host ? ensure_drain(s, T, seg_records, int(GROUP)) : GSV_OK;
     if (rc) return rc;
+  }
+  // A pass that commits with BLAKE3 carries the same commitments in every slice: a slice without MAC workers leaves the MAC states
+  // behind, one without the hash kernels the BLAKE3 state, and the commitment returned at the end would cover part of the stream
+  {
+    const uint8_t commit = uint8_t((want_mac ? 1 : 0) | (want_b3 ? 2 : 0));
+    if (new_pass || !s->plan) s->pass_commit = commit;
+    else if (commit != s->pass_commit && ((commit | s->pass_commit) & 2)) return fail(GSV_ERR_INVALID, "every slice of a pass with a BLAKE3 commitment must ask for the same commitments as its first slice");
+  }
+  // BLAKE3: the state lives in the session like the MAC states — a new pass starts it afresh, later slices chain
+  if (want_b3) {
+    if (new_pass) { int rc = b3_begin(s->b3, n_inst, s->plan ? s->plan->n_ct : s->replays * g.n_ct, seg_records, s->pass.b3_subtree_log2); if (rc) return rc; }
+    else if (!s->b3 || s->b3->n_inst != n_inst || s->b3->seg_cap < seg_records) return fail(GSV_ERR_INVALID, "this slice continues a pass whose earlier slices computed no BLAKE3 commitment for these instances");
   }
   if (ev && (s->ct_ring || ev->ct_ring)) return fail(GSV_ERR_INVALID, "garble || evaluate pairs need sessions with explicit launch windows (window_ct_records, e.g. 1 << 28): the default is one whole-pass window over a ciphertext ring");
   if (ev) { int rc = ensure_pair(s); if (rc) return rc; }
@@ -281,8 +298,8 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   if (s->plan && new_pass) HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));  // a new pass starts with a clean dependency-wait flag
   if (ev && new_pass) HIPCHK(hipMemsetAsync(ev->sd.d_error.get(), 0, 4, s->e->stream.get()));
   std::vector<CbcMacHost> no_macs;
-  if (want_drain && (new_pass || s->drain->macs.size() != n_inst)) s->drain->macs.assign(n_inst, CbcMacHost());  // a new pass starts from h = 0; later slices chain
-  std::vector<CbcMacHost>& macs = want_drain ? s->drain->macs : no_macs;
+  if (want_host && (new_pass || s->drain->macs.size() != n_inst)) s->drain->macs.assign(n_inst, CbcMacHost());  // a new pass starts from h = 0; later slices chain
+  std::vector<CbcMacHost>& macs = want_host ? s->drain->macs : no_macs;
   std::vector<FILE*> files(n_inst, nullptr);
   std::vector<std::string> paths(n_inst);
   auto close_files = [&]() { for (FILE*& f : files) if (f) { std::fclose(f); f = nullptr; } };
@@ -295,7 +312,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
       if (!files[i]) { close_files(); return fail(GSV_ERR_INVALID, "cannot create " + paths[i]); }
     }
   std::atomic<int> err{0};
-  const uint64_t chunk = want_drain ? s->drain->chunk : 0;
+  const uint64_t chunk = want_host ? s->drain->chunk : 0;
   // The drain is a PIPELINE of segments: the device side (garble a window, bring it into gate order in one of `depth` gate-order
   // buffers) runs ahead of the host side (copy out, CBC-MAC, files, sink) by up to `depth` segments.  A window's ciphertext count is
   // fixed but its garbling time is not (the ladders and inversions produce a gigabyte of ciphertexts in seconds, the Miller loop in
@@ -309,7 +326,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
     size_t want = 1;
     size_t n_units = size_t((total - first + seg - 1) / seg);  // drain units of this call: segments (plans) or rings
     if (s->plan) { n_units = 0; for (size_t w = pw0; w < pw1; ++w) n_units += s->sched.windows[w].seg1 - s->sched.windows[w].seg0; }
-    if (seg_records && n_units > 1) {
+    if (seg_records && n_units > 1 && want_host) {  // (BLAKE3 alone: a buffer is free again when the hash kernels of its segment have finished, one serves)
       size_t free_b = 0, total_b = 0;
       (void)hipMemGetInfo(&free_b, &total_b);
       const size_t buf_bytes = n_inst * size_t(seg_records) * 16;
@@ -387,7 +404,43 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
     }
   };
   std::vector<std::thread> workers;
-  if (want_drain) for (size_t t = 0; t < T; ++t) workers.emplace_back(worker_main, t);
+  if (want_host) for (size_t t = 0; t < T; ++t) workers.emplace_back(worker_main, t);
+  // BLAKE3: the group values of a segment (32 bytes per 2^k chunks and instance) are folded into the instances' hashers by a small pool
+  // of their own, in segment order, off the thread that launches the windows; a task is released when every thread of the pool is done with it.
+  // What the launching thread itself does per segment is copy those values out of the page-locked buffer (b3_submit: 32 B x groups x
+  // instances, a few KiB), which has to happen before the next segment's copy lands there.
+  struct B3Task { std::vector<uint8_t> vals; uint32_t groups = 0; size_t done = 0; };
+  std::mutex b3_mu;
+  std::condition_variable b3_cv;
+  std::vector<std::unique_ptr<B3Task>> b3_tasks;
+  bool b3_closed = false;
+  const size_t B3T = want_b3 ? std::min<size_t>(4, n_inst) : 0;
+  const unsigned b3_k = want_b3 ? s->b3->k : 0;
+  auto b3_main = [&](size_t t) {
+    for (size_t j = 0;; ++j) {
+      B3Task* task;
+      {
+        std::unique_lock<std::mutex> lk(b3_mu);
+        b3_cv.wait(lk, [&] { return j < b3_tasks.size() || b3_closed; });
+        if (j >= b3_tasks.size()) return;
+        task = b3_tasks[j].get();
+      }
+      if (!b3_absorb(*s->b3, task->vals.data(), task->groups, b3_k, t, B3T)) err = 4;
+      std::lock_guard<std::mutex> lk(b3_mu);
+      if (++task->done == B3T) b3_tasks[j].reset();
+    }
+  };
+  std::vector<std::thread> b3_threads;
+  for (size_t t = 0; t < B3T; ++t) b3_threads.emplace_back(b3_main, t);
+  // after the stream the segment's hash kernels ran on has been synchronised: its group values leave the page-locked buffer
+  auto b3_submit = [&](uint32_t groups) {
+    if (!groups) return;
+    std::unique_ptr<B3Task> task(new B3Task());
+    task->groups = groups;
+    task->vals.assign(s->b3->pinned.get(), s->b3->pinned.get() + n_inst * size_t(groups) * 32);
+    { std::lock_guard<std::mutex> lk(b3_mu); b3_tasks.push_back(std::move(task)); }
+    b3_cv.notify_all();
+  };
   // GSV_DRAIN_STATS=1: where the host thread of the pipeline waits (for a free gate-order buffer = the host side is the slower stage;
   // for the kernel + gather = the device is), printed once per call
   const bool stats = s->pass.drain_stats;
@@ -397,7 +450,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   auto secs = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
   // blocks until the segment that last used buffer `b` has been consumed by every worker (segment index = its position in `segments`)
   auto wait_buffer = [&](size_t n_pushed) {
-    if (!want_drain || n_pushed < depth) return;
+    if (!want_host || n_pushed < depth) return;
     const auto t0 = std::chrono::steady_clock::now();
     std::unique_lock<std::mutex> lk(q_mu);
     q_cv.wait(lk, [&] { return seg_done[n_pushed - depth] == T; });
@@ -413,6 +466,10 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
     const auto t0 = std::chrono::steady_clock::now();
     for (auto& th : workers) th.join();
     workers.clear();
+    { std::lock_guard<std::mutex> lk(b3_mu); b3_closed = true; }
+    b3_cv.notify_all();
+    for (auto& th : b3_threads) th.join();
+    b3_threads.clear();
     t_wait_drain += secs(t0);
   };
   size_t n_pushed = 0;
@@ -420,7 +477,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   double worst_gap = 0;
   s->ring_diag.clear();
   Event device_done_owner;
-  if (want_drain && T + 1 > gsv_drain::usable_cores()) (void)device_done_owner.create(hipEventBlockingSync | hipEventDisableTiming);
+  if (want_host && T + 1 > gsv_drain::usable_cores()) (void)device_done_owner.create(hipEventBlockingSync | hipEventDisableTiming);
   const hipEvent_t device_done = device_done_owner.get();
   int rc = GSV_OK;
   // The stream the garbler's windows are launched on: the engine's, or — a garble || evaluate pair with CU-masked streams (ensure_pair) —
@@ -479,7 +536,10 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
           const auto tg = std::chrono::steady_clock::now();
           rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, seg_records, 0, block, gate_bufs[n_pushed % depth], s->aux_stream.get());
           if (rc != GSV_OK) break;
+          uint32_t b3_groups = 0;  // the hash kernels follow the gather on the side stream; the buffer is free again when they have finished
+          if (want_b3 && (rc = b3_segment(*s->b3, gate_bufs[n_pushed % depth], seg_records, sg.n_ct, s->aux_stream.get(), &b3_groups)) != GSV_OK) break;
           if (hipStreamSynchronize(s->aux_stream.get()) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "ciphertext gather failed"); break; }
+          if (want_b3) b3_submit(b3_groups);
           t_gather += secs(tg);
           if (s->ct_ring) {
             __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);  // the calls whose blocks overlap this segment's may write now
@@ -494,7 +554,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
             t_last_pub = std::chrono::steady_clock::now();
           }
           drained_records += sg.n_ct;
-          push_segment(sg.n_ct, sg.ct0, n_pushed % depth);
+          if (want_host) push_segment(sg.n_ct, sg.ct0, n_pushed % depth);
           ++n_pushed;
         }
         if (rc != GSV_OK) break;
@@ -513,6 +573,8 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
         break;
       }
     }
+    uint32_t b3_groups = 0;
+    if (want_b3 && (rc = b3_segment(*s->b3, gate_bufs[n_pushed % depth], seg_records, n_records, s->e->stream.get(), &b3_groups)) != GSV_OK) break;
     {
       // the workers own the cores when there is one chain per core: this thread then sleeps on a blocking-sync event instead of
       // spinning in hipStreamSynchronize
@@ -522,7 +584,9 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
       t_wait_device += secs(t0);
     }
     drained_records += n_records;
-    if (want_drain) { push_segment(n_records, base, n_pushed % depth); ++n_pushed; }
+    if (want_b3) b3_submit(b3_groups);
+    if (want_host) push_segment(n_records, base, n_pushed % depth);
+    if (want_drain) ++n_pushed;
   }
   if (s->ct_ring && rc != GSV_OK) {
     // a failed pass: calls of the running window may still wait for room in the ring — let them run out (the results are discarded)
@@ -546,8 +610,10 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   close_files();
   if (rc == GSV_OK && s->plan) rc = check_plan_error(s);
   if (rc == GSV_OK && ev) rc = check_plan_error(ev);
-  if (rc == GSV_OK && err) rc = fail(err == 2 ? GSV_ERR_INVALID : err == 3 ? GSV_ERR_INVALID : GSV_ERR_DEVICE,
-                                     err == 2 ? "short write to a gc file" : err == 3 ? "the ciphertext sink reported an error" : "device copy failed while draining ciphertexts");
+  if (rc == GSV_OK && err) rc = fail(err == 2 ? GSV_ERR_INVALID : err == 3 ? GSV_ERR_INVALID : err == 4 ? GSV_ERR_INVALID : GSV_ERR_DEVICE,
+                                     err == 2 ? "short write to a gc file" : err == 3 ? "the ciphertext sink reported an error" : err == 4 ? "internal: BLAKE3 group values out of order" : "device copy failed while draining ciphertexts");
+  // the call that ends the pass finishes the BLAKE3 streams: pending chunk values and the last chunks come to the host (<= 1 KiB + 32 B x 2^k per instance)
+  if (rc == GSV_OK && want_b3 && (!s->plan || c1 == s->plan->calls.size())) rc = b3_finish(*s->b3, s->e->stream.get(), sink.b3);
   if (rc != GSV_OK) { remove_files(); return rc; }
   if (want_mac) for (size_t i = 0; i < n_inst; ++i) macs[i].digest(sink.hashes + 16 * i);
   s->garbled = true;
@@ -627,6 +693,24 @@ int gsv_session_garble_streaming_calls(gsv_session* s, uint64_t gate_id_base, ui
   if (rc) return rc;
   if (dir && !hashes) return fail(GSV_ERR_INVALID, "null hash buffer");
   rc = garble_streaming_range(s, gate_id_base, size_t(first_call), size_t(first_call + n_calls), mac_file_sink(hashes, dir, first_index), n_threads);
+  if (rc == GSV_OK) { s->next_call = first_call + n_calls; s->garbled = s->plan_retain && s->next_call == s->plan->calls.size(); }
+  return rc;
+}
+// Either commitment or both (include/gsv_engine.h, "BLAKE3 commitments"): the CBC-MAC on the host's cores, BLAKE3 where the ciphertexts are.
+int gsv_session_garble_streaming_commit(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* dir, uint64_t first_index, int n_threads,
+                                        uint8_t* cbcmac_hashes, uint8_t* blake3_digests) {
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
+  if (!s) return fail(GSV_ERR_INVALID, "null argument");
+  DrainSink k = mac_file_sink(cbcmac_hashes, dir, first_index);
+  k.b3 = blake3_digests;
+  if (!s->plan) {
+    if (first_call || n_calls) return fail(GSV_ERR_INVALID, "program sessions are garbled in one pass (first_call = n_calls = 0)");
+    return garble_streaming_range(s, gate_id_base, 0, 1, k, n_threads);
+  }
+  if (first_call == 0 && n_calls == 0) n_calls = s->plan->calls.size();
+  int rc = check_slice(s, first_call, n_calls);
+  if (rc) return rc;
+  rc = garble_streaming_range(s, gate_id_base, size_t(first_call), size_t(first_call + n_calls), k, n_threads);
   if (rc == GSV_OK) { s->next_call = first_call + n_calls; s->garbled = s->plan_retain && s->next_call == s->plan->calls.size(); }
   return rc;
 }

@@ -191,11 +191,13 @@ struct gsv_engine {
   int device = 0;
   Stream stream;
   DevBuf te;  // device T-tables
+  double b3_streams_seconds = 0;  // last gsv_engine_blake3_streams: HIP-event time from the first hash kernel to the last (upload in front and the host's finish behind are outside)
   ~gsv_engine() { (void)hipSetDevice(device); }  // ... then te, then the stream
 };
 
 struct gsv_drain;
 struct PairState;
+struct B3Stream;
 struct gsv_session {
   gsv_engine* e = nullptr;
   gsv_program* p = nullptr;
@@ -254,10 +256,12 @@ struct gsv_session {
   bool ran = false, last_eval = false, garbled = false;
   std::vector<uint64_t> ct_uploaded;  // per instance: records supplied by gsv_session_upload_ciphertexts
   std::unique_ptr<gsv_drain> drain;    // streaming drain: copy streams, pinned buffers, per-instance MAC states (created on first use)
+  uint8_t pass_commit = 0;             // commitments of the pass in progress (1 CBC-MAC, 2 BLAKE3): a pass with BLAKE3 carries the same ones in every slice
+  std::unique_ptr<B3Stream> b3;        // BLAKE3 commitments of the drained streams: device buffers and per-instance hashers, beside drain->macs (engine_blake3.ipp)
   std::vector<DevBuf> ct_gate_more;    // further gate-order buffers of the drain pipeline (ct_gate is the first)
   DevBuf ct_alt;                       // garble -> evaluate on the device: the second program-order ciphertext block
   std::unique_ptr<PairState> pair;     // ... and its stream / events (created on first use)
-  gsv_session();   // (both in engine_drain.ipp, where gsv_drain and PairState are complete)
+  gsv_session();   // (both in engine_drain.ipp, where gsv_drain, PairState and B3Stream are complete)
   ~gsv_session();  // selects the device and synchronises the engine's stream; the members then release what they hold
   uint64_t ct_stride() const { return plan ? (plan_retain ? plan->n_ct : plan_max_block) : ct_cap * p->prog.n_ct; }  // n_ct does not depend on the variant
 };

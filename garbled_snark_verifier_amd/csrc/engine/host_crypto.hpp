@@ -9,6 +9,7 @@
 //                      GarbleMode::new + issue_garbled_wire draw them (garble_mode.rs:80-97,116-118);
 //                      only the stand-alone harness needs it: a Rust host hands labels in directly.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -230,6 +231,128 @@ class CbcMacHost {
 
  private:
   uint8_t h_[16];
+};
+
+// BLAKE3 in plain hash mode (no key, no derive-key context, 32-byte output), portable and incremental: the chunk state plus the
+// chaining-value stack of the specification.  Besides bytes it takes PRE-REDUCED subtrees — "the next 2^k chunks have this chaining
+// value" (absorb_subtree) — which is how a stream hashed on the device is finished: the device computes every chunk but the last and
+// reduces aligned groups of 2^k chunks to one parent value each (blake3_device.hpp), the host absorbs those values, hashes the last
+// chunk itself (the only place where ROOT can be due) and folds the stack.  Also hashes gc files, and is the twin the kernels are
+// tested against.
+class Blake3Host {
+ public:
+  static constexpr uint32_t CHUNK_START = 1, CHUNK_END = 2, PARENT = 4, ROOT = 8;
+  static constexpr uint32_t IV[8] = {0x6A09E667u, 0xBB67AE85u, 0x3C6EF372u, 0xA54FF53Au, 0x510E527Fu, 0x9B05688Cu, 0x1F83D9ABu, 0x5BE0CD19u};
+  Blake3Host() { std::memcpy(cv_, IV, sizeof cv_); }
+  // out = the first eight words of compress(cv, block, counter, block_len, flags)
+  static void compress(const uint32_t cv[8], const uint32_t block[16], uint64_t counter, uint32_t block_len, uint32_t flags, uint32_t out[8]) {
+    uint32_t v[16] = {cv[0], cv[1], cv[2], cv[3], cv[4], cv[5], cv[6], cv[7], IV[0], IV[1], IV[2], IV[3], uint32_t(counter), uint32_t(counter >> 32), block_len, flags};
+    uint32_t m[16], t[16];
+    std::memcpy(m, block, sizeof m);
+    static const uint8_t perm[16] = {2, 6, 3, 10, 7, 0, 4, 13, 1, 11, 12, 5, 9, 14, 15, 8};
+    for (int r = 0;; ++r) {
+      g(v, 0, 4, 8, 12, m[0], m[1]); g(v, 1, 5, 9, 13, m[2], m[3]); g(v, 2, 6, 10, 14, m[4], m[5]); g(v, 3, 7, 11, 15, m[6], m[7]);
+      g(v, 0, 5, 10, 15, m[8], m[9]); g(v, 1, 6, 11, 12, m[10], m[11]); g(v, 2, 7, 8, 13, m[12], m[13]); g(v, 3, 4, 9, 14, m[14], m[15]);
+      if (r == 6) break;
+      for (int i = 0; i < 16; ++i) t[i] = m[perm[i]];
+      std::memcpy(m, t, sizeof m);
+    }
+    for (int i = 0; i < 8; ++i) out[i] = v[i] ^ v[i + 8];
+  }
+  void update(const uint8_t* p, uint64_t n) {
+    while (n) {
+      if (blocks_ == 15 && block_len_ == 64) {  // a full chunk and more input: it was not the last one
+        uint32_t cv[8];
+        chunk_output(cv, 0);
+        push(cv);
+        ++chunk_; blocks_ = 0; block_len_ = 0;
+        std::memcpy(cv_, IV, sizeof cv_);
+      }
+      if (block_len_ == 64) {
+        uint32_t w[16];
+        words(block_, w);
+        compress(cv_, w, chunk_, 64, blocks_ == 0 ? CHUNK_START : 0, cv_);
+        ++blocks_; block_len_ = 0;
+      }
+      const uint32_t take = uint32_t(std::min<uint64_t>(64 - block_len_, n));
+      std::memcpy(block_ + block_len_, p, take);
+      block_len_ += take; p += take; n -= take;
+    }
+  }
+  // The next 2^k chunks of the input, given as the chaining value of their subtree (k = 0: a chunk's own chaining value, computed with
+  // CHUNK_START / CHUNK_END and the chunk's counter; k > 0: reduced with PARENT; never ROOT).  Only between chunks, at a chunk count that
+  // is a multiple of 2^k, and more input must follow: the last chunk of a stream is always given as bytes.
+  bool absorb_subtree(const uint8_t cv_bytes[32], unsigned k) {
+    if (blocks_ || block_len_ || k > 40 || (chunk_ & ((1ull << k) - 1))) return false;
+    uint32_t cv[8];
+    for (int i = 0; i < 8; ++i) cv[i] = load32(cv_bytes + 4 * i);
+    push(cv);
+    chunk_ += 1ull << k;
+    absorbed_last_ = true;
+    return true;
+  }
+  // false (and no output): the input ended with an absorbed subtree
+  bool finalize(uint8_t out[32]) const {
+    if (absorbed_last_ && !blocks_ && !block_len_) return false;
+    // the chunk in progress is not the right sibling of the newest entry unless the chunk count says so: complete the merges the
+    // chunks in front of it allow (never the root: the chunk in progress follows), then fold what is left from the right
+    uint32_t st[66][8], n = stack_len_;
+    std::memcpy(st, stack_, sizeof(uint32_t) * 8 * n);
+    while (n > uint32_t(__builtin_popcountll(chunk_))) {
+      uint32_t w[16];
+      std::memcpy(w, st[n - 2], 32);
+      std::memcpy(w + 8, st[n - 1], 32);
+      compress(IV, w, 0, 64, PARENT, st[n - 2]);
+      --n;
+    }
+    uint32_t cv[8];
+    chunk_output(cv, n ? 0 : ROOT);
+    for (uint32_t i = n; i-- > 0;) {
+      uint32_t w[16];
+      std::memcpy(w, st[i], 32);
+      std::memcpy(w + 8, cv, 32);
+      compress(IV, w, 0, 64, PARENT | (i == 0 ? ROOT : 0), cv);
+    }
+    for (int i = 0; i < 8; ++i) { out[4 * i] = uint8_t(cv[i]); out[4 * i + 1] = uint8_t(cv[i] >> 8); out[4 * i + 2] = uint8_t(cv[i] >> 16); out[4 * i + 3] = uint8_t(cv[i] >> 24); }
+    return true;
+  }
+
+ private:
+  static uint32_t rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
+  static uint32_t load32(const uint8_t* p) { return uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16 | uint32_t(p[3]) << 24; }
+  static void words(const uint8_t b[64], uint32_t w[16]) { for (int i = 0; i < 16; ++i) w[i] = load32(b + 4 * i); }
+  static void g(uint32_t* v, int a, int b, int c, int d, uint32_t x, uint32_t y) {
+    v[a] += v[b] + x; v[d] = rotr(v[d] ^ v[a], 16);
+    v[c] += v[d]; v[b] = rotr(v[b] ^ v[c], 12);
+    v[a] += v[b] + y; v[d] = rotr(v[d] ^ v[a], 8);
+    v[c] += v[d]; v[b] = rotr(v[b] ^ v[c], 7);
+  }
+  // the chunk in progress as a chaining value: its buffered last block zero-padded, CHUNK_END (and `extra`: ROOT for a one-chunk input)
+  void chunk_output(uint32_t out[8], uint32_t extra) const {
+    uint8_t b[64] = {0};
+    std::memcpy(b, block_, block_len_);
+    uint32_t w[16];
+    words(b, w);
+    compress(cv_, w, chunk_, block_len_, (blocks_ == 0 ? CHUNK_START : 0) | CHUNK_END | extra, out);
+  }
+  // A subtree that starts at chunk count chunk_: first merge what the chunks before it complete (the stack holds one entry per set
+  // bit of the count), then push.  The newest entry is never merged eagerly: it may yet become the right child of the root.
+  void push(const uint32_t cv[8]) {
+    while (stack_len_ > uint32_t(__builtin_popcountll(chunk_))) {
+      uint32_t w[16];
+      std::memcpy(w, stack_[stack_len_ - 2], 32);
+      std::memcpy(w + 8, stack_[stack_len_ - 1], 32);
+      compress(IV, w, 0, 64, PARENT, stack_[stack_len_ - 2]);
+      --stack_len_;
+    }
+    std::memcpy(stack_[stack_len_++], cv, 32);
+  }
+  uint32_t cv_[8];
+  uint8_t block_[64];
+  uint32_t block_len_ = 0, blocks_ = 0, stack_len_ = 0;
+  uint64_t chunk_ = 0;      // chunks (as bytes or as subtrees) in front of the one in progress
+  bool absorbed_last_ = false;
+  uint32_t stack_[66][8];
 };
 
 // rand_core 0.6.4 seed_from_u64 (PCG32 fill) -> rand_chacha 0.3.1 ChaCha20 (64-bit counter, stream 0)

@@ -107,4 +107,11 @@ int gsvk_gather_segment(void* ring, uint64_t ring_stride, const void* ct_pos, ui
 int gsvk_probe_overlap(void* word, unsigned long long ticks, hipStream_t first, hipStream_t second);
 int gsvk_copy_slots(void* W, void* VB, uint32_t n_slots, const uint32_t* src, const uint32_t* dst, uint32_t n, uint32_t n_instances, hipStream_t s);
 int gsvk_scatter_bits(void* VB, uint32_t n_slots, uint32_t first_slot, const void* bits, uint32_t n, uint32_t n_instances, hipStream_t stream);
+// BLAKE3 of the gate-order streams (blake3_device.hpp).  Chunk values of carry_in[inst] (carry_n records) || seg[inst] (strides in records):
+// chunk j < n_chunks is chunk chunk0 + j of the stream, its value goes to cv[inst][cv_off + j] (stride in 32-byte values); the tail_n
+// records behind the last chunk go to carry_out[inst] (64 records per instance, never carry_in)
+int gsvk_b3_chunks(const void* seg, uint64_t seg_stride, const void* carry_in, uint32_t carry_n, void* carry_out, uint32_t tail_n, uint64_t chunk0, uint32_t n_chunks,
+                   void* cv, uint64_t cv_stride, uint32_t cv_off, uint32_t n_instances, hipStream_t s);
+// the first (n_have >> k) << k values of cv[inst] become n_have >> k group values in red[inst] (dense), the rest moves to the front of cv_next[inst]
+int gsvk_b3_reduce(void* cv, uint64_t cv_stride, uint32_t n_have, uint32_t k, void* red, void* cv_next, uint32_t n_instances, hipStream_t s);
 }

@@ -878,6 +878,8 @@ __global__ void probe_set_kernel(uint32_t* word) { __hip_atomic_store(word, 1u, 
 }  // namespace dev
 }  // namespace gsv
 
+#include "blake3_device.hpp"  // BLAKE3 tree hash of the gate-order ciphertext streams: kernels and their launchers
+
 extern "C" {
 
 int gsvk_upload_round_keys(const uint32_t rk[44]) {

@@ -50,6 +50,7 @@
 // GSV_DRAIN_COPIES            int      3                    pass                                   copy streams of the drain
 // GSV_DRAIN_DEPTH             int      by free memory       pass                                   gate-order buffers of the drain pipeline
 // GSV_PAIR_CU_MASK            flag     1                    pass                                   CU-masked streams for garble || evaluate pairs
+// GSV_B3_SUBTREE_LOG2         0..20    10                   pass, gsv_engine_blake3_streams        BLAKE3 commitments: log2 of the chunks the device reduces to one value (anything else: the call is refused)
 #pragma once
 #include <algorithm>  // (with <initializer_list>)
 #include <cstdlib>
@@ -84,6 +85,10 @@ inline size_t plan_id_slack() {
   if (e && (end == e || *end != 0 || v < 0 || v > (1ll << 28))) gsv_panic("GSV_PLAN_ID_SLACK must be an integer in [0, 2^28]");
   return size_t(v);
 }
+inline uint32_t b3_subtree_log2() {
+  const char* e = getenv("GSV_B3_SUBTREE_LOG2"); char* end = nullptr; const long long v = e ? std::strtoll(e, &end, 10) : 10;
+  return e && (end == e || *end != 0 || v < 0 || v > 20) ? ~0u : uint32_t(v);  // ~0u = set to something else: the entry point that needs it refuses (like window_div)
+}
 struct PlanBuild {
   CompileOptions opt = compile_options(Scope::Plan);
   size_t compile_threads = knobs::compile_threads();
@@ -108,5 +113,6 @@ struct Pass {
   int drain_group = int(one_of("GSV_DRAIN_GROUP", {1, 4, 16}, 0, 0)), drain_copies = int(std::max(1ll, int_or("GSV_DRAIN_COPIES", 3)));  // group 0 = by cores / VAES
   uint64_t drain_chunk_mb = uint64_t(std::max(1ll, int_or("GSV_DRAIN_CHUNK_MB", 16)));
   size_t drain_depth = size_t(at_least_1("GSV_DRAIN_DEPTH"));  // 0 = by free memory
+  uint32_t b3_subtree_log2 = knobs::b3_subtree_log2();
 };
 }  // namespace gsv::knobs

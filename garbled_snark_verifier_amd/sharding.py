@@ -121,12 +121,19 @@ def all_gather_records(local, total, rank, world, device=None):
     return out.cpu()[torch.from_numpy(np.argsort(idx, kind="stable"))]
 
 
-def garble_and_commit(circuit, seeds, indexes, engine=None, program=None, replays=1, gc_dir=None, session_kw=None, threads=0):
+def _check_commitment(commitment):
+    if commitment not in ("cbcmac", "blake3"):
+        raise ValueError("commitment must be 'cbcmac' or 'blake3'")
+
+
+def garble_and_commit(circuit, seeds, indexes, engine=None, program=None, replays=1, gc_dir=None, session_kw=None, threads=0, commitment="cbcmac"):
     """Garbler::create + commit (garbler.rs:191-257) for the given (index, seed) pairs in ONE session: returns the
     [len(seeds), record_len] commit records; with gc_dir the ciphertext streams go to gc_<index>.bin
     (ciphertext_repository.rs:94-127).  Indexes must be consecutive when gc_dir is used.  `program` may be a Plan (the
-    verifier): the stream is then drained window by window of the session's schedule."""
+    verifier): the stream is then drained window by window of the session's schedule.  commitment="blake3": the record's 16-byte
+    ciphertext hash is the truncated BLAKE3 digest of the stream, computed on the device (Blake3Hasher truncates the same way)."""
     from . import Engine, Plan, Program, Session, labels_from_seed
+    _check_commitment(commitment)
     engine = engine or Engine(0)
     program = program or Program.from_circuit(circuit, chain_feedback=replays > 1)
     n_in = program.info["n_inputs"]
@@ -141,28 +148,33 @@ def garble_and_commit(circuit, seeds, indexes, engine=None, program=None, replay
     sess.set_garble_inputs(delta, consts, inputs)
     if gc_dir is not None:
         assert list(indexes) == list(range(indexes[0], indexes[0] + B)), "gc files are numbered first_index + i"
-    hashes = sess.garble_streaming(directory=gc_dir, first_index=int(indexes[0]) if B else 0, threads=threads)  # threads: host MAC workers (0 = the engine's default)
+    hashes = sess.garble_streaming(directory=gc_dir, first_index=int(indexes[0]) if B else 0, threads=threads, commitment=commitment)  # threads: host MAC workers (0 = the engine's default)
+    if commitment == "blake3":
+        hashes = [d[:16] for d in hashes]
     outs = sess.read_outputs()
     recs = np.stack([commit_record(indexes[i], hashes[i], outs[i], delta[i], consts[i, 0], consts[i, 1], inputs[i]) for i in range(B)])
     sess.close()
     return recs
 
 
-def cut_and_choose_commit(circuit, master_seed, total, rank, world, engine=None, program=None, garble=None, device=None, session_kw=None, threads=0):
+def cut_and_choose_commit(circuit, master_seed, total, rank, world, engine=None, program=None, garble=None, device=None, session_kw=None, threads=0, commitment="cbcmac"):
     """BASELINE config 5 / `Garbler::create` -> `commit` (garbler.rs:191-257) across ranks: `total` seeds are drawn from one master
     seed (:201-203), instance i goes to rank i mod world (the reference: one instance per pinned core, mod.rs:131-186), every rank
     garbles its instances WITH the ciphertext commitment (AESAccumulatingHash over the whole stream, :219-222) and builds their
     GarbledInstanceCommit records, and ONE all-gather leaves every rank with the [total, record_len] table ordered by instance
     index.  Nothing else is exchanged.  `garble(circuit, seeds, indexes) -> records` replaces the GPU garbler in the CPU tests.
     `threads`: host MAC workers of this rank's drain — the ranks of a node share the host's cores (bench.mac_threads_for_rank).
-    Returns (table as a uint8 numpy array, seeds)."""
+    commitment="blake3": the records carry the truncated BLAKE3 digest of the stream instead of the CBC-MAC; a `garble` stand-in is
+    then called as garble(circuit, seeds, indexes, commitment="blake3").  Returns (table as a uint8 numpy array, seeds)."""
+    _check_commitment(commitment)
     seeds = instance_seeds(master_seed, total)
     mine = shard_instances(total, rank, world)
     if garble is None:
-        garble = lambda c, sd, idx: garble_and_commit(c, sd, idx, engine=engine, program=program, session_kw=session_kw, threads=threads)  # noqa: E731
+        garble = lambda c, sd, idx, **kw: garble_and_commit(c, sd, idx, engine=engine, program=program, session_kw=session_kw, threads=threads, **kw)  # noqa: E731
     n_out, n_in = (program.info["n_outputs"], program.info["n_inputs"]) if program is not None else (None, None)
     if mine:
-        local = np.ascontiguousarray(garble(circuit, [int(seeds[i]) for i in mine], mine), np.uint8)
+        kw = {} if commitment == "cbcmac" else {"commitment": commitment}
+        local = np.ascontiguousarray(garble(circuit, [int(seeds[i]) for i in mine], mine, **kw), np.uint8)
     else:
         if n_out is None:
             raise ValueError("a rank without instances needs `program` to size its (empty) share of the gather")
@@ -171,23 +183,25 @@ def cut_and_choose_commit(circuit, master_seed, total, rank, world, engine=None,
     return table.numpy(), seeds
 
 
-def run_regarbling(commits, to_finalize, seeds, circuit, gc_dir, engine=None, program=None, replays=1):
+def run_regarbling(commits, to_finalize, seeds, circuit, gc_dir, engine=None, program=None, replays=1, commitment="cbcmac"):
     """Evaluator::run_regarbling (cut_and_choose/evaluator.rs:83-181).  `commits`: [total, record_len] table of the
     garbler's commit records; `to_finalize`: indexes kept for evaluation; `seeds`: {index: seed} of the OPENED instances.
       * finalized index: its gc_<index>.bin is streamed through the CBC-MAC and compared with the committed ciphertext
         hash ("ciphertext corrupted" otherwise);
       * opened index: the circuit is garbled again from the revealed seed — all opened instances in one GPU launch —
         and the whole commit record must match ("regarbling failed"); a missing seed is an error ("failed to find seed").
-    Returns (ok, errors) with errors = {index: message}; the reference returns Err(()) as soon as any instance fails."""
+    commitment="blake3": the committed hash is the truncated BLAKE3 digest — the file is hashed with blake3_file, the re-garbling
+    commits the same way.  Returns (ok, errors) with errors = {index: message}; the reference returns Err(()) as soon as any instance fails."""
     import os
-    from . import gc_file_name, read_gc_file
+    from . import blake3_file, gc_file_name, read_gc_file
+    _check_commitment(commitment)
     commits = np.asarray(commits, np.uint8)
     errors = {}
     fin = set(int(i) for i in to_finalize)
     for index in sorted(fin):
         path = os.path.join(gc_dir, gc_file_name(index))
         try:
-            _, h = read_gc_file(path)
+            h = blake3_file(path)[:16] if commitment == "blake3" else read_gc_file(path)[1]
         except Exception as e:  # FileSource::from_path failing (ciphertext_source.rs:36-60)
             errors[index] = "failed to get ciphertext source: %s" % e
             continue
@@ -199,7 +213,7 @@ def run_regarbling(commits, to_finalize, seeds, circuit, gc_dir, engine=None, pr
         errors[i] = "failed to find seed"
     todo = [i for i in opened if i in seeds]
     if todo:
-        recs = garble_and_commit(circuit, [seeds[i] for i in todo], todo, engine=engine, program=program, replays=replays)
+        recs = garble_and_commit(circuit, [seeds[i] for i in todo], todo, engine=engine, program=program, replays=replays, commitment=commitment)
         for k, i in enumerate(todo):
             if not (recs[k] == commits[i]).all():
                 errors[i] = "regarbling failed"

@@ -444,6 +444,42 @@ int gsv_cbcmac_chains_per_step(void);
 /* AesLabelCommitHasher: AES_K(label) for n labels (cut_and_choose/mod.rs:41-48). */
 int gsv_commit_labels(const uint8_t* labels, uint64_t n, uint8_t* out);
 
+/* ---- BLAKE3 commitments ---------------------------------------------------------------------------------------------------------
+ * A second, opt-in ciphertext commitment beside the CBC-MAC (ciphertext_hasher.rs:3: "It can be any"): commit_i = BLAKE3(stream_i),
+ * plain hash mode (no key, no derive-key context, 32 bytes), stream_i = the instance's ciphertexts in gate order as gc_<i>.bin holds
+ * them; an empty stream commits to BLAKE3 of the empty string; where 16 bytes are wanted (CiphertextCommit) they are the first 16.
+ * BLAKE3 is a tree hash, so unlike the serial CBC-MAC chain it is computed where the ciphertexts are: the device hashes every 1 KiB
+ * chunk but a stream's last and reduces aligned groups of 2^k chunks (GSV_B3_SUBTREE_LOG2, default 10: 1 MiB) to one 32-byte value
+ * each; only those values and the last chunk cross the link, the host folds them.  Any BLAKE3 implementation verifies the digest.
+ *
+ * gsv_session_garble_streaming_commit: gsv_session_garble_streaming[_calls] with either commitment or both.  first_call = n_calls = 0
+ * is the whole pass (the only form program sessions accept); other ranges are slices as for gsv_session_garble_streaming_calls, the
+ * BLAKE3 state chains from slice to slice like the MAC states and restarts with a slice that starts at call 0.  cbcmac_hashes
+ * (n x 16, or NULL) receives the MAC states after this call; blake3_digests (n x 32, or NULL) is written when the call ends the pass
+ * and left untouched otherwise; every slice of such a pass must ask for the same commitments as its first (GSV_ERR_INVALID otherwise:
+ * a slice without one of them would leave that state behind).  n = the drained instances (gsv_session_set_drain_instances).  dir needs neither.  With
+ * blake3_digests alone nothing of the stream is copied to the host and no MAC workers run. */
+int gsv_session_garble_streaming_commit(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* dir, uint64_t first_index, int n_threads,
+                                        uint8_t* cbcmac_hashes, uint8_t* blake3_digests);
+/* The host hasher: incremental, portable.  gsv_blake3_absorb_subtree takes the next 2^log2_chunks chunks of the input as the chaining
+ * value of their subtree (log2_chunks = 0: a chunk's own chaining value): only between chunks, at a chunk count that is a multiple of
+ * 2^log2_chunks, and never as the end of the input — the last chunk is always given as bytes. */
+typedef struct gsv_blake3 gsv_blake3;
+int gsv_blake3_create(gsv_blake3** out);
+void gsv_blake3_destroy(gsv_blake3* h);
+int gsv_blake3_update(gsv_blake3* h, const uint8_t* data, uint64_t n_bytes);
+int gsv_blake3_absorb_subtree(gsv_blake3* h, const uint8_t* chaining_value, uint32_t log2_chunks);
+int gsv_blake3_finalize(const gsv_blake3* h, uint8_t* out /* 32 */);
+int gsv_blake3_file(const char* path, uint8_t* out /* 32 */);
+/* The device kernels alone: n_streams streams of records_per_stream 16-byte records each (data: [stream][record]) are uploaded and
+ * fed, in the given segmentation (segment_records adds up to records_per_stream), to the same chunk, reduce and carry code as the
+ * drain; the host finishes them.  digests: n_streams x 32. */
+int gsv_engine_blake3_streams(gsv_engine* e, const uint8_t* data, uint64_t n_streams, uint64_t records_per_stream, const uint64_t* segment_records, uint64_t n_segments,
+                              uint8_t* digests /* n_streams x 32 */);
+/* Device time of the engine's last gsv_engine_blake3_streams from the first hash kernel to the last (HIP events on the engine's stream:
+ * the upload in front and the host's finish behind are outside; with several segments the host's folding between them is inside). */
+int gsv_engine_blake3_streams_seconds(const gsv_engine* e, double* seconds);
+
 #ifdef __cplusplus
 }
 #endif

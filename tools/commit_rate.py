@@ -1,0 +1,229 @@
+#!/usr/bin/env python3
+"""What a commitment costs: whole verifier passes with the ciphertexts discarded, drained into the host's CBC-MACs, and hashed on the
+device with BLAKE3 (DESIGN.md §3 "Commitment stage", §6), and the stand-alone rate of the BLAKE3 kernels.
+
+    python tools/commit_rate.py [--instances 64,1024] [--rounds 2] [--kernel-gib 1] [--out profiles/commit_blake3]
+
+The driver touches no GPU.  Every GPU step is a child process of this file under its own `timeout`:
+  kernel   gsv.blake3_streams on 16 streams of --kernel-gib GiB each, one segment: device seconds from the first hash kernel to the last
+           (gsv_engine_blake3_streams_seconds), one digest compared with the host hasher's;
+  check    the 16 instances of tests/golden/cc16_verifier_golden.json with commitment="both": every CBC-MAC equals the oracle's fixture in
+           the very pass that produced the BLAKE3 digests, which the rounds below must reproduce for their first 16 instances;
+  file     ONE instance (the fixture's first seed) in a pass of its own with commitment="blake3" and its stream written to gc_0.bin: the
+           device's digest equals gsv.blake3_file of that file (47.7 GB through the host hasher) and the digest of the check pass;
+  round    one batch size, warm (a discarded pass first), then the three legs in turn: discard, CBC-MAC drain, device BLAKE3 — `--rounds`
+           children per batch size, so the legs alternate; GSV_DRAIN_STATS lines of the draining legs go to the log.
+A child that fails, is killed at its time limit or dies ends the run: nothing more is started on the GPU.  At most 16 host threads
+(--threads) serve a drain.  Results: <out>/commit_rate.json and <out>/commit_rate.log.  Batches run in ascending order; one whose CBC-MAC
+leg — the plan's ciphertext bytes at the link rate the previous batch's CBC-MAC leg measured — cannot end within --leg-seconds is not
+started and the JSON says so.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _child_setup():
+    import threading
+    t0 = time.time()
+
+    def alive():  # a CBC-MAC leg of a large batch is minutes of silence: a line a minute shows the child is running
+        while True:
+            time.sleep(60)
+            print("commit_rate: running, %.0f s" % (time.time() - t0), file=sys.stderr, flush=True)
+    threading.Thread(target=alive, daemon=True).start()
+    import numpy as np
+    import bench_support as bs
+    import garbled_snark_verifier_amd as gsv
+    return np, bs, gsv, gsv.Engine(0)
+
+
+def _load_plan(bs, gsv, eng, log):
+    case = json.load(open(os.path.join(ROOT, "tests", "golden", bs.FIXTURE["verifier_compressed"])))
+    args = argparse.Namespace(no_plan_cache=False, plan_cache=None)
+    plan, info, _ = bs.get_plan(gsv, eng, args, case["circuit"], bs.VERIFIER_UNITS + ["fp254::exp_chunk"], 0, 0, 1, bs.Dist(1, None, None), log)
+    log("plan %s in %.1f s" % (info.get("how"), info["seconds"]))
+    return case, plan
+
+
+def child_kernel(a):
+    np, bs, gsv, eng = _child_setup()
+    records = (a.kernel_gib << 30) // 16
+    data = np.empty((16, records, 16), np.uint8)
+    block = np.random.default_rng(1).integers(0, 256, (1 << 20, 16), dtype=np.uint8)
+    for s in range(16):
+        for off in range(0, records, 1 << 20):
+            n = min(1 << 20, records - off)
+            data[s, off:off + n] = block[:n] ^ np.uint8(s + 1)
+    secs, digests = [], None
+    for _ in range(11):
+        digests, sec = gsv.blake3_streams(eng, data, [records], with_seconds=True)
+        secs.append(sec)
+    secs = sorted(secs[1:])  # (the first call also allocates)
+    med = secs[len(secs) // 2]
+    ok = digests[5] == gsv.blake3(data[5])
+    print(json.dumps({"step": "kernel", "streams": 16, "gib_per_stream": a.kernel_gib, "calls": len(secs), "device_seconds_median": med, "device_seconds_min": secs[0], "device_seconds_max": secs[-1],
+                      "bytes_per_s": data.size / med, "ciphertexts_per_s": data.size / 16 / med, "digest_matches_host_hasher": ok, "read_pattern": "one lane per chunk"}), flush=True)
+    return 0 if ok else 1
+
+
+def _work(np, bs, gsv, eng, plan, B, gold):
+    seeds = [int(s) for s in gold["seeds"][:min(B, 16)]] + bs.instance_seeds(0, B)[:max(0, B - 16)]
+    return bs.VerifierWork(gsv, eng, plan, B, seeds)
+
+
+def child_check(a):
+    np, bs, gsv, eng = _child_setup()
+    log = lambda m: print("commit_rate: " + m, file=sys.stderr, flush=True)  # noqa: E731
+    case, plan = _load_plan(bs, gsv, eng, log)
+    gold = bs.cc16_verifier_fixture(case)
+    w = _work(np, bs, gsv, eng, plan, 16, gold)
+    w.new_pass()
+    t0 = time.perf_counter()
+    macs, digests = w.sess.garble_streaming(threads=a.threads, commitment="both")
+    dt = time.perf_counter() - t0
+    ok = [macs[i].hex() == gold["ct_hashes"][i] for i in range(16)]
+    w.close()
+    print(json.dumps({"step": "check", "instances": 16, "seconds": dt, "ciphertexts_per_instance": plan.info["n_ciphertexts"], "cbcmacs_equal_to_the_oracle_fixture": sum(ok), "blake3_digests": [d.hex() for d in digests]}), flush=True)
+    return 0 if all(ok) else 1
+
+
+def child_file(a):
+    import shutil
+    import tempfile
+    np, bs, gsv, eng = _child_setup()
+    log = lambda m: print("commit_rate: " + m, file=sys.stderr, flush=True)  # noqa: E731
+    case, plan = _load_plan(bs, gsv, eng, log)
+    gold = bs.cc16_verifier_fixture(case)
+    need = plan.info["n_ciphertexts"] * 16
+    roots = [d for d in ("/dev/shm", tempfile.gettempdir()) if os.path.isdir(d) and os.statvfs(d).f_bavail * os.statvfs(d).f_frsize > 1.25 * need]
+    if not roots:
+        print(json.dumps({"step": "file", "skipped": "no directory with room for a %.1f GB gc file" % (need / 1e9)}), flush=True)
+        return 0
+    d = tempfile.mkdtemp(prefix="gsv_commit_rate_", dir=roots[0])
+    try:
+        w = _work(np, bs, gsv, eng, plan, 1, gold)
+        w.new_pass()
+        t0 = time.perf_counter()
+        digest = w.sess.garble_streaming(directory=d, threads=a.threads, commitment="blake3")[0]
+        t1 = time.perf_counter()
+        w.close()
+        path = os.path.join(d, gsv.gc_file_name(0))
+        size = os.path.getsize(path)
+        file_digest = gsv.blake3_file(path)
+        t2 = time.perf_counter()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    ok = digest == file_digest and size == need
+    print(json.dumps({"step": "file", "instances": 1, "file_bytes": size, "pass_seconds": t1 - t0, "host_hash_seconds": t2 - t1, "host_hash_bytes_per_s": size / (t2 - t1),
+                      "device_digest": digest.hex(), "blake3_file_digest": file_digest.hex(), "equal": ok}), flush=True)
+    return 0 if ok else 1
+
+
+def child_round(a):
+    np, bs, gsv, eng = _child_setup()
+    log = lambda m: print("commit_rate: " + m, file=sys.stderr, flush=True)  # noqa: E731
+    case, plan = _load_plan(bs, gsv, eng, log)
+    gold = bs.cc16_verifier_fixture(case)
+    B, gates, n_ct = a.batch, plan.info["n_gates"], plan.info["n_ciphertexts"]
+    w = _work(np, bs, gsv, eng, plan, B, gold)
+    si = w.sess.schedule_info()
+    out = {"step": "round", "instances": B, "gates_per_instance": gates, "ciphertexts_per_instance": n_ct, "windows": si["n_windows"], "segments": si["n_segments"],
+           "segment_ct_records": si["segment_ct_records"], "instances_per_workgroup": w.sess.instances_per_workgroup, "legs": {}}
+    w.run_pass()  # warm: first launches, allocations
+    os.environ["GSV_DRAIN_STATS"] = "1"  # (read per pass: where the drain's host thread waited goes to the log, one line per draining leg)
+    for leg in ("discard", "cbcmac", "blake3"):
+        w.new_pass()
+        t0 = time.perf_counter()
+        if leg == "discard":
+            w.sess.garble_streaming(discard=True)
+        elif leg == "cbcmac":
+            macs = w.sess.garble_streaming(threads=a.threads)
+        else:
+            digests = w.sess.garble_streaming(threads=a.threads, commitment="blake3")
+        dt = time.perf_counter() - t0
+        out["legs"][leg] = {"seconds": dt, "gates_per_s": gates * B / dt, "ciphertexts_per_s": n_ct * B / dt}
+        log("%d instances, %s: %.2f s, %.3e gates/s" % (B, leg, dt, gates * B / dt))
+    out["cbcmacs_equal_to_the_oracle_fixture"] = sum(macs[i].hex() == gold["ct_hashes"][i] for i in range(min(B, 16)))
+    out["blake3_digests_first16"] = [d.hex() for d in digests[:16]]
+    out["distinct_blake3_digests"] = len(set(digests))
+    w.close()
+    print(json.dumps(out), flush=True)
+    return 0 if out["cbcmacs_equal_to_the_oracle_fixture"] == min(B, 16) else 1
+
+
+def driver(a):
+    os.makedirs(a.out, exist_ok=True)
+    log_f = open(os.path.join(a.out, "commit_rate.log"), "w")
+    results, stopped = [], None
+
+    def step(name, seconds, extra):
+        nonlocal stopped
+        if stopped:
+            return None
+        cmd = ["timeout", "-k", "10", str(seconds), sys.executable, os.path.relpath(os.path.abspath(__file__), ROOT), "--child", name, "--threads", str(a.threads), "--kernel-gib", str(a.kernel_gib)] + extra
+        log_f.write("$ " + " ".join(["python"] + cmd[5:]) + "\n"); log_f.flush()
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=log_f, text=True, cwd=ROOT)
+        log_f.write(p.stdout); log_f.flush()
+        rows = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]
+        if p.returncode != 0:
+            stopped = "%s %s ended with status %d: nothing more was started" % (name, " ".join(extra), p.returncode)
+        results.extend(rows)
+        save()
+        return rows[0] if rows else None
+
+    def save():
+        summary = {}
+        for r in results:
+            if r.get("step") == "round" and "legs" in r:
+                s = summary.setdefault(str(r["instances"]), {k: [] for k in r["legs"]})
+                for k, v in r["legs"].items():
+                    s[k].append(v["gates_per_s"])
+        json.dump({"results": results, "gates_per_s_by_instances": summary, "stopped": stopped}, open(os.path.join(a.out, "commit_rate.json"), "w"), indent=1)
+        return summary
+
+    step("kernel", 300, [])
+    check = step("check", a.leg_seconds, [])
+    if not a.no_file_check:
+        f = step("file", a.leg_seconds, [])
+        if f and check and "device_digest" in f and f["device_digest"] != check["blake3_digests"][0]:
+            stopped = stopped or "the digest of the file pass differs from the checked pass"
+    link_bytes_per_s = None  # what the last CBC-MAC leg moved: a larger batch cannot be faster than that
+    for B in sorted(a.instances):
+        if link_bytes_per_s and check:
+            need_s = B * check["ciphertexts_per_instance"] * 16 / link_bytes_per_s
+            if need_s > 0.8 * a.leg_seconds:
+                results.append({"step": "round", "instances": B, "skipped": "its CBC-MAC leg alone needs %.0f s (%d ciphertexts per instance at the %.1f GB/s the previous batch's CBC-MAC leg moved): beyond --leg-seconds %d"
+                                % (need_s, check["ciphertexts_per_instance"], link_bytes_per_s / 1e9, a.leg_seconds)})
+                continue
+        for _ in range(a.rounds):
+            r = step("round", a.leg_seconds, ["--batch", str(B)])
+            if r and "legs" in r:
+                link_bytes_per_s = r["legs"]["cbcmac"]["ciphertexts_per_s"] * 16
+            if r and check and r["blake3_digests_first16"] != check["blake3_digests"][:len(r["blake3_digests_first16"])]:
+                stopped = stopped or "the BLAKE3 digests of a round differ from the checked pass"
+    summary = save()
+    print(json.dumps({"gates_per_s_by_instances": summary, "kernel": next((r for r in results if r.get("step") == "kernel"), None), "stopped": stopped}))
+    return 1 if stopped else 0
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--instances", type=lambda s: [int(x) for x in s.split(",")], default=[64, 1024])
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--kernel-gib", type=int, default=1)
+    ap.add_argument("--leg-seconds", type=int, default=1500)  # a 1 024-instance round: ~900 s of CBC-MAC leg alone
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "commit_blake3"))
+    ap.add_argument("--no-file-check", action="store_true")
+    ap.add_argument("--child", choices=["kernel", "check", "round", "file"])
+    ap.add_argument("--batch", type=int, default=64)
+    a = ap.parse_args()
+    a.threads = max(1, min(16, a.threads))
+    sys.exit({"kernel": child_kernel, "check": child_check, "round": child_round, "file": child_file, None: driver}[a.child](a))
