@@ -61,6 +61,44 @@ int hostsim_compile(const char* spec, int chain_feedback, SimProgram** out, uint
     return 0;
   } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }
+// An explicit gate list, numbered as Program.from_gates wants it — wires 0 / 1 the constants, the inputs 2 .. 2 + n_inputs - 1, every
+// other wire written once, in first-write order (so a wire's number IS its SSA id in the recorder's trace); c == DEAD_WIRE: a dead gate —
+// compiled the way gsv_program_compile_opts compiles a recording: the program-scope knobs, and for window_div 2 | 4 ONE image for
+// half / a quarter of the LDS window.  fb_src / fb_dst: feedback pairs (output index -> input index) of chained replays.
+int hostsim_compile_gates(uint32_t n_inputs, uint64_t n_gates, const uint8_t* type, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+                          const uint32_t* outputs, uint32_t n_outputs, uint32_t window_div, const uint32_t* fb_src, const uint32_t* fb_dst, uint32_t n_fb,
+                          SimProgram** out, uint64_t* info /* 18 */) {
+  try {
+    if (window_div != 0 && window_div != 1 && window_div != 2 && window_div != 4) gsv_panic("window_div must be 0, 1, 2 or 4");
+    Trace t;
+    t.n_wires = 2 + n_inputs;
+    for (uint64_t i = 0; i < n_gates; ++i) {
+      if (type[i] >= GATE_TYPE_COUNT || a[i] >= t.n_wires || b[i] >= t.n_wires) gsv_panic("gate " + std::to_string(i) + ": unknown gate type or operand not yet written");
+      if (c[i] != DEAD_WIRE && c[i] != t.n_wires) gsv_panic("gate " + std::to_string(i) + ": wires must be numbered in first-write order");
+      t.type.push_back(type[i]); t.a.push_back(a[i]); t.b.push_back(b[i]); t.c.push_back(c[i]);
+      if (c[i] != DEAD_WIRE) ++t.n_wires;
+    }
+    std::vector<uint32_t> in_ssa, out_ssa(outputs, outputs + n_outputs);
+    for (uint32_t i = 0; i < n_inputs; ++i) in_ssa.push_back(2 + i);
+    for (uint32_t w : out_ssa) if (w >= t.n_wires) gsv_panic("output wire was never written");
+    std::vector<std::pair<uint32_t, uint32_t>> fb;
+    for (uint32_t i = 0; i < n_fb; ++i) fb.push_back({fb_src[i], fb_dst[i]});
+    CompileOptions opt = knobs::compile_options(knobs::Scope::Program);
+    if (window_div > 1) opt.lds_slots = std::min<uint32_t>(opt.lds_slots, LDS_WINDOW_SLOTS / window_div);
+    auto sp = std::make_unique<SimProgram>();
+    sp->prog = compile_program(t, in_ssa, out_ssa, fb, opt);
+    const Program& g = sp->prog;
+    if (info) {
+      info[0] = g.input_slots.size(); info[1] = g.output_slots.size(); info[2] = g.n_gates; info[3] = g.n_ct; info[4] = g.n_dead;
+      info[5] = g.steps.size(); info[6] = g.and_depth; info[7] = g.n_and_steps; info[8] = g.max_step_width; info[9] = g.n_slots;
+      info[10] = g.peak_live; info[11] = 0;
+      info[12] = g.n_lds_slots; info[13] = g.reads_lds; info[14] = g.reads_hbm; info[15] = g.writes_lds; info[16] = g.writes_hbm;
+      info[17] = g.n_fused_free;
+    }
+    *out = sp.release();
+    return 0;
+  } catch (const std::exception& e) { g_err = e.what(); return 1; }
+}
 void hostsim_free(SimProgram* p) { delete p; }
 
 // One pass of one compiled program over a wire file (W labels / VB plaintext bits, at least g.n_slots entries; slots 0/1/2
@@ -68,11 +106,21 @@ void hostsim_free(SimProgram* p) { delete p; }
 static void interpret(const Program& g, bool evaluate, uint64_t gb, const Label& d, std::vector<uint8_t>& W, std::vector<uint8_t>& VB, uint8_t* ct) {
   const AesTables& T = AesTables::fixed_key();
   dev::PlainTables aes{{T.te[0], T.te[1], T.te[2], T.te[3]}, T.rk};
-  std::vector<uint8_t> LW(size_t(LDS_WINDOW_SLOTS) * 16, 0x5A), LB(LDS_WINDOW_SLOTS, 0);  // LDS window image
-  std::memset(&LW[0], 0, 16);  // window entry 0: the all-zero label of absent operands
-  LB[0] = 0;
-  auto lab = [&](uint32_t slot) -> uint8_t* { return (slot & SLOT_LDS_FLAG) ? &LW[size_t(slot & SLOT_INDEX_MASK) * 16] : &W[size_t(slot) * 16]; };
-  auto bit = [&](uint32_t slot) -> uint8_t& { return (slot & SLOT_LDS_FLAG) ? LB[slot & SLOT_INDEX_MASK] : VB[slot]; };
+  // LDS window image of ONE instance: the share the program was compiled for (g.lds_slots_limit), not the whole window.  On the device
+  // entry `limit` of an instance is entry 0 of its neighbour in the workgroup (kernels.hip, win_base / bit_base): a record that names
+  // it is refused here, by name, where the device would quietly corrupt another instance.
+  const uint32_t win = g.lds_slots_limit;
+  std::vector<uint8_t> LW(size_t(win) * 16, 0x5A), LB(win, 0);
+  if (win) std::memset(&LW[0], 0, 16);  // window entry 0: the all-zero label (and bit) of absent operands
+  auto entry = [&](uint32_t slot) -> uint32_t {
+    const uint32_t i = slot & SLOT_INDEX_MASK;
+    if (i >= win)
+      gsv_panic(win ? "a record names LDS window slot " + std::to_string(i) + " of a program compiled for a window of " + std::to_string(win) + " slots"
+                    : "a record names LDS window slot " + std::to_string(i) + " of a program compiled without an LDS window (lds_slots == 0)");
+    return i;
+  };
+  auto lab = [&](uint32_t slot) -> uint8_t* { return (slot & SLOT_LDS_FLAG) ? &LW[size_t(entry(slot)) * 16] : &W[size_t(slot) * 16]; };
+  auto bit = [&](uint32_t slot) -> uint8_t& { return (slot & SLOT_LDS_FLAG) ? LB[entry(slot)] : VB[slot]; };
   // the records carry PROGRAM-order ciphertext positions; `ct` is in gate order
   std::vector<uint32_t> gate_of(g.ct_pos.size());
   for (size_t k = 0; k < g.ct_pos.size(); ++k) gate_of[g.ct_pos[k]] = uint32_t(k);

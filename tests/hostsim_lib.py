@@ -20,6 +20,8 @@ def lib():
         L.hostsim_last_error.restype = C.c_char_p
         u8p = C.POINTER(C.c_uint8)
         L.hostsim_compile.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        u32p = C.POINTER(C.c_uint32)
+        L.hostsim_compile_gates.argtypes = [C.c_uint32, C.c_uint64, u8p, u32p, u32p, u32p, u32p, C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.hostsim_free.argtypes = [C.c_void_p]
         L.hostsim_run.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, u8p, u8p, u8p, u8p, u8p, u8p, u8p]
         L.hostsim_plan_build.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -49,6 +51,27 @@ class SimProgram:
             raise RuntimeError(lib().hostsim_last_error().decode())
         self.h = h
         self.info = dict(zip(INFO_FIELDS, (int(x) for x in info)))
+
+    @classmethod
+    def from_gates(cls, n_inputs, gates, outputs, window_div=None, feedback=None):
+        """An explicit gate list as garbled_snark_verifier_amd.Program.from_gates takes it ((type, a, b, c-or-None); inputs 2 .. 2 + n_inputs - 1,
+        further wires in first-write order), compiled the same way: the program-scope knobs of the environment, window_div = 2 | 4 for
+        ONE image for half / a quarter of the LDS window, feedback = [(output index, input index)]."""
+        u32p = C.POINTER(C.c_uint32)
+        t = np.array([g[0] for g in gates], np.uint8)
+        a, b = np.array([g[1] for g in gates], np.uint32), np.array([g[2] for g in gates], np.uint32)
+        c = np.array([0xFFFFFFFF if g[3] is None else g[3] for g in gates], np.uint32)
+        outs = np.array(outputs, np.uint32)
+        fb_src, fb_dst = np.array([x for x, _ in feedback or []], np.uint32), np.array([y for _, y in feedback or []], np.uint32)
+        h = C.c_void_p()
+        info = np.zeros(len(INFO_FIELDS), np.uint64)
+        if lib().hostsim_compile_gates(n_inputs, len(gates), _p(t), a.ctypes.data_as(u32p), b.ctypes.data_as(u32p), c.ctypes.data_as(u32p), outs.ctypes.data_as(u32p), len(outs),
+                                       int(window_div or 0), fb_src.ctypes.data_as(u32p), fb_dst.ctypes.data_as(u32p), len(fb_src), C.byref(h), info.ctypes.data_as(C.POINTER(C.c_uint64))):
+            raise RuntimeError(lib().hostsim_last_error().decode())
+        self = cls.__new__(cls)
+        self.h = h
+        self.info = dict(zip(INFO_FIELDS, (int(x) for x in info)))
+        return self
 
     def __del__(self):
         if getattr(self, "h", None):
