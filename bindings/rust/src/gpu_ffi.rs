@@ -145,6 +145,9 @@ extern "C" {
     pub fn gsv_plan_call_record_form(p: *const GsvPlan, call: u64, and_terms: *mut u32) -> c_int;
     // BLAKE3 commitments: computed on the device beside (or instead of) the CBC-MAC; `blake3::Hasher` verifies the digests
     pub fn gsv_session_garble_streaming_commit(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, dir: *const c_char, first_index: u64, n_threads: c_int, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int;
+    pub fn gsv_session_evaluate_streaming_commit(s: *mut GsvSession, gate_id_base: u64, dir: *const c_char, indexes: *const u64, first_index: u64, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int;
+    pub fn gsv_session_evaluate_streaming_source_commit(s: *mut GsvSession, gate_id_base: u64, source: GsvCtSourceFn, user: *mut std::ffi::c_void, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int;
+    pub fn gsv_session_ciphertext_blake3(s: *mut GsvSession, digests: *mut u8) -> c_int;
     pub fn gsv_blake3_file(path: *const c_char, out: *mut u8) -> c_int;
     pub fn gsv_engine_blake3_streams(e: *mut GsvEngine, data: *const u8, n_streams: u64, records_per_stream: u64, segment_records: *const u64, n_segments: u64, digests: *mut u8) -> c_int;
 }

@@ -125,6 +125,7 @@ EXPORTS = [
     "gsv_recorder_allocate_wires", "gsv_plan_recorder_allocate_wires", "gsv_program_compile_opts", "gsv_program_wait", "gsv_plan_recorder_create_opts", "gsv_session_set_drain_instances",
     "gsv_session_garble_streaming_commit", "gsv_blake3_create", "gsv_blake3_destroy", "gsv_blake3_update", "gsv_blake3_absorb_subtree", "gsv_blake3_finalize", "gsv_blake3_file",
     "gsv_engine_blake3_streams", "gsv_engine_blake3_streams_seconds",
+    "gsv_session_evaluate_streaming_commit", "gsv_session_evaluate_streaming_source_commit", "gsv_session_ciphertext_blake3",
 ]
 
 # CiphertextHandler / CiphertextSource as host callbacks (include/gsv_engine.h: gsv_ct_sink_fn, gsv_ct_source_fn)
@@ -233,6 +234,9 @@ def lib():
         L.gsv_blake3_file.argtypes = [C.c_char_p, u8p]
         L.gsv_engine_blake3_streams.argtypes = [vp, u8p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64, u8p]
         L.gsv_engine_blake3_streams_seconds.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gsv_session_evaluate_streaming_commit.argtypes = [vp, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, u8p, u8p]
+        L.gsv_session_evaluate_streaming_source_commit.argtypes = [vp, C.c_uint64, CT_SOURCE_FN, vp, u8p, u8p]
+        L.gsv_session_ciphertext_blake3.argtypes = [vp, u8p]
         _lib = L
     return _lib
 
@@ -787,18 +791,38 @@ class Session:
             _chk(lib().gsv_session_garble_evaluate(self.h, evaluator.h, gate_id_base, threads, _p(out)))
         return [bytes(out[i]) for i in range(self.n)] if with_hashes else None
 
-    def evaluate_streaming_indexed(self, directory, indexes, gate_id_base=0):
-        """Evaluate with instance i reading gc_<indexes[i]>.bin: the finalized instances of a cut-and-choose run in one session."""
+    def _evaluate_commit(self, commitment, call):
+        """The streaming evaluators' commitments: `call(macs, digests)` runs the C entry point with the arrays this commitment asks for
+        (None for the other); returns the MACs, the 32-byte BLAKE3 digests (computed on the device), or (MACs, digests) for "both"."""
+        macs = np.zeros((self.n, 16), np.uint8) if commitment != "blake3" else None
+        dig = np.zeros((self.n, 32), np.uint8) if commitment != "cbcmac" else None
+        call(macs, dig)
+        m = [bytes(macs[i]) for i in range(self.n)] if macs is not None else None
+        d = [bytes(dig[i]) for i in range(self.n)] if dig is not None else None
+        return (m, d) if commitment == "both" else m if d is None else d
+
+    def evaluate_streaming_indexed(self, directory, indexes, gate_id_base=0, commitment="cbcmac"):
+        """Evaluate with instance i reading gc_<indexes[i]>.bin: the finalized instances of a cut-and-choose run in one session.
+        commitment as for evaluate_streaming."""
+        _check_commitment(commitment, False)
         idx = np.ascontiguousarray(indexes, np.uint64)
         assert idx.size == self.n
-        out = np.zeros((self.n, 16), np.uint8)
-        with _gc_paused():
-            _chk(lib().gsv_session_evaluate_streaming_indexed(self.h, gate_id_base, directory.encode(), idx.ctypes.data_as(C.POINTER(C.c_uint64)), _p(out)))
-        return [bytes(out[i]) for i in range(self.n)]
+        idx_p = idx.ctypes.data_as(C.POINTER(C.c_uint64))
 
-    def evaluate_from_source(self, source, gate_id_base=0):
+        def call(macs, dig):
+            with _gc_paused():
+                if dig is None:
+                    _chk(lib().gsv_session_evaluate_streaming_indexed(self.h, gate_id_base, directory.encode(), idx_p, _p(macs)))
+                else:
+                    _chk(lib().gsv_session_evaluate_streaming_commit(self.h, gate_id_base, directory.encode(), idx_p, 0, _p(macs), _p(dig)))
+
+        return self._evaluate_commit(commitment, call)
+
+    def evaluate_from_source(self, source, gate_id_base=0, commitment="cbcmac"):
         """Evaluate with the ciphertexts pulled from `source(instance, first_record, n) -> [n,16] uint8` (None / short = exhausted):
-        the generic CiphertextSource (ciphertext_source.rs:14-34).  Returns the CBC-MACs of what was read."""
+        the generic CiphertextSource (ciphertext_source.rs:14-34).  Returns the CBC-MACs of what was read; commitment as for
+        evaluate_streaming."""
+        _check_commitment(commitment, False)
         failure = []
 
         def _cb(_user, inst, first, ptr, n):
@@ -816,13 +840,18 @@ class Session:
                 return 2
 
         cb = CT_SOURCE_FN(_cb)
-        out = np.zeros((self.n, 16), np.uint8)
-        with _gc_paused():
-            rc = lib().gsv_session_evaluate_streaming_source(self.h, gate_id_base, cb, None, _p(out))
-        if failure:
-            raise failure[0]
-        _chk(rc)
-        return [bytes(out[i]) for i in range(self.n)]
+
+        def call(macs, dig):
+            with _gc_paused():
+                if dig is None:
+                    rc = lib().gsv_session_evaluate_streaming_source(self.h, gate_id_base, cb, None, _p(macs))
+                else:
+                    rc = lib().gsv_session_evaluate_streaming_source_commit(self.h, gate_id_base, cb, None, _p(macs), _p(dig))
+            if failure:
+                raise failure[0]
+            _chk(rc)
+
+        return self._evaluate_commit(commitment, call)
 
     def schedule_info(self):
         """Plan sessions: the call-level schedule this session executes (windows, batches of calls side by side, wire-file layout,
@@ -856,12 +885,20 @@ class Session:
         """Timing harnesses only: allow garble_calls slices that do not continue the previous one (stale wires, meaningless MACs)."""
         _chk(lib().gsv_session_set_unchecked_slices(self.h, int(bool(on))))
 
-    def evaluate_streaming(self, directory, first_index=0, gate_id_base=0):
-        """Evaluate with the ciphertexts read from gc_<first_index+i>.bin segment by segment; returns the files' CBC-MACs."""
-        out = np.zeros((self.n, 16), np.uint8)
-        with _gc_paused():
-            _chk(lib().gsv_session_evaluate_streaming(self.h, gate_id_base, directory.encode(), first_index, _p(out)))
-        return [bytes(out[i]) for i in range(self.n)]
+    def evaluate_streaming(self, directory, first_index=0, gate_id_base=0, commitment="cbcmac"):
+        """Evaluate with the ciphertexts read from gc_<first_index+i>.bin segment by segment; returns the files' CBC-MACs.
+        commitment="blake3": the files' 32-byte BLAKE3 digests instead, computed on the device from the uploaded segments (no MAC
+        worker runs); "both": (CBC-MACs, BLAKE3 digests).  Comparing them with the garbler's commitments is the caller's part."""
+        _check_commitment(commitment, False)
+
+        def call(macs, dig):
+            with _gc_paused():
+                if dig is None:
+                    _chk(lib().gsv_session_evaluate_streaming(self.h, gate_id_base, directory.encode(), first_index, _p(macs)))
+                else:
+                    _chk(lib().gsv_session_evaluate_streaming_commit(self.h, gate_id_base, directory.encode(), None, first_index, _p(macs), _p(dig)))
+
+        return self._evaluate_commit(commitment, call)
 
     def set_evaluate_inputs(self, const_active, input_active, input_bits):
         c = _u8(const_active, (self.n, 32))
@@ -920,6 +957,19 @@ class Session:
         h = np.zeros(16, np.uint8)
         _chk(lib().gsv_session_ciphertext_hash(self.h, instance, _p(h)))
         return h.tobytes()
+
+    def ciphertext_blake3(self, with_seconds=False):
+        """BLAKE3 of every instance's resident stream in gate order (after garble(), or after upload_ciphertexts of every instance),
+        hashed on the device where it lies: a list of 32-byte digests.  Sessions that retain the whole stream only.
+        with_seconds=True: (digests, device seconds from the first hash kernel to the last)."""
+        out = np.zeros((self.n, 32), np.uint8)
+        _chk(lib().gsv_session_ciphertext_blake3(self.h, _p(out)))
+        digests = [bytes(out[i]) for i in range(self.n)]
+        if not with_seconds:
+            return digests
+        s = C.c_double()
+        _chk(lib().gsv_engine_blake3_streams_seconds(self.engine.h, C.byref(s)))
+        return digests, s.value
 
     def close(self):
         if getattr(self, "h", None) is not None and _lib is not None and self.h and not sys.is_finalizing():

@@ -11,6 +11,8 @@
 // Records of a segment that do not fill a chunk (< 64) are carried to the next segment through one of two carry buffers (ping-pong:
 // a launch reads one and writes the other), chunk values that do not fill a group likewise through one of two value buffers.
 // Every instance has the same stream length and segmentation, so all counts are launch parameters the host computes.
+// A stream that is RESIDENT in program order (gsv_session_ciphertext_blake3) is hashed where it lies: b3_chunk_indexed_kernel reads the
+// records of a range through the position table instead of from a gate-order buffer; the carry, the values and the reduce are the same.
 //
 // Read pattern: one lane per chunk, i.e. neighbouring lanes read 1 KiB apart, four 16-byte non-temporal loads per 64-byte block.
 // No LDS, no atomics, no grid-wide synchronisation: a launch boundary separates the tree levels.
@@ -86,6 +88,65 @@ __global__ __launch_bounds__(64) void b3_chunk_kernel(const uint4* seg_, uint64_
   out[1] = u32x4{cv[4], cv[5], cv[6], cv[7]};
 }
 
+// The chunk kernel over a stream that lies in PROGRAM order (a resident ring / a plan call's block: program.hpp, ct_pos): record q of
+// the block's gate-order stream is block[(q / n_ct) * n_ct + ct_pos[q % n_ct]], and the launch hashes carry_in || records
+// [first, first + n) of it, n = 64 n_chunks + tail_n - carry_n.  Everything else — chunk numbers, the carry, where the values go — is
+// b3_chunk_kernel's, so the reduce kernels and the host's bookkeeping (B3Stream) do not know which of the two ran.
+// A cursor divides once, where it enters the block, and then steps (replay, g) with a wrap.  Read pattern: neighbouring lanes are 64
+// gate positions apart at scattered program-order addresses (the read of gather_segment_kernel without its write and the second read);
+// the records of a 128-byte line are read by several lanes, or by one lane in successive trips, at different times.  Plain loads (they
+// may hit the CU's L1; non-temporal ones are served by L2 every time) measured 19 % faster here.
+#ifndef GSV_B3_INDEXED_NT
+#define GSV_B3_INDEXED_NT 0  // load flavour of the scattered record reads: plain (0) or non-temporal (1).  Measured: plain 814 GB/s, non-temporal 662-688 GB/s
+#endif
+struct B3IndexedCursor {
+  const glb_u128* carry;
+  const glb_u128* block;
+  const uint32_t* ct_pos;
+  uint64_t n_ct, idx, rep_base, g;  // idx: position in carry || range; (rep_base, g): where the next record of the range lies
+  uint32_t carry_n;
+  __device__ __forceinline__ B3IndexedCursor(const glb_u128* carry_, uint32_t carry_n_, const glb_u128* block_, const uint32_t* ct_pos_, uint64_t n_ct_, uint64_t first, uint64_t idx_)
+      : carry(carry_), block(block_), ct_pos(ct_pos_), n_ct(n_ct_), idx(idx_), carry_n(carry_n_) {
+    const uint64_t q = first + (idx_ > carry_n_ ? idx_ - carry_n_ : 0u);
+    rep_base = (q / n_ct_) * n_ct_;
+    g = q - rep_base;
+  }
+  __device__ __forceinline__ u32x4 next() {
+    if (idx < carry_n) return __builtin_nontemporal_load(carry + idx++);
+    const glb_u128* p = block + (rep_base + ct_pos[g]);
+    if (++g == n_ct) { g = 0; rep_base += n_ct; }
+#if GSV_B3_INDEXED_NT
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+  }
+};
+// grid and outputs as b3_chunk_kernel; block_stride = records between the instances' blocks
+__global__ __launch_bounds__(64) void b3_chunk_indexed_kernel(const uint4* block_, uint64_t block_stride, const uint32_t* ct_pos, uint64_t n_ct, uint64_t first, const uint4* carry_in_, uint32_t carry_n,
+                                                              uint4* carry_out_, uint32_t tail_n, uint64_t chunk0, uint32_t n_chunks, uint32_t* cv_, uint64_t cv_stride, uint32_t cv_off) {
+  const uint32_t inst = blockIdx.y;
+  const glb_u128* block = (const glb_u128*)(block_) + uint64_t(inst) * block_stride;
+  const glb_u128* carry = (const glb_u128*)(carry_in_) + uint64_t(inst) * 64u;
+  if (blockIdx.x == 0 && threadIdx.x < tail_n)
+    ((glb_u128*)carry_out_)[uint64_t(inst) * 64u + threadIdx.x] = B3IndexedCursor(carry, carry_n, block, ct_pos, n_ct, first, uint64_t(n_chunks) * 64u + threadIdx.x).next();
+  const uint32_t j = blockIdx.x * 64u + threadIdx.x;
+  if (j >= n_chunks) return;
+  const uint64_t ctr = chunk0 + j;
+  B3IndexedCursor cur(carry, carry_n, block, ct_pos, n_ct, first, uint64_t(j) * 64u);
+  uint32_t cv[8] = {0x6A09E667u, 0xBB67AE85u, 0x3C6EF372u, 0xA54FF53Au, 0x510E527Fu, 0x9B05688Cu, 0x1F83D9ABu, 0x5BE0CD19u};
+  u32x4 r0 = cur.next(), r1 = cur.next(), r2 = cur.next(), r3 = cur.next();
+#pragma unroll 1
+  for (uint32_t b = 0; b < 16u; ++b) {
+    const uint32_t m[16] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, r3.x, r3.y, r3.z, r3.w};
+    if (b < 15u) { r0 = cur.next(); r1 = cur.next(); r2 = cur.next(); r3 = cur.next(); }  // the next block's records are in flight while this one is compressed
+    b3_compress(cv, m, uint32_t(ctr), uint32_t(ctr >> 32), (b == 0 ? GSV_B3_CHUNK_START : 0u) | (b == 15u ? GSV_B3_CHUNK_END : 0u));
+  }
+  glb_u128* out = (glb_u128*)(cv_) + (uint64_t(inst) * cv_stride + cv_off + j) * 2u;
+  out[0] = u32x4{cv[0], cv[1], cv[2], cv[3]};
+  out[1] = u32x4{cv[4], cv[5], cv[6], cv[7]};
+}
+
 // One level of the group trees, in place: cv[inst][i * step] <- parent(cv[inst][i * step], cv[inst][i * step + step / 2]) for i < n_parents.
 // A lane reads both children before it writes over the left one, and no other lane of the launch touches either.
 __global__ __launch_bounds__(64) void b3_parent_kernel(uint32_t* cv_, uint64_t cv_stride, uint32_t n_parents, uint32_t step) {
@@ -125,6 +186,16 @@ int gsvk_b3_chunks(const void* seg, uint64_t seg_stride, const void* carry_in, u
   if (n_chunks == 0 && tail_n == 0) return 0;
   hipLaunchKernelGGL(gsv::dev::b3_chunk_kernel, dim3(n_chunks ? (n_chunks + 63u) / 64u : 1u, n_instances), dim3(64), 0, s, static_cast<const uint4*>(seg), seg_stride,
                      static_cast<const uint4*>(carry_in), carry_n, static_cast<uint4*>(carry_out), tail_n, chunk0, n_chunks, static_cast<uint32_t*>(cv), cv_stride, cv_off);
+  return int(hipGetLastError());
+}
+// the same over records [first, first + n) of a program-order block's gate-order stream (b3_chunk_indexed_kernel); the caller keeps the range inside the block
+int gsvk_b3_chunks_indexed(const void* block, uint64_t block_stride, const void* ct_pos, uint64_t n_ct, uint64_t first, const void* carry_in, uint32_t carry_n, void* carry_out, uint32_t tail_n,
+                           uint64_t chunk0, uint32_t n_chunks, void* cv, uint64_t cv_stride, uint32_t cv_off, uint32_t n_instances, hipStream_t s) {
+  if (n_instances == 0 || n_ct == 0 || tail_n > 64u || carry_n > 64u || uint64_t(cv_off) + n_chunks > cv_stride) return int(hipErrorInvalidValue);
+  if (n_chunks == 0 && tail_n == 0) return 0;
+  hipLaunchKernelGGL(gsv::dev::b3_chunk_indexed_kernel, dim3(n_chunks ? (n_chunks + 63u) / 64u : 1u, n_instances), dim3(64), 0, s, static_cast<const uint4*>(block), block_stride,
+                     static_cast<const uint32_t*>(ct_pos), n_ct, first, static_cast<const uint4*>(carry_in), carry_n, static_cast<uint4*>(carry_out), tail_n, chunk0, n_chunks,
+                     static_cast<uint32_t*>(cv), cv_stride, cv_off);
   return int(hipGetLastError());
 }
 // n_have values per instance in cv (stride cv_stride values): n_have / 2^k groups are reduced and written to red (dense), the rest moves to the

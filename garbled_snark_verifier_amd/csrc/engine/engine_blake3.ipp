@@ -1,5 +1,6 @@
 // Part of engine.cpp: BLAKE3 commitments — the host hasher behind gsv_blake3_*, and the device tree hash of n equally long streams
-// that arrive in segments of a gate-order buffer (blake3_device.hpp), shared by the streaming drain (engine_drain.ipp) and
+// that arrive in segments of a gate-order buffer (blake3_device.hpp), shared by the streaming drain (engine_drain.ipp), the streaming
+// evaluators and gsv_session_ciphertext_blake3 (engine_evaluate.ipp: the latter feeds ranges of the resident program-order stream) and
 // gsv_engine_blake3_streams.
 //
 // Split (DESIGN.md §3 "Commitment stage"): a stream of L records has N = max(1, ceil(L / 64)) chunks.  The device hashes chunks
@@ -42,7 +43,10 @@ static int b3_begin(std::unique_ptr<B3Stream>& p, size_t n_inst, uint64_t total,
 }
 // The next n records of every stream: buf[inst * stride + r], r < n.  Launches on st; when st has been synchronised *n_groups group values
 // per instance sit in b.pinned ([inst][group], dense) and buf is free again.
-static int b3_segment(B3Stream& b, const void* buf, uint64_t stride, uint64_t n, hipStream_t st, uint32_t* n_groups) {
+// ... or, with `ix`, records [ix->first, ix->first + n) of the gate-order stream of a block that lies in program order (a resident
+// ring, a plan call's block): block[inst * stride + (q / n_ct) * n_ct + ct_pos[q % n_ct]].  The block is only read.
+struct B3Indexed { const void* ct_pos; uint64_t n_ct, first; };
+static int b3_segment(B3Stream& b, const void* buf, uint64_t stride, uint64_t n, hipStream_t st, uint32_t* n_groups, const B3Indexed* ix = nullptr) {
   *n_groups = 0;
   if (n > b.seg_cap || b.records_done + n > b.total) return fail(GSV_ERR_INVALID, "internal: BLAKE3 segment outside the stream");
   if (n == 0) return GSV_OK;
@@ -50,8 +54,9 @@ static int b3_segment(B3Stream& b, const void* buf, uint64_t stride, uint64_t n,
   const uint32_t n_chunks = uint32_t(std::min<uint64_t>(avail / 64, b.dev_chunks - b.chunks_done));
   const uint64_t tail = avail - 64ull * n_chunks;
   if (tail > 64 || uint64_t(b.pend) + n_chunks > b.cv_stride) return fail(GSV_ERR_INVALID, "internal: BLAKE3 carry / value buffer overflow");
-  if (gsvk_b3_chunks(buf, stride, b.carry[b.cpar].get(), b.carry_n, b.carry[b.cpar ^ 1].get(), uint32_t(tail), b.chunks_done, n_chunks, b.cv[b.vpar].get(), b.cv_stride, b.pend, uint32_t(b.n_inst), st) != 0)
-    return fail(GSV_ERR_DEVICE, "BLAKE3 chunk kernel launch failed");
+  const int krc = ix ? gsvk_b3_chunks_indexed(buf, stride, ix->ct_pos, ix->n_ct, ix->first, b.carry[b.cpar].get(), b.carry_n, b.carry[b.cpar ^ 1].get(), uint32_t(tail), b.chunks_done, n_chunks, b.cv[b.vpar].get(), b.cv_stride, b.pend, uint32_t(b.n_inst), st)
+                     : gsvk_b3_chunks(buf, stride, b.carry[b.cpar].get(), b.carry_n, b.carry[b.cpar ^ 1].get(), uint32_t(tail), b.chunks_done, n_chunks, b.cv[b.vpar].get(), b.cv_stride, b.pend, uint32_t(b.n_inst), st);
+  if (krc != 0) return fail(GSV_ERR_DEVICE, "BLAKE3 chunk kernel launch failed");
   b.cpar ^= 1; b.carry_n = uint32_t(tail); b.chunks_done += n_chunks; b.records_done += n;
   if (n_chunks) {
     const uint32_t n_have = b.pend + n_chunks, groups = n_have >> b.k;

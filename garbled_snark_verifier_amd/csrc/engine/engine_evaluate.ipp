@@ -17,7 +17,9 @@ int gsv_session_evaluate(gsv_session* s, uint64_t gate_id_base) {
 // page-locked 16 MiB staging buffer: a window may be gigabytes), are folded into the per-instance CBC-MAC as FileSource does while
 // reading (ciphertext_source.rs:36-107), uploaded, scattered to the program-order positions the kernel reads, and evaluated.
 //   read(instance, first_record, dst, n) -> 0, or non-zero when the source runs dry ("Ciphertext source exhausted", evaluate_mode.rs:139-142)
-static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const std::function<int(size_t, uint64_t, uint8_t*, uint64_t)>& read, uint8_t* hashes) {
+// With `digests` the uploaded gate-order segments are also fed to the BLAKE3 kernels of the garbler's drain (engine_blake3.ipp), on the
+// stream that scatters them: what the evaluator compares with commit_i = BLAKE3(gc_<i>.bin) costs the host 32 bytes per group of chunks.
+static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const std::function<int(size_t, uint64_t, uint8_t*, uint64_t)>& read, uint8_t* hashes, uint8_t* digests) {
   const Program& g = s->prog();
   // plan sessions: one window of the schedule per launch, its ciphertexts uploaded SEGMENT by segment (schedule.hpp: a gate-order buffer
   // holds the largest segment, the program-order device block the largest window); program sessions: one ring per launch
@@ -69,6 +71,31 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
     }
     ~MacPool() { finish(); }
   } pool(macs, T, NB);
+  // BLAKE3: every pass starts the hash afresh (the pass the safe-schedule fallback repeats too).  The group values of a segment sit in
+  // the page-locked buffer once `b3_ev` — recorded behind the segment's hash kernels, in front of its scatter — has passed, and are
+  // absorbed before the next segment's kernels are enqueued.
+  Event b3_ev;
+  uint32_t b3_groups = 0;
+  if (digests) {
+    int brc = b3_begin(s->b3_eval, n_inst, s->plan ? s->plan->n_ct : s->replays * g.n_ct, seg_records, s->pass.b3_subtree_log2);
+    if (brc) return brc;
+    HIPCHK(b3_ev.create(hipEventDisableTiming));
+  }
+  auto b3_flush = [&]() -> int {
+    if (!b3_groups) return GSV_OK;
+    if (hipEventSynchronize(b3_ev.get()) != hipSuccess) return fail(GSV_ERR_DEVICE, "event wait failed");
+    const bool ok = b3_absorb(*s->b3_eval, s->b3_eval->pinned.get(), b3_groups, s->b3_eval->k, 0, 1);
+    b3_groups = 0;
+    return ok ? GSV_OK : fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
+  };
+  // the `n` records per instance just uploaded to the gate-order buffer through `st`
+  auto b3_feed = [&](uint64_t n, hipStream_t st) -> int {
+    if (!digests) return GSV_OK;
+    int frc = b3_flush();
+    if (frc == GSV_OK) frc = b3_segment(*s->b3_eval, s->ct_gate.get(), seg_records, n, st, &b3_groups);
+    if (frc == GSV_OK && b3_groups && hipEventRecord(b3_ev.get(), st) != hipSuccess) frc = fail(GSV_ERR_DEVICE, "event record failed");
+    return frc;
+  };
   if (s->plan) HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));
   HIPCHK(hipEventRecord(s->ev0.get(), s->e->stream.get()));
   int rc = GSV_OK;
@@ -110,6 +137,7 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
         if (window_done) { rc = fail(GSV_ERR_DEVICE, "internal: the window finished before its ciphertexts were uploaded"); break; }
         // uploads and the scatter go through the side stream (the main stream holds the running window)
         rc = upload(sg.ct0, sg.n_ct, s->aux_stream.get());
+        if (rc == GSV_OK) rc = b3_feed(sg.n_ct, s->aux_stream.get());
         if (rc == GSV_OK) rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, seg_records, 1, nullptr, nullptr, s->aux_stream.get());
         if (rc == GSV_OK && hipStreamSynchronize(s->aux_stream.get()) != hipSuccess) rc = fail(GSV_ERR_DEVICE, "ciphertext scatter failed");
         if (rc == GSV_OK) __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);
@@ -129,6 +157,7 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
         const Schedule::Segment& sg = s->sched.segments[q];
         // (the stream orders this segment's uploads behind the scatter of the previous one, which read the same buffer)
         rc = upload(sg.ct0, sg.n_ct, s->e->stream.get());
+        if (rc == GSV_OK) rc = b3_feed(sg.n_ct, s->e->stream.get());
         if (rc == GSV_OK) rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, seg_records, 1, nullptr, nullptr, nullptr);
       }
       if (rc == GSV_OK) rc = launch_plan_window(s, w, gate_id_base, true);
@@ -138,6 +167,7 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
     for (uint64_t r0 = 0; r0 < total && rc == GSV_OK; r0 += seg) {
       const uint64_t r1 = std::min(total, r0 + seg);
       rc = upload(r0 * n_ct, (r1 - r0) * n_ct, s->e->stream.get());
+      if (rc == GSV_OK) rc = b3_feed((r1 - r0) * n_ct, s->e->stream.get());
       if (rc != GSV_OK) break;
       if (gsvk_gather_segment(s->CT.get(), s->ct_stride(), s->dp->ct_pos.as<const uint32_t>(), n_ct, uint32_t(r1 - r0), uint32_t(n_inst), s->ct_gate.get(), seg_records, 1, s->e->stream.get()) != 0) { rc = fail(GSV_ERR_DEVICE, "ciphertext scatter launch failed"); break; }
       rc = launch(s, gate_id_base, true, r0, r1 - r0);
@@ -147,23 +177,28 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
   if (rc != GSV_OK) return rc;
   if (s->plan) { HIPCHK(hipEventRecord(s->ev1.get(), s->e->stream.get())); rc = gather_plan_outputs(s, true); if (rc) return rc; HIPCHK(hipStreamSynchronize(s->e->stream.get())); rc = check_plan_error(s); if (rc) return rc; }
   pool.finish();
+  if (digests) {  // (before the MACs are written: a failure leaves both arrays untouched)
+    rc = b3_flush();
+    if (rc == GSV_OK) rc = b3_finish(*s->b3_eval, s->e->stream.get(), digests);
+    if (rc) return rc;
+  }
   if (hashes) for (size_t i = 0; i < n_inst; ++i) macs[i].digest(hashes + 16 * i);
   return GSV_OK;
 }
 // The evaluator's side of the safe-schedule fallback (engine_drain.ipp, fall_back_to_safe_schedule): a pass that ended with a dependency wait
 // giving up switches the session to one call per launch; a source that can be read again from the start (gc files) is then evaluated
 // again at once, any other source gets the error with the remedy (its records have been consumed) and the host's repeat succeeds.
-static int evaluate_streaming_impl(gsv_session* s, uint64_t gate_id_base, const std::function<int(size_t, uint64_t, uint8_t*, uint64_t)>& read, uint8_t* hashes, bool rereadable = false) {
-  int rc = evaluate_streaming_pass(s, gate_id_base, read, hashes);
+static int evaluate_streaming_impl(gsv_session* s, uint64_t gate_id_base, const std::function<int(size_t, uint64_t, uint8_t*, uint64_t)>& read, uint8_t* hashes, uint8_t* digests, bool rereadable = false) {
+  int rc = evaluate_streaming_pass(s, gate_id_base, read, hashes, digests);
   if (rc != GSV_ERR_DEVICE || !s->plan || !s->dep_fault || s->safe_mode) return rc;
   const std::string first_error = g_err;
   if (fall_back_to_safe_schedule(s)) return fail(GSV_ERR_DEVICE, first_error + "; the fall-back to the safe schedule failed too: " + g_err);
   if (!rereadable) return fail(GSV_ERR_DEVICE, first_error + "; the session now runs the safe schedule (one call per launch): repeat the pass from gsv_session_set_evaluate_inputs");
   if (s->pass.drain_debug || s->pass.plan_debug) std::fprintf(stderr, "plan session: %s -- repeating the evaluation on the safe schedule (one call per launch)\n", first_error.c_str());
-  return evaluate_streaming_pass(s, gate_id_base, read, hashes);
+  return evaluate_streaming_pass(s, gate_id_base, read, hashes, digests);
 }
 // FileSource: instance i reads <dir>/gc_<indexes[i]>.bin (indexes == NULL: first_index + i)
-static int evaluate_from_files(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint64_t first_index, uint8_t* hashes) {
+static int evaluate_from_files(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint64_t first_index, uint8_t* hashes, uint8_t* digests) {
   if (!s || !dir) return fail(GSV_ERR_INVALID, "null argument");
   std::vector<FILE*> files(s->n_inst, nullptr);
   struct Closer { std::vector<FILE*>& f; ~Closer() { for (FILE*& q : f) if (q) { std::fclose(q); q = nullptr; } } } closer{files};
@@ -179,21 +214,31 @@ static int evaluate_from_files(gsv_session* s, uint64_t gate_id_base, const char
     if (n && std::fread(dst, 16, n, files[i]) != n) return 1;
     pos[i] += n;
     return 0;
-  }, hashes, /*rereadable=*/true);
+  }, hashes, digests, /*rereadable=*/true);
 }
 int gsv_session_evaluate_streaming(gsv_session* s, uint64_t gate_id_base, const char* dir, uint64_t first_index, uint8_t* hashes) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
-  return evaluate_from_files(s, gate_id_base, dir, nullptr, first_index, hashes);
+  return evaluate_from_files(s, gate_id_base, dir, nullptr, first_index, hashes, nullptr);
 }
 int gsv_session_evaluate_streaming_indexed(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint8_t* hashes) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   if (!indexes) return fail(GSV_ERR_INVALID, "null index list");
-  return evaluate_from_files(s, gate_id_base, dir, indexes, 0, hashes);
+  return evaluate_from_files(s, gate_id_base, dir, indexes, 0, hashes, nullptr);
 }
 int gsv_session_evaluate_streaming_source(gsv_session* s, uint64_t gate_id_base, gsv_ct_source_fn source, void* user, uint8_t* hashes) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   if (!s || !source) return fail(GSV_ERR_INVALID, "null argument");
-  return evaluate_streaming_impl(s, gate_id_base, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t n) -> int { return source(user, i, first, dst, n); }, hashes);
+  return evaluate_streaming_impl(s, gate_id_base, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t n) -> int { return source(user, i, first, dst, n); }, hashes, nullptr);
+}
+// The three above with either commitment or both (blake3_digests == NULL is what they do)
+int gsv_session_evaluate_streaming_commit(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint64_t first_index, uint8_t* cbcmac_hashes, uint8_t* blake3_digests) {
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
+  return evaluate_from_files(s, gate_id_base, dir, indexes, first_index, cbcmac_hashes, blake3_digests);
+}
+int gsv_session_evaluate_streaming_source_commit(gsv_session* s, uint64_t gate_id_base, gsv_ct_source_fn source, void* user, uint8_t* cbcmac_hashes, uint8_t* blake3_digests) {
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
+  if (!s || !source) return fail(GSV_ERR_INVALID, "null argument");
+  return evaluate_streaming_impl(s, gate_id_base, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t n) -> int { return source(user, i, first, dst, n); }, cbcmac_hashes, blake3_digests);
 }
 
 int gsv_session_set_hasher(gsv_session* s, int kind) {
@@ -309,6 +354,66 @@ int gsv_session_ciphertext_hash(gsv_session* s, size_t instance, uint8_t hash[16
   }
   mac.digest(hash);
   return GSV_OK;
+}
+// BLAKE3 of every instance's retained stream, hashed where it lies (blake3_device.hpp, b3_chunk_indexed_kernel): ranges of at most
+// GSV_B3_RESIDENT_RECORDS records per instance — of the one ring (program sessions), of one call block after the other (plan sessions;
+// chunks straddle ranges and blocks through the carry) — go through the chunk, reduce and carry code of the drain on the engine's stream.
+int gsv_session_ciphertext_blake3(gsv_session* s, uint8_t* digests) {
+  if (!s || !digests) return fail(GSV_ERR_INVALID, "null argument");
+  const knobs::ResidentB3 kn;
+  if (s->ct_cap != s->replays || (s->plan && !s->plan_retain)) return fail(GSV_ERR_INVALID, "the session retains only part of the stream (ct_capacity_replays < replays)");
+  const uint64_t total = s->ct_stride();
+  if (!s->garbled)
+    for (size_t i = 0; i < s->n_inst; ++i)
+      if (s->ct_uploaded[i] < total)
+        return fail(GSV_ERR_EXHAUSTED, "Ciphertext source exhausted: instance " + std::to_string(i) + " holds " + std::to_string(s->ct_uploaded[i]) + " of " + std::to_string(total) + " ciphertexts");
+  HIPCHK(hipSetDevice(s->e->device));
+  uint64_t cap = kn.resident_records;
+  if (!cap) {
+    // two value buffers of (2^k - 1 pending + cap / 64 + 2) x 32 bytes per instance (b3_begin) in a tenth of what is free
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t values = uint64_t(free_b) / 10 / (2 * 32 * s->n_inst), fixed = (1ull << std::min<uint32_t>(kn.b3_subtree_log2, 20)) + 2;
+    cap = std::min<uint64_t>(64ull << 20, values > fixed ? (values - fixed) * 64 : 64);
+  }
+  cap = std::min(cap, std::max<uint64_t>(total, 1));
+  const hipStream_t st = s->e->stream.get();
+  std::unique_ptr<B3Stream> b;
+  struct Quiesce { hipStream_t st; ~Quiesce() { (void)hipStreamSynchronize(st); } } quiesce{st};  // declared after `b`: nothing of its buffers is in flight when they go
+  int rc = b3_begin(b, s->n_inst, total, cap, kn.b3_subtree_log2);
+  if (rc) return rc;
+  Event t0, t1;
+  HIPCHK(t0.create()); HIPCHK(t1.create());
+  HIPCHK(hipEventRecord(t0.get(), st));
+  // records [first, first + n) of the gate-order stream of one block (block_off records into every instance's stream, n_ct records per replay)
+  auto feed = [&](uint64_t block_off, const DevBuf& ct_pos, uint64_t n_ct, uint64_t block_records) -> int {
+    for (uint64_t first = 0; first < block_records; first += cap) {
+      const B3Indexed ix{ct_pos.get(), n_ct, first};
+      uint32_t groups = 0;
+      int frc = b3_segment(*b, static_cast<const uint8_t*>(s->CT.get()) + block_off * 16, s->ct_stride(), std::min(cap, block_records - first), st, &groups, &ix);
+      if (frc) return frc;
+      if (groups) {  // the group values sit in the page-locked buffer once the stream is idle, and must be out of it before the next range
+        HIPCHK(hipStreamSynchronize(st));
+        if (!b3_absorb(*b, b->pinned.get(), groups, b->k, 0, 1)) return fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
+      }
+    }
+    return GSV_OK;
+  };
+  if (!s->plan) rc = total ? feed(0, s->dp->ct_pos, s->prog().n_ct, total) : GSV_OK;
+  else
+    for (size_t k = 0; k < s->plan->calls.size() && rc == GSV_OK; ++k) {
+      const uint64_t n_ct = s->call_prog(k).n_ct;
+      if (n_ct) rc = feed(s->plan->calls[k].ct_off, s->call_dev[k]->ct_pos, n_ct, n_ct);
+    }
+  if (rc) return rc;
+  float ms = 0;
+  HIPCHK(hipEventRecord(t1.get(), st));
+  HIPCHK(hipEventSynchronize(t1.get()));
+  HIPCHK(hipEventElapsedTime(&ms, t0.get(), t1.get()));
+  s->e->b3_streams_seconds = double(ms) * 1e-3;
+  rc = b3_finish(*b, st, digests);
+  if (rc) return rc;
+  return s->plan ? check_plan_error(s) : GSV_OK;  // (behind an asynchronous garble: a pass whose dependency wait gave up left no stream to commit to)
 }
 int gsv_cbcmac_update(uint8_t state[16], const uint8_t* cts, uint64_t n_records) {
   if (!state || (!cts && n_records)) return fail(GSV_ERR_INVALID, "null argument");

@@ -112,6 +112,10 @@ int gsvk_scatter_bits(void* VB, uint32_t n_slots, uint32_t first_slot, const voi
 // records behind the last chunk go to carry_out[inst] (64 records per instance, never carry_in)
 int gsvk_b3_chunks(const void* seg, uint64_t seg_stride, const void* carry_in, uint32_t carry_n, void* carry_out, uint32_t tail_n, uint64_t chunk0, uint32_t n_chunks,
                    void* cv, uint64_t cv_stride, uint32_t cv_off, uint32_t n_instances, hipStream_t s);
+// the same with the records read where a resident stream lies: record q of [first, first + n), n = 64 n_chunks + tail_n - carry_n, is
+// block[inst][(q / n_ct) * n_ct + ct_pos[q % n_ct]] (block_stride in records; the range must lie inside the block)
+int gsvk_b3_chunks_indexed(const void* block, uint64_t block_stride, const void* ct_pos, uint64_t n_ct, uint64_t first, const void* carry_in, uint32_t carry_n, void* carry_out, uint32_t tail_n,
+                           uint64_t chunk0, uint32_t n_chunks, void* cv, uint64_t cv_stride, uint32_t cv_off, uint32_t n_instances, hipStream_t s);
 // the first (n_have >> k) << k values of cv[inst] become n_have >> k group values in red[inst] (dense), the rest moves to the front of cv_next[inst]
 int gsvk_b3_reduce(void* cv, uint64_t cv_stride, uint32_t n_have, uint32_t k, void* red, void* cv_next, uint32_t n_instances, hipStream_t s);
 }

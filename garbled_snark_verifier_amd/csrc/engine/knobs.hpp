@@ -50,7 +50,11 @@
 // GSV_DRAIN_COPIES            int      3                    pass                                   copy streams of the drain
 // GSV_DRAIN_DEPTH             int      by free memory       pass                                   gate-order buffers of the drain pipeline
 // GSV_PAIR_CU_MASK            flag     1                    pass                                   CU-masked streams for garble || evaluate pairs
-// GSV_B3_SUBTREE_LOG2         0..20    10                   pass, gsv_engine_blake3_streams        BLAKE3 commitments: log2 of the chunks the device reduces to one value (anything else: the call is refused)
+// GSV_B3_SUBTREE_LOG2         0..20    10                   pass, gsv_engine_blake3_streams,       BLAKE3 commitments: log2 of the chunks the device reduces to one value (anything else: the call is refused)
+//                                                             gsv_session_ciphertext_blake3
+// -- a knobs::ResidentB3 at gsv_session_ciphertext_blake3 (with GSV_B3_SUBTREE_LOG2)
+// GSV_B3_RESIDENT_RECORDS     int      by free memory       gsv_session_ciphertext_blake3          most records per instance one launch range of the resident hash covers
+//                                                                                                    (default: the two chunk-value buffers take <= 1/10 of the free memory, <= 64 M records)
 #pragma once
 #include <algorithm>  // (with <initializer_list>)
 #include <cstdlib>
@@ -114,5 +118,9 @@ struct Pass {
   uint64_t drain_chunk_mb = uint64_t(std::max(1ll, int_or("GSV_DRAIN_CHUNK_MB", 16)));
   size_t drain_depth = size_t(at_least_1("GSV_DRAIN_DEPTH"));  // 0 = by free memory
   uint32_t b3_subtree_log2 = knobs::b3_subtree_log2();
+};
+struct ResidentB3 {
+  uint32_t b3_subtree_log2 = knobs::b3_subtree_log2();
+  uint64_t resident_records = at_least_1("GSV_B3_RESIDENT_RECORDS");  // 0 = by free memory
 };
 }  // namespace gsv::knobs

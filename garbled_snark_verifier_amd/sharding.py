@@ -228,13 +228,15 @@ class ConsistencyError(Exception):
         self.kind, self.index, self.details = kind, index, details
 
 
-def _gpu_evaluate_batch(circuit, engine, program, gc_dir):
+def _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment="cbcmac"):
     """Default evaluation backend of evaluate_from: EvaluateMode over FileSources on the GPU, ALL finalized instances in one session —
     one launch per window of the stream for the whole batch (gsv_session_evaluate_streaming_indexed).  The reference evaluates the
     cases side by side on a rayon pool (`into_par_iter`, cut_and_choose/evaluator.rs:354-475); a one-instance session per case would
     use one CU of 256 and pay a session per case.  The files' CBC-MACs (the CiphertextMismatch check) are folded while reading, instance i on
-    worker i mod T of the engine's pool, beside the uploads (engine.cpp, evaluate_streaming_impl)."""
+    worker i mod T of the engine's pool, beside the uploads (engine.cpp, evaluate_streaming_impl).  commitment="blake3": the hash of a
+    case is the first 16 bytes of its file's BLAKE3 digest instead, computed on the device from the uploaded segments (no MAC worker)."""
     from . import Engine, Plan, Program, Session
+    _check_commitment(commitment)
     eng = engine or Engine(0)
     prog = program or Program.from_circuit(circuit)
 
@@ -244,7 +246,7 @@ def _gpu_evaluate_batch(circuit, engine, program, gc_dir):
         try:
             consts = np.stack([np.asarray(false_active, np.uint8).reshape(B, 16), np.asarray(true_active, np.uint8).reshape(B, 16)], axis=1)
             sess.set_evaluate_inputs(consts, np.asarray(input_active, np.uint8).reshape(B, -1, 16), np.asarray(input_bits, np.uint8).reshape(B, -1))
-            hashes = sess.evaluate_streaming_indexed(gc_dir, [int(i) for i in indexes])
+            hashes = [h[:16] for h in sess.evaluate_streaming_indexed(gc_dir, [int(i) for i in indexes], commitment=commitment)]
             labels, bits = sess.read_outputs(with_bits=True)
             return [(labels[k], bits[k], hashes[k]) for k in range(B)]
         finally:
@@ -252,7 +254,7 @@ def _gpu_evaluate_batch(circuit, engine, program, gc_dir):
     return run
 
 
-def evaluate_from(commits, cases, circuit, gc_dir, n_outputs, engine=None, program=None, evaluate=None, evaluate_batch=None):
+def evaluate_from(commits, cases, circuit, gc_dir, n_outputs, engine=None, program=None, evaluate=None, evaluate_batch=None, commitment="cbcmac"):
     """Evaluator::evaluate_from (cut_and_choose/evaluator.rs:338-476): evaluate the finalized instances from their gc_<i>.bin and
     check everything the evaluator was handed against the garbler's commit record BEFORE trusting the result.
     `cases`: list of dicts {index, true_constant_wire[16], false_constant_wire[16], input_active[n_in,16], input_bits[n_in]}
@@ -265,15 +267,19 @@ def evaluate_from(commits, cases, circuit, gc_dir, n_outputs, engine=None, progr
     raised is the one a case-by-case run in list order would raise (per case the reference's order of checks, evaluator.rs:371-465).
     `evaluate_batch(indexes, true[B,16], false[B,16], input_active[B,n_in,16], input_bits[B,n_in]) -> [(output_active, output_bits,
     ciphertext_hash)]` defaults to the GPU evaluator; `evaluate(index, true, false, input_active, input_bits) -> (..)` is the
-    case-by-case form tests without a GPU pass (the CPU oracle's)."""
+    case-by-case form tests without a GPU pass (the CPU oracle's).
+    commitment="blake3": the table was written with commitment="blake3" (garble_and_commit), the record's hash field is the first 16
+    bytes of BLAKE3(gc_<i>.bin), and the default GPU evaluator returns that of the file it read; the stand-ins keep their signature
+    and return whatever hash they choose."""
     import os
     from . import gc_file_name
+    _check_commitment(commitment)
     commits = np.asarray(commits, np.uint8)
     if evaluate_batch is None:
         if evaluate is not None:
             evaluate_batch = lambda idx, t, f, a, b: [evaluate(idx[k], t[k], f[k], a[k], b[k]) for k in range(len(idx))]  # noqa: E731
         else:
-            evaluate_batch = _gpu_evaluate_batch(circuit, engine, program, gc_dir)
+            evaluate_batch = _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment)
     n_in_committed = (commits.shape[1] - record_len(n_outputs, 0)) // 32
     parsed, first_error = [], None
     for case in cases:

@@ -461,6 +461,24 @@ int gsv_commit_labels(const uint8_t* labels, uint64_t n, uint8_t* out);
  * blake3_digests alone nothing of the stream is copied to the host and no MAC workers run. */
 int gsv_session_garble_streaming_commit(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* dir, uint64_t first_index, int n_threads,
                                         uint8_t* cbcmac_hashes, uint8_t* blake3_digests);
+/* The evaluator's side.  gsv_session_evaluate_streaming_commit is gsv_session_evaluate_streaming (indexes == NULL: instance i reads
+ * <dir>/gc_<first_index + i>.bin) and gsv_session_evaluate_streaming_indexed (instance i reads gc_<indexes[i]>.bin) with either
+ * commitment or both; gsv_session_evaluate_streaming_source_commit likewise for a generic source.  cbcmac_hashes (n_instances x 16, or
+ * NULL) receives the CBC-MAC of what was read, blake3_digests (n_instances x 32, or NULL) its BLAKE3: every uploaded segment is hashed
+ * on the device, in gate order, on the stream that scatters it, before the evaluation reads it.  With blake3_digests alone no MAC
+ * worker runs on the host.  The digest covers what was read, tampered or not: comparing it with the garbler's commitment is the
+ * caller's part.  A source that runs dry is GSV_ERR_EXHAUSTED and leaves both arrays untouched; the pass the safe-schedule fallback
+ * repeats restarts both hashes. */
+int gsv_session_evaluate_streaming_commit(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes /* NULL: first_index + i */, uint64_t first_index,
+                                          uint8_t* cbcmac_hashes, uint8_t* blake3_digests);
+int gsv_session_evaluate_streaming_source_commit(gsv_session* s, uint64_t gate_id_base, gsv_ct_source_fn source, void* user, uint8_t* cbcmac_hashes, uint8_t* blake3_digests);
+/* BLAKE3 of every instance's RESIDENT stream in gate order (what gsv_session_read_ciphertexts returns), after gsv_session_garble or
+ * after every instance's gsv_session_upload_ciphertexts: the device hashes the program-order stream where it lies, through the position
+ * table, at most GSV_B3_RESIDENT_RECORDS records per instance and launch (default: by free device memory); nothing of the stream is
+ * copied.  Sessions that hold the whole stream only (ct_capacity_replays == replays; plan sessions with retain_stream = 1), else
+ * GSV_ERR_INVALID; a stream neither garbled nor fully uploaded is GSV_ERR_EXHAUSTED as for gsv_session_evaluate.  The work is enqueued
+ * on the engine's stream (behind an asynchronous garble); the call returns when the digests are there. */
+int gsv_session_ciphertext_blake3(gsv_session* s, uint8_t* digests /* n_instances x 32 */);
 /* The host hasher: incremental, portable.  gsv_blake3_absorb_subtree takes the next 2^log2_chunks chunks of the input as the chaining
  * value of their subtree (log2_chunks = 0: a chunk's own chaining value): only between chunks, at a chunk count that is a multiple of
  * 2^log2_chunks, and never as the end of the input — the last chunk is always given as bytes. */
@@ -476,8 +494,9 @@ int gsv_blake3_file(const char* path, uint8_t* out /* 32 */);
  * drain; the host finishes them.  digests: n_streams x 32. */
 int gsv_engine_blake3_streams(gsv_engine* e, const uint8_t* data, uint64_t n_streams, uint64_t records_per_stream, const uint64_t* segment_records, uint64_t n_segments,
                               uint8_t* digests /* n_streams x 32 */);
-/* Device time of the engine's last gsv_engine_blake3_streams from the first hash kernel to the last (HIP events on the engine's stream:
- * the upload in front and the host's finish behind are outside; with several segments the host's folding between them is inside). */
+/* Device time of the engine's last gsv_engine_blake3_streams — or gsv_session_ciphertext_blake3 of one of its sessions — from the first
+ * hash kernel to the last (HIP events on the engine's stream: the upload in front and the host's finish behind are outside; with
+ * several segments the host's folding between them is inside). */
 int gsv_engine_blake3_streams_seconds(const gsv_engine* e, double* seconds);
 
 #ifdef __cplusplus

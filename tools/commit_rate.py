@@ -3,6 +3,7 @@
 device with BLAKE3 (DESIGN.md §3 "Commitment stage", §6), and the stand-alone rate of the BLAKE3 kernels.
 
     python tools/commit_rate.py [--instances 64,1024] [--rounds 2] [--kernel-gib 1] [--out profiles/commit_blake3]
+    python tools/commit_rate.py --evaluator [--resident-instances 4] [--evaluate-instances 16] [--out profiles/commit_blake3]
 
 The driver touches no GPU.  Every GPU step is a child process of this file under its own `timeout`:
   kernel   gsv.blake3_streams on 16 streams of --kernel-gib GiB each, one segment: device seconds from the first hash kernel to the last
@@ -13,6 +14,14 @@ The driver touches no GPU.  Every GPU step is a child process of this file under
            device's digest equals gsv.blake3_file of that file (47.7 GB through the host hasher) and the digest of the check pass;
   round    one batch size, warm (a discarded pass first), then the three legs in turn: discard, CBC-MAC drain, device BLAKE3 — `--rounds`
            children per batch size, so the legs alternate; GSV_DRAIN_STATS lines of the draining legs go to the log.
+  resident (--evaluator) a retained fq_mul program session of --resident-instances instances x --kernel-gib GiB of stream (one launch range
+           each by default): device seconds of Session.ciphertext_blake3() — the stream hashed in place through the position table
+           (gsv_engine_blake3_streams_seconds) — one digest compared with the host hasher's over read_ciphertexts; then, for the same
+           shape, the gather-then-hash cost of the drain: garble_streaming(commitment="blake3") minus garble_streaming(discard=True);
+  evaluate (--evaluator) fq12_mix, --batch instances: gc files written by a garbling pass, then evaluate_streaming with
+           commitment="cbcmac" and "blake3" in turn: wall seconds and host CPU seconds (user + system of the process) per pass;
+           digests and MACs equal the garbler's.
+--evaluator runs these two only (the evaluator's and the resident halves), into <out>/evaluator_rate.{json,log}.
 A child that fails, is killed at its time limit or dies ends the run: nothing more is started on the GPU.  At most 16 host threads
 (--threads) serve a drain.  Results: <out>/commit_rate.json and <out>/commit_rate.log.  Batches run in ascending order; one whose CBC-MAC
 leg — the plan's ciphertext bytes at the link rate the previous batch's CBC-MAC leg measured — cannot end within --leg-seconds is not
@@ -158,16 +167,117 @@ def child_round(a):
     return 0 if out["cbcmacs_equal_to_the_oracle_fixture"] == min(B, 16) else 1
 
 
+def _median(v):
+    return sorted(v)[len(v) // 2]
+
+
+def child_resident(a):
+    np, bs, gsv, eng = _child_setup()
+    prog = gsv.Program.from_circuit("fq_mul")
+    n_ct, n_in, B = prog.info["n_ciphertexts"], prog.info["n_inputs"], a.resident_instances
+    replays = -(-((a.kernel_gib << 30) // 16) // n_ct)
+    labs = [gsv.labels_from_seed(s, n_in) for s in range(1, B + 1)]
+    inputs = (np.stack([x[0] for x in labs]), np.stack([np.stack([x[1], x[2]]) for x in labs]), np.stack([x[3] for x in labs]))
+    sess = gsv.Session(eng, prog, B, replays)
+    sess.set_garble_inputs(*inputs)
+    sess.garble()
+    sess.sync()
+    secs, digests = [], None
+    for _ in range(7):
+        digests, sec = sess.ciphertext_blake3(with_seconds=True)
+        secs.append(sec)
+    secs = sorted(secs[1:])  # (the first call also allocates)
+    ok = digests[B - 1] == gsv.blake3(sess.read_ciphertexts(B - 1))
+    sess.close()
+    stream_bytes = B * replays * n_ct * 16
+    # the drain's way for the same shape: the whole stream is one segment, gathered into a gate-order buffer and hashed there
+    drain = gsv.Session(eng, prog, B, replays)
+    drain.set_garble_inputs(*inputs)
+    drain.garble_streaming(discard=True)  # warm
+    legs = {"discard": [], "blake3": []}
+    drained = None
+    for _ in range(3):
+        for leg in ("discard", "blake3"):
+            drain.set_garble_inputs(*inputs)
+            t0 = time.perf_counter()
+            if leg == "discard":
+                drain.garble_streaming(discard=True)
+            else:
+                drained = drain.garble_streaming(commitment="blake3")
+            legs[leg].append(time.perf_counter() - t0)
+    drain.close()
+    ok = ok and drained == digests
+    med = _median(secs)
+    print(json.dumps({"step": "resident", "circuit": "fq_mul", "instances": B, "replays": replays, "ciphertexts_per_replay": n_ct, "stream_bytes": stream_bytes, 
+                      "engine_library": os.environ.get("GSV_ENGINE_SO", "default"), "in_place_device_seconds": secs, "in_place_device_seconds_median": med, "in_place_bytes_per_s": stream_bytes / med,
+                      "drain_discard_seconds": legs["discard"], "drain_blake3_seconds": legs["blake3"], "gather_then_hash_seconds_median": _median(legs["blake3"]) - _median(legs["discard"]),
+                      "digests_equal_host_hasher_and_drain": ok}), flush=True)
+    return 0 if ok else 1
+
+
+def child_evaluate(a):
+    import resource
+    import shutil
+    import tempfile
+    np, bs, gsv, eng = _child_setup()
+    plan = gsv.Plan.from_circuit("fq12_mix", ["fq12::mul_montgomery", "fq12::square_montgomery"])
+    B, n_in, n_ct = a.batch, plan.info["n_inputs"], plan.info["n_ciphertexts"]
+    need = B * n_ct * 16
+    roots = [d for d in ("/dev/shm", tempfile.gettempdir()) if os.path.isdir(d) and os.statvfs(d).f_bavail * os.statvfs(d).f_frsize > 1.25 * need]
+    if not roots:
+        print(json.dumps({"step": "evaluate", "skipped": "no directory with room for %.1f GB of gc files" % (need / 1e9)}), flush=True)
+        return 0
+    labs = [gsv.labels_from_seed(s, n_in) for s in range(1, B + 1)]
+    delta = np.stack([x[0] for x in labs]); consts = np.stack([np.stack([x[1], x[2]]) for x in labs]); inputs = np.stack([x[3] for x in labs])
+    bits = np.random.default_rng(1).integers(0, 2, (B, n_in)).astype(np.uint8)
+    active = np.where(bits[:, :, None] == 1, inputs ^ delta[:, None, :], inputs)
+    consts_active = np.stack([consts[:, 0], consts[:, 1] ^ delta], axis=1)
+    d = tempfile.mkdtemp(prefix="gsv_commit_rate_", dir=roots[0])
+    try:
+        g = gsv.Session(eng, plan, B, retain_stream=False)
+        g.set_garble_inputs(delta, consts, inputs)
+        macs, digests = g.garble_streaming(directory=d, threads=a.threads, commitment="both")
+        out0 = g.read_outputs()
+        g.close()
+        ev = gsv.Session(eng, plan, B, retain_stream=False)
+
+        def leg(commitment):
+            ev.set_evaluate_inputs(consts_active, active, bits)
+            r0, t0 = resource.getrusage(resource.RUSAGE_SELF), time.perf_counter()
+            got = ev.evaluate_streaming(d, commitment=commitment)
+            dt, r1 = time.perf_counter() - t0, resource.getrusage(resource.RUSAGE_SELF)
+            return got, dt, (r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime)
+
+        ok = leg("both")[0] == (macs, digests)  # warm
+        legs = {"cbcmac": {"wall_seconds": [], "cpu_seconds": []}, "blake3": {"wall_seconds": [], "cpu_seconds": []}}
+        for _ in range(a.rounds + 1):
+            for c in ("cbcmac", "blake3"):
+                got, dt, cpu = leg(c)
+                ok = ok and got == (macs if c == "cbcmac" else digests)
+                legs[c]["wall_seconds"].append(dt); legs[c]["cpu_seconds"].append(cpu)
+        act, ob = ev.read_outputs(with_bits=True)
+        ok = ok and bool((act == np.where(ob[:, :, None] == 1, out0 ^ delta[:, None, :], out0)).all())
+        ev.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    for v in legs.values():
+        v["wall_seconds_median"], v["cpu_seconds_median"] = _median(v["wall_seconds"]), _median(v["cpu_seconds"])
+    print(json.dumps({"step": "evaluate", "circuit": "fq12_mix", "instances": B, "ciphertexts_per_instance": n_ct, "file_bytes": need, "files_in": roots[0], "legs": legs,
+                      "commitments_equal_the_garblers_and_outputs_select": ok}), flush=True)
+    return 0 if ok else 1
+
+
 def driver(a):
     os.makedirs(a.out, exist_ok=True)
-    log_f = open(os.path.join(a.out, "commit_rate.log"), "w")
+    log_f = open(os.path.join(a.out, "evaluator_rate.log" if a.evaluator else "commit_rate.log"), "w")
     results, stopped = [], None
 
     def step(name, seconds, extra):
         nonlocal stopped
         if stopped:
             return None
-        cmd = ["timeout", "-k", "10", str(seconds), sys.executable, os.path.relpath(os.path.abspath(__file__), ROOT), "--child", name, "--threads", str(a.threads), "--kernel-gib", str(a.kernel_gib)] + extra
+        cmd = ["timeout", "-k", "10", str(seconds), sys.executable, os.path.relpath(os.path.abspath(__file__), ROOT), "--child", name, "--threads", str(a.threads), "--kernel-gib", str(a.kernel_gib),
+               "--resident-instances", str(a.resident_instances), "--rounds", str(a.rounds)] + extra
         log_f.write("$ " + " ".join(["python"] + cmd[5:]) + "\n"); log_f.flush()
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=log_f, text=True, cwd=ROOT)
         log_f.write(p.stdout); log_f.flush()
@@ -185,9 +295,15 @@ def driver(a):
                 s = summary.setdefault(str(r["instances"]), {k: [] for k in r["legs"]})
                 for k, v in r["legs"].items():
                     s[k].append(v["gates_per_s"])
-        json.dump({"results": results, "gates_per_s_by_instances": summary, "stopped": stopped}, open(os.path.join(a.out, "commit_rate.json"), "w"), indent=1)
+        json.dump({"results": results, "gates_per_s_by_instances": summary, "stopped": stopped}, open(os.path.join(a.out, "evaluator_rate.json" if a.evaluator else "commit_rate.json"), "w"), indent=1)
         return summary
 
+    if a.evaluator:
+        step("resident", 600, [])
+        step("evaluate", 600, ["--batch", str(a.evaluate_instances)])
+        save()
+        print(json.dumps({"results": results, "stopped": stopped}))
+        return 1 if stopped else 0
     step("kernel", 300, [])
     check = step("check", a.leg_seconds, [])
     if not a.no_file_check:
@@ -222,8 +338,11 @@ if __name__ == "__main__":
     ap.add_argument("--leg-seconds", type=int, default=1500)  # a 1 024-instance round: ~900 s of CBC-MAC leg alone
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "commit_blake3"))
     ap.add_argument("--no-file-check", action="store_true")
-    ap.add_argument("--child", choices=["kernel", "check", "round", "file"])
+    ap.add_argument("--evaluator", action="store_true")
+    ap.add_argument("--resident-instances", type=int, default=4)
+    ap.add_argument("--evaluate-instances", type=int, default=16)
+    ap.add_argument("--child", choices=["kernel", "check", "round", "file", "resident", "evaluate"])
     ap.add_argument("--batch", type=int, default=64)
     a = ap.parse_args()
     a.threads = max(1, min(16, a.threads))
-    sys.exit({"kernel": child_kernel, "check": child_check, "round": child_round, "file": child_file, None: driver}[a.child](a))
+    sys.exit({"kernel": child_kernel, "check": child_check, "round": child_round, "file": child_file, "resident": child_resident, "evaluate": child_evaluate, None: driver}[a.child](a))
