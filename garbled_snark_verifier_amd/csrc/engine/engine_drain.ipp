@@ -5,51 +5,6 @@
 // sequential D2H copies (the copy engines work beside the kernel), fold each instance's bytes into its CBC-MAC (strictly
 // serial per instance, hence the host: ciphertext_hasher.rs:23-29) and optionally append them to gc_<index>.bin
 // (ciphertext_repository.rs:94-127).
-//
-// The drain machinery (copy streams, pinned chunk buffers, the per-instance MAC states) lives in the session, so that a plan can
-// be garbled in SLICES of consecutive calls (gsv_session_garble_streaming_calls): the MACs chain from slice to slice and the
-// page-locked buffers are set up once.
-struct gsv_drain {
-  // Many host threads are wanted for the MACs (one serial chain per instance) but only a few D2H copies should be in
-  // flight at once: measured on the MI355X box, 128 concurrent copy streams move 9 GB/s where a handful move 22 GB/s
-  // (and the number of STREAMS matters as much as the number of copies: the copies share a small pool of streams).
-  struct CopyGate {
-    std::mutex mu; std::condition_variable cv; std::vector<hipStream_t> idle;
-    hipStream_t acquire() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !idle.empty(); }); hipStream_t st = idle.back(); idle.pop_back(); return st; }
-    void release(hipStream_t st) { { std::lock_guard<std::mutex> lk(mu); idle.push_back(st); } cv.notify_one(); }
-  } copy_gate;
-  std::vector<Stream> copy_streams;  // (copy_gate hands them out)
-  // Instances whose MAC chains one worker advances side by side: four (AES-NI, CbcMacHost::update_interleaved) or, on hosts with
-  // VAES + AVX-512 and sessions with at least 128 instances (eight workers' worth), sixteen (update_interleaved16_vaes: one core
-  // then MACs ~3 x as many blocks per second, so a node's GPUs need a third of the host cores for their commitments).
-  static constexpr int GROUP_MAX = 16;
-  // CPUs this process may actually use: the visible ones, capped by the container's CPU bandwidth quota (cgroup cpu.max)
-  static size_t usable_cores() {
-    size_t n = std::max<size_t>(1, std::thread::hardware_concurrency());
-    if (FILE* f = std::fopen("/sys/fs/cgroup/cpu.max", "r")) {
-      char q[64] = {0}; double per = 0;
-      if (std::fscanf(f, "%63s %lf", q, &per) == 2 && std::strcmp(q, "max") != 0 && per > 0) n = std::min<size_t>(n, std::max<size_t>(1, size_t(std::atof(q) / per)));
-      std::fclose(f);
-    }
-    return n;
-  }
-  // One chain per worker while there is a core per instance: a chain alone advances at ~1.1e8 blocks/s, one of four interleaved at
-  // ~0.75e8 — sixteen instances (BASELINE config 5 on one GPU) hashed four to a worker took 40 s for 34.8 s of garbling, their
-  // sixteen chains one per core take 27 s.  More instances than cores: four (AES-NI) or sixteen (VAES, >= 128 instances) per worker.
-  static int group_for(size_t n_inst, int forced) {  // forced: GSV_DRAIN_GROUP, 0 = not set
-    if (forced) return forced;
-    if (n_inst <= usable_cores()) return 1;
-    return CbcMacHost::have_vaes() && n_inst >= 128 ? 16 : 4;
-  }
-  int group = 4;
-  struct Worker {
-    MappedHost<uint8_t> pinned[2][GROUP_MAX];  // two sets of pinned chunk buffers: copy set j+1 while set j is hashed
-    Event done;                   // blocking-sync event: a worker waiting for its copies sleeps instead of spinning on a core
-  };
-  std::vector<Worker> workers;
-  uint64_t chunk = 0;  // records per chunk buffer
-  std::vector<CbcMacHost> macs;
-};
 static int ensure_drain(gsv_session* s, size_t T, uint64_t seg_records, int group) {
   // records per chunk: 16 MiB by default — measured on the MI355X box (tools/d2h_bw.py) a D2H copy stream moves 39-48 GB/s in 4 MiB
   // pieces and 54-57 GB/s from 16 MiB up; the buffers are page-locked once per session, not per call as in round 1
@@ -104,18 +59,6 @@ static int garble_discard(gsv_session* s, uint64_t gate_id_base, size_t c0, size
   return rc;
 }
 
-// Where a drained stream goes (any combination): the per-instance CBC-MAC (AESAccumulatingHash), gc_<index>.bin files, a host callback,
-// the per-instance BLAKE3 tree hash on the device (engine_blake3.ipp) — the one destination for which no ciphertext leaves the device.
-struct DrainSink {
-  uint8_t* hashes = nullptr;           // n_inst x 16: the MAC states after this call
-  const char* dir = nullptr;           // gc_<index>.bin, index = indexes ? indexes[i] : first_index + i
-  uint64_t first_index = 0;
-  gsv_ct_sink_fn fn = nullptr;         // CiphertextHandler::handle over a run of records of one instance
-  void* user = nullptr;
-  uint8_t* b3 = nullptr;               // n_inst x 32: the BLAKE3 digests, written by the call that ends the pass
-  bool host() const { return hashes || dir || fn; }  // the stream is copied to the host
-  bool any() const { return host() || b3; }
-};
 // Garble -> evaluate on the device (gsv_session_garble_evaluate): the evaluator session consumes window k from the garbler's
 // program-order block while the garbler writes window k+1 into the other one of two blocks.
 struct PairState {
@@ -248,6 +191,140 @@ static int ensure_aux(gsv_session* s) {
   return GSV_OK;
 }
 
+// The gate-order buffers a call's pipeline runs over (drain_pipeline.hpp, DrainWorkers): ct_gate and as many further ones as `n_units`
+// drain units (segments of plans, rings of programs) can use.
+static std::vector<void*> drain_gate_buffers(gsv_session* s, size_t n_units, size_t n_inst, uint64_t seg_records, bool want_host) {
+  std::vector<void*> gate_bufs(1, s->ct_gate.get());
+  size_t want = 1;
+  if (seg_records && n_units > 1 && want_host) {  // (BLAKE3 alone: a buffer is free again when the hash kernels of its segment have finished, one serves)
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const size_t buf_bytes = n_inst * size_t(seg_records) * 16;
+    // up to eight buffers, within half of the free memory and 32 GB (allocating device memory takes time too: ~25 GB/s)
+    want = std::min<size_t>(std::min<size_t>(8, 1 + size_t(double(free_b) * 0.5 / double(buf_bytes))), std::max<size_t>(2, size_t(32e9 / double(buf_bytes))));
+    if (s->pass.drain_depth) want = s->pass.drain_depth;
+  }
+  while (1 + s->ct_gate_more.size() < want) {
+    DevBuf q;
+    if (q.alloc(s->ct_gate.bytes()) != hipSuccess) break;  // (every buffer of the pipeline has ct_gate's capacity)
+    s->ct_gate_more.push_back(std::move(q));
+  }
+  for (const DevBuf& q : s->ct_gate_more) if (gate_bufs.size() < want) gate_bufs.push_back(q.get());
+  return gate_bufs;
+}
+static int fail_drain(DrainError e) {
+  switch (e) {
+    case DrainError::FileWrite: return fail(GSV_ERR_INVALID, "short write to a gc file");
+    case DrainError::Sink: return fail(GSV_ERR_INVALID, "the ciphertext sink reported an error");
+    case DrainError::B3Order: return fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
+    default: return fail(GSV_ERR_DEVICE, "device copy failed while draining ciphertexts");
+  }
+}
+// What the device loops of one garble_streaming_pass share
+struct DrainPass {
+  gsv_session *s, *ev;             // ev: the evaluator of a garble || evaluate pair, or null
+  uint64_t gate_id_base;
+  size_t pw0, n_inst;              // plans: the first window of this call; instances whose streams leave the device
+  uint64_t seg_records;            // records between two instances in a gate-order buffer
+  bool want_drain, want_b3;        // finished segments are brought into gate order; ... and hashed there
+  std::vector<void*> gate_bufs;
+  DrainWorkers& workers; B3Absorbers* b3; DrainStats& stats;
+  hipStream_t gs;                  // the stream the garbler's windows are launched on
+  hipEvent_t device_done;          // not null: the host thread sleeps on this blocking-sync event instead of spinning in hipStreamSynchronize
+  std::chrono::steady_clock::time_point t_last_pub;  // ring diagnostics: the last publication of the host's position ...
+  double worst_gap;                                  // ... and the longest interval between two
+  void* gate() const { return gate_bufs[workers.next_buffer()]; }  // the gate-order buffer the next segment goes to
+  bool wait_device(hipStream_t st) const { return device_done ? hipEventRecord(device_done, st) == hipSuccess && hipEventSynchronize(device_done) == hipSuccess : hipStreamSynchronize(st) == hipSuccess; }
+  void b3_submit(uint32_t groups) { if (b3) b3->submit(s->b3->pinned.get(), n_inst * size_t(groups) * 32, groups); }
+};
+// One window of a plan: launched (in a pair: handed to the evaluator as well), then drained segment by segment while it runs.
+static int drain_plan_window(DrainPass& p, size_t w) {
+  gsv_session *const s = p.s, *const ev = p.ev;
+  const hipStream_t gs = p.gs;
+  DrainStats& st = p.stats;
+  void* block = s->CT.get();
+  const int b = int(w & 1);
+  if (ev) {
+    // window w goes to block w & 1; the evaluator must be done with what that block held (window w - 2)
+    block = b ? s->ct_alt.get() : s->CT.get();
+    if (w >= p.pw0 + 2 && hipStreamWaitEvent(gs, s->pair->evaluated[b].get(), 0) != hipSuccess) return fail(GSV_ERR_DEVICE, "hipStreamWaitEvent failed");
+  }
+  int rc = launch_plan_window(s, w, p.gate_id_base, false, block, gs);
+  if (rc != GSV_OK) return rc;
+  if (ev) {
+    if (hipEventRecord(s->pair->garbled[b].get(), gs) != hipSuccess || hipStreamWaitEvent(s->pair->stream.get(), s->pair->garbled[b].get(), 0) != hipSuccess) return fail(GSV_ERR_DEVICE, "event hand-over failed");
+    rc = launch_plan_window(ev, w, p.gate_id_base, true, block, s->pair->stream.get());
+    if (rc != GSV_OK) return rc;
+    if (hipEventRecord(s->pair->evaluated[b].get(), s->pair->stream.get()) != hipSuccess) return fail(GSV_ERR_DEVICE, "hipEventRecord failed");
+  }
+  // The window is running.  Its segments leave the device one after the other, in stream order, each as soon as every call of it
+  // has completed for every instance group: the host follows the completion flags of the running launch (a page-locked copy,
+  // refreshed through a side stream), brings the finished segment into gate order with a gather kernel on that side stream — the
+  // session's schedule leaves it a few CUs — and hands it to the workers, while the window goes on garbling.
+  const Schedule::Window& win = s->sched.windows[w];
+  bool window_done = false;
+  for (uint32_t q = win.seg0; p.want_drain && q < win.seg1; ++q) {
+    const Schedule::Segment& sg = s->sched.segments[q];
+    const bool last = q + 1 == win.seg1;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!last && (rc = wait_calls_done(s, w, sg.call0, sg.call1, &window_done, gs)) != GSV_OK) return rc;
+    if (last && !window_done) {
+      // the last segment ends with the window: sleep on the stream (on a blocking-sync event when the workers own the cores)
+      if (!p.wait_device(gs)) return fail(GSV_ERR_DEVICE, "kernel failed");
+      window_done = true;
+    }
+    st.t_wait_device += drain_secs(t0);
+    const double waited = p.workers.wait_buffer();  // the gate-order buffer this segment goes to is free again
+    st.t_wait_drain += waited;
+    const auto tg = std::chrono::steady_clock::now();
+    rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, p.seg_records, 0, block, p.gate(), s->aux_stream.get());
+    if (rc != GSV_OK) return rc;
+    uint32_t b3_groups = 0;  // the hash kernels follow the gather on the side stream; the buffer is free again when they have finished
+    if (p.want_b3 && (rc = b3_segment(*s->b3, p.gate(), p.seg_records, sg.n_ct, s->aux_stream.get(), &b3_groups)) != GSV_OK) return rc;
+    if (hipStreamSynchronize(s->aux_stream.get()) != hipSuccess) return fail(GSV_ERR_DEVICE, "ciphertext gather failed");
+    p.b3_submit(b3_groups);
+    st.t_gather += drain_secs(tg);
+    if (s->ct_ring) {
+      __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);  // the calls whose blocks overlap this segment's may write now
+      const double gap = drain_secs(p.t_last_pub);
+      if (gap > p.worst_gap) {
+        p.worst_gap = gap;
+        char buf[256];
+        std::snprintf(buf, sizeof buf, "longest interval between two positions %.2f s, before segment %u (calls [%u, %u)): %.2f s waiting for its calls, %.2f s for a free gate-order buffer, %.2f s gathering", gap, q,
+                      sg.call0, sg.call1, std::chrono::duration<double>(tg - t0).count() - waited, waited, drain_secs(tg));
+        s->ring_diag = buf;
+      }
+      p.t_last_pub = std::chrono::steady_clock::now();
+    }
+    st.drained_records += sg.n_ct;
+    p.workers.push(sg.n_ct, sg.ct0);
+  }
+  if (hipStreamSynchronize(gs) != hipSuccess) return fail(GSV_ERR_DEVICE, "kernel failed");
+  return GSV_OK;
+}
+// One ring of a program session, replays [r0, r1): garbled, gathered into gate order on the engine's stream, handed to the workers.
+static int drain_program_ring(DrainPass& p, uint64_t r0, uint64_t r1) {
+  gsv_session* const s = p.s;
+  const uint64_t n_ct = s->prog().n_ct, n_records = (r1 - r0) * n_ct, base = r0 * n_ct;  // per instance, in this ring; stream index of its first record
+  // ring slots are (replay % ct_cap): a segment starts at a multiple of ct_cap, so its replays sit in slots 0..n_rep-1
+  int rc = launch(s, p.gate_id_base, false, r0, r1 - r0);
+  if (rc != GSV_OK) return rc;
+  p.stats.t_wait_drain += p.workers.wait_buffer();
+  if (gsvk_gather_segment(s->CT.get(), s->ct_stride(), s->dp->ct_pos.as<const uint32_t>(), n_ct, uint32_t(r1 - r0), uint32_t(p.n_inst), p.gate(), p.seg_records, 0, s->e->stream.get()) != 0)
+    return fail(GSV_ERR_DEVICE, "ciphertext gather launch failed");
+  uint32_t b3_groups = 0;
+  if (p.want_b3 && (rc = b3_segment(*s->b3, p.gate(), p.seg_records, n_records, s->e->stream.get(), &b3_groups)) != GSV_OK) return rc;
+  // the workers own the cores when there is one chain per core: this thread then sleeps on a blocking-sync event instead of
+  // spinning in hipStreamSynchronize
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!p.wait_device(s->e->stream.get())) return fail(GSV_ERR_DEVICE, "kernel failed");
+  p.stats.t_wait_device += drain_secs(t0);
+  p.stats.drained_records += n_records;
+  p.b3_submit(b3_groups);
+  p.workers.push(n_records, base);
+  return GSV_OK;
+}
+
 // `ev`: an evaluator session over the same plan / schedule (plan sessions that do not retain the stream): every window is evaluated
 // straight from the garbler's device block while the next window is garbled.
 static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c0, size_t c1, const DrainSink& sink, int n_threads, gsv_session* ev) {
@@ -300,306 +377,47 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   std::vector<CbcMacHost> no_macs;
   if (want_host && (new_pass || s->drain->macs.size() != n_inst)) s->drain->macs.assign(n_inst, CbcMacHost());  // a new pass starts from h = 0; later slices chain
   std::vector<CbcMacHost>& macs = want_host ? s->drain->macs : no_macs;
-  std::vector<FILE*> files(n_inst, nullptr);
-  std::vector<std::string> paths(n_inst);
-  auto close_files = [&]() { for (FILE*& f : files) if (f) { std::fclose(f); f = nullptr; } };
-  // a failed pass must not leave a plausible-looking prefix of a ciphertext file behind
-  auto remove_files = [&]() { if (sink.dir) for (const std::string& q : paths) if (!q.empty()) std::remove(q.c_str()); };
-  if (sink.dir)
-    for (size_t i = 0; i < n_inst; ++i) {
-      paths[i] = std::string(sink.dir) + "/gc_" + std::to_string(sink.first_index + i) + ".bin";
-      files[i] = std::fopen(paths[i].c_str(), new_pass ? "wb" : "ab");
-      if (!files[i]) { close_files(); return fail(GSV_ERR_INVALID, "cannot create " + paths[i]); }
-    }
-  std::atomic<int> err{0};
-  const uint64_t chunk = want_host ? s->drain->chunk : 0;
-  // The drain is a PIPELINE of segments: the device side (garble a window, bring it into gate order in one of `depth` gate-order
-  // buffers) runs ahead of the host side (copy out, CBC-MAC, files, sink) by up to `depth` segments.  A window's ciphertext count is
-  // fixed but its garbling time is not (the ladders and inversions produce a gigabyte of ciphertexts in seconds, the Miller loop in
-  // half a second), while the serial CBC-MAC chain takes the same 0.58 s for every gigabyte: with ONE buffer a pass costs
-  // sum(max(garble_w, mac_w)) — 37.0 s for one instance whose garbling takes 31 s and whose chain takes 27 s — with a few buffers
-  // max(sum garble, sum mac).  Workers are persistent for the call and take the segments strictly in order (an instance's chain must
-  // see its stream in order); a buffer is reused once every worker is done with the segment that held it.
-  std::vector<void*> gate_bufs;
+  GcFiles files;  // (removed again on every return but the last)
+  if (std::string failed; sink.dir && !files.open(sink.dir, sink.first_index, n_inst, new_pass ? "wb" : "ab", &failed)) return fail(GSV_ERR_INVALID, "cannot create " + failed);
+  DrainShape shape;
+  shape.device = s->e->device; shape.n_inst = n_inst; shape.group = GROUP; shape.n_workers = want_host ? T : 0;
+  shape.chunk = want_host ? s->drain->chunk : 0; shape.seg_records = seg_records; shape.blocking_wait = T > 8;
   if (want_drain) {
-    gate_bufs.push_back(s->ct_gate.get());
-    size_t want = 1;
     size_t n_units = size_t((total - first + seg - 1) / seg);  // drain units of this call: segments (plans) or rings
     if (s->plan) { n_units = 0; for (size_t w = pw0; w < pw1; ++w) n_units += s->sched.windows[w].seg1 - s->sched.windows[w].seg0; }
-    if (seg_records && n_units > 1 && want_host) {  // (BLAKE3 alone: a buffer is free again when the hash kernels of its segment have finished, one serves)
-      size_t free_b = 0, total_b = 0;
-      (void)hipMemGetInfo(&free_b, &total_b);
-      const size_t buf_bytes = n_inst * size_t(seg_records) * 16;
-      // up to eight buffers, within half of the free memory and 32 GB (allocating device memory takes time too: ~25 GB/s)
-      want = std::min<size_t>(std::min<size_t>(8, 1 + size_t(double(free_b) * 0.5 / double(buf_bytes))), std::max<size_t>(2, size_t(32e9 / double(buf_bytes))));
-      if (s->pass.drain_depth) want = s->pass.drain_depth;
-    }
-    while (1 + s->ct_gate_more.size() < want) {
-      DevBuf q;
-      if (q.alloc(s->ct_gate.bytes()) != hipSuccess) break;  // (every buffer of the pipeline has ct_gate's capacity)
-      s->ct_gate_more.push_back(std::move(q));
-    }
-    for (const DevBuf& q : s->ct_gate_more) if (gate_bufs.size() < want) gate_bufs.push_back(q.get());
+    shape.gate_bufs = drain_gate_buffers(s, n_units, n_inst, seg_records, want_host);
   }
-  const size_t depth = std::max<size_t>(1, gate_bufs.size());
-  struct Segment { uint64_t n, base; size_t buf; };
-  std::mutex q_mu;
-  std::condition_variable q_cv;
-  std::vector<Segment> segments;          // pushed by the device side, in stream order
-  std::vector<size_t> seg_done;           // per segment: workers that have finished it
-  bool q_closed = false;
-  auto worker_main = [&](size_t t) {
-    if (hipSetDevice(s->e->device) != hipSuccess) { err = 1; }
-    gsv_drain& dr = *s->drain;
-    gsv_drain::Worker& w = dr.workers[t];
-    for (size_t j = 0;; ++j) {
-      Segment sg;
-      {
-        std::unique_lock<std::mutex> lk(q_mu);
-        q_cv.wait(lk, [&] { return j < segments.size() || q_closed; });
-        if (j >= segments.size()) return;
-        sg = segments[j];
-      }
-      const uint64_t n = sg.n, base = sg.base;
-      const uint8_t* const gate = static_cast<const uint8_t*>(gate_bufs[sg.buf]);
-      for (size_t grp = t; grp < n_groups && !err && n; grp += T) {
-        const size_t i0 = grp * GROUP, ng = std::min(GROUP, n_inst - i0);  // instances i0 .. i0+ng-1 advance together
-        // the copies of one chunk set share a stream of the pool (a set holds a slot of the gate from issue to completion)
-        auto copy = [&](uint64_t off, int b) {
-          hipStream_t st = dr.copy_gate.acquire();
-          bool ok = true;
-          for (size_t g = 0; g < ng && ok; ++g)
-            ok = hipMemcpyAsync(w.pinned[b][g].get(), gate + ((i0 + g) * seg_records + off) * 16, std::min(chunk, n - off) * 16, hipMemcpyDeviceToHost, st) == hipSuccess;
-          // many workers: sleep on the blocking-sync event (spinning workers eat the cores the MACs need); a handful of
-          // workers (one instance: the whole-stream check) spin instead, a blocking wait's wake-up latency would be paid per chunk
-          ok = ok && (T > 8 ? hipEventRecord(w.done.get(), st) == hipSuccess && hipEventSynchronize(w.done.get()) == hipSuccess : hipStreamSynchronize(st) == hipSuccess);
-          dr.copy_gate.release(st);
-          return ok;
-        };
-        int b = 0;
-        if (!copy(0, 0)) { err = 1; break; }
-        for (uint64_t off = 0; off < n; off += chunk, b ^= 1) {
-          const uint64_t m = std::min(chunk, n - off);
-          if (want_mac) {
-            CbcMacHost* mp[gsv_drain::GROUP_MAX];
-            const uint8_t* cp[gsv_drain::GROUP_MAX];
-            for (size_t g = 0; g < ng; ++g) { mp[g] = &macs[i0 + g]; cp[g] = w.pinned[b][g].get(); }
-            CbcMacHost::update_many(mp, cp, ng, m);  // sixteen / four chains per step, a ragged last group chain by chain
-          }
-          if (sink.dir)
-            for (size_t g = 0; g < ng; ++g)
-              if (std::fwrite(w.pinned[b][g].get(), 16, m, files[i0 + g]) != m) { err = 2; break; }
-          if (sink.fn && !err)
-            for (size_t g = 0; g < ng; ++g)
-              if (sink.fn(sink.user, i0 + g, base + off, w.pinned[b][g].get(), m) != 0) { err = 3; break; }
-          if (err) break;
-          if (off + chunk < n && !copy(off + chunk, b ^ 1)) { err = 1; break; }
-        }
-      }
-      {
-        std::lock_guard<std::mutex> lk(q_mu);
-        seg_done[j]++;
-      }
-      q_cv.notify_all();
-    }
-  };
-  std::vector<std::thread> workers;
-  if (want_host) for (size_t t = 0; t < T; ++t) workers.emplace_back(worker_main, t);
-  // BLAKE3: the group values of a segment (32 bytes per 2^k chunks and instance) are folded into the instances' hashers by a small pool
-  // of their own, in segment order, off the thread that launches the windows; a task is released when every thread of the pool is done with it.
-  // What the launching thread itself does per segment is copy those values out of the page-locked buffer (b3_submit: 32 B x groups x
-  // instances, a few KiB), which has to happen before the next segment's copy lands there.
-  struct B3Task { std::vector<uint8_t> vals; uint32_t groups = 0; size_t done = 0; };
-  std::mutex b3_mu;
-  std::condition_variable b3_cv;
-  std::vector<std::unique_ptr<B3Task>> b3_tasks;
-  bool b3_closed = false;
-  const size_t B3T = want_b3 ? std::min<size_t>(4, n_inst) : 0;
-  const unsigned b3_k = want_b3 ? s->b3->k : 0;
-  auto b3_main = [&](size_t t) {
-    for (size_t j = 0;; ++j) {
-      B3Task* task;
-      {
-        std::unique_lock<std::mutex> lk(b3_mu);
-        b3_cv.wait(lk, [&] { return j < b3_tasks.size() || b3_closed; });
-        if (j >= b3_tasks.size()) return;
-        task = b3_tasks[j].get();
-      }
-      if (!b3_absorb(*s->b3, task->vals.data(), task->groups, b3_k, t, B3T)) err = 4;
-      std::lock_guard<std::mutex> lk(b3_mu);
-      if (++task->done == B3T) b3_tasks[j].reset();
-    }
-  };
-  std::vector<std::thread> b3_threads;
-  for (size_t t = 0; t < B3T; ++t) b3_threads.emplace_back(b3_main, t);
-  // after the stream the segment's hash kernels ran on has been synchronised: its group values leave the page-locked buffer
-  auto b3_submit = [&](uint32_t groups) {
-    if (!groups) return;
-    std::unique_ptr<B3Task> task(new B3Task());
-    task->groups = groups;
-    task->vals.assign(s->b3->pinned.get(), s->b3->pinned.get() + n_inst * size_t(groups) * 32);
-    { std::lock_guard<std::mutex> lk(b3_mu); b3_tasks.push_back(std::move(task)); }
-    b3_cv.notify_all();
-  };
-  // GSV_DRAIN_STATS=1: where the host thread of the pipeline waits (for a free gate-order buffer = the host side is the slower stage;
-  // for the kernel + gather = the device is), printed once per call
-  const bool stats = s->pass.drain_stats;
-  double t_wait_drain = 0, t_wait_device = 0, t_gather = 0;
-  uint64_t drained_records = 0;
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto secs = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-  // blocks until the segment that last used buffer `b` has been consumed by every worker (segment index = its position in `segments`)
-  auto wait_buffer = [&](size_t n_pushed) {
-    if (!want_host || n_pushed < depth) return;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::unique_lock<std::mutex> lk(q_mu);
-    q_cv.wait(lk, [&] { return seg_done[n_pushed - depth] == T; });
-    t_wait_drain += secs(t0);
-  };
-  auto push_segment = [&](uint64_t n, uint64_t base, size_t buf) {
-    { std::lock_guard<std::mutex> lk(q_mu); segments.push_back(Segment{n, base, buf}); seg_done.push_back(0); }
-    q_cv.notify_all();
-  };
-  auto finish_workers = [&]() {
-    { std::lock_guard<std::mutex> lk(q_mu); q_closed = true; }
-    q_cv.notify_all();
-    const auto t0 = std::chrono::steady_clock::now();
-    for (auto& th : workers) th.join();
-    workers.clear();
-    { std::lock_guard<std::mutex> lk(b3_mu); b3_closed = true; }
-    b3_cv.notify_all();
-    for (auto& th : b3_threads) th.join();
-    b3_threads.clear();
-    t_wait_drain += secs(t0);
-  };
-  size_t n_pushed = 0;
-  auto t_last_pub = std::chrono::steady_clock::now();
-  double worst_gap = 0;
+  // The pools are declared after everything their threads use — the gate-order buffers, `macs`, `files`: they are joined first, however
+  // this function returns.  Their threads run members of the pools (drain_pipeline.hpp), never a lambda over the locals here.
+  std::atomic<DrainError> err{DrainError::None};
+  DrainWorkers workers(s->drain.get(), shape, sink, macs, files, err);
+  B3Stream* const b3s = want_b3 ? s->b3.get() : nullptr;
+  B3Absorbers absorbers(want_b3 ? std::min<size_t>(4, n_inst) : 0, [b3s](const uint8_t* vals, uint32_t groups, size_t t, size_t n) { return b3_absorb(*b3s, vals, groups, b3s->k, t, n); }, err);
+  DrainStats stats;
   s->ring_diag.clear();
-  Event device_done_owner;
-  if (want_host && T + 1 > gsv_drain::usable_cores()) (void)device_done_owner.create(hipEventBlockingSync | hipEventDisableTiming);
-  const hipEvent_t device_done = device_done_owner.get();
-  int rc = GSV_OK;
+  Event device_done;
+  if (want_host && T + 1 > gsv_drain::usable_cores()) (void)device_done.create(hipEventBlockingSync | hipEventDisableTiming);
   // The stream the garbler's windows are launched on: the engine's, or — a garble || evaluate pair with CU-masked streams (ensure_pair) —
   // the pair's masked garbler stream, which first waits for whatever the engine's stream still holds (input staging, the memsets above).
   hipStream_t gs = s->e->stream.get();
   if (ev && s->pair->gstream) {
     gs = s->pair->gstream.get();
-    if (hipEventRecord(s->pair->ready.get(), s->e->stream.get()) != hipSuccess || hipStreamWaitEvent(gs, s->pair->ready.get(), 0) != hipSuccess) { finish_workers(); close_files(); return fail(GSV_ERR_DEVICE, "stream hand-over failed"); }
+    if (hipEventRecord(s->pair->ready.get(), s->e->stream.get()) != hipSuccess || hipStreamWaitEvent(gs, s->pair->ready.get(), 0) != hipSuccess) return fail(GSV_ERR_DEVICE, "stream hand-over failed");
   }
-  if (hipEventRecord(s->ev0.get(), gs) != hipSuccess) { finish_workers(); close_files(); return fail(GSV_ERR_DEVICE, "hipEventRecord failed"); }
-  for (uint64_t r0 = first; r0 < total && rc == GSV_OK; r0 += seg) {
-    const uint64_t r1 = std::min(total, r0 + seg);
-    uint64_t n_records, base;  // per instance, in this segment; stream index of its first record
-    if (s->plan) {
-      const size_t w = size_t(r0);
-      void* block = s->CT.get();
-      if (ev) {
-        // window w goes to block w & 1; the evaluator must be done with what that block held (window w - 2)
-        const int b = int(w & 1);
-        block = b ? s->ct_alt.get() : s->CT.get();
-        if (w >= pw0 + 2 && hipStreamWaitEvent(gs, s->pair->evaluated[b].get(), 0) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "hipStreamWaitEvent failed"); break; }
-      }
-      rc = launch_plan_window(s, w, gate_id_base, false, block, gs);
-      if (rc != GSV_OK) break;
-      if (ev) {
-        const int b = int(w & 1);
-        if (hipEventRecord(s->pair->garbled[b].get(), gs) != hipSuccess || hipStreamWaitEvent(s->pair->stream.get(), s->pair->garbled[b].get(), 0) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "event hand-over failed"); break; }
-        rc = launch_plan_window(ev, w, gate_id_base, true, block, s->pair->stream.get());
-        if (rc != GSV_OK) break;
-        if (hipEventRecord(s->pair->evaluated[b].get(), s->pair->stream.get()) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "hipEventRecord failed"); break; }
-      }
-      // The window is running.  Its segments leave the device one after the other, in stream order, each as soon as every call of it
-      // has completed for every instance group: the host follows the completion flags of the running launch (a page-locked copy,
-      // refreshed through a side stream), brings the finished segment into gate order with a gather kernel on that side stream — the
-      // session's schedule leaves it a few CUs — and hands it to the workers, while the window goes on garbling.
-      const Schedule::Window& win = s->sched.windows[w];
-      n_records = win.n_ct;
-      base = win.ct0;
-      if (want_drain) {
-        bool window_done = false;
-        for (uint32_t q = win.seg0; q < win.seg1 && rc == GSV_OK; ++q) {
-          const Schedule::Segment& sg = s->sched.segments[q];
-          const bool last = q + 1 == win.seg1;
-          const auto t0 = std::chrono::steady_clock::now();
-          const double drain_before = t_wait_drain;
-          if (!last) rc = wait_calls_done(s, w, sg.call0, sg.call1, &window_done, gs);
-          if (rc != GSV_OK) break;
-          if (last && !window_done) {
-            // the last segment ends with the window: sleep on the stream (on a blocking-sync event when the workers own the cores)
-            const bool ok = device_done ? hipEventRecord(device_done, gs) == hipSuccess && hipEventSynchronize(device_done) == hipSuccess : hipStreamSynchronize(gs) == hipSuccess;
-            if (!ok) { rc = fail(GSV_ERR_DEVICE, "kernel failed"); break; }
-            window_done = true;
-          }
-          t_wait_device += secs(t0);
-          wait_buffer(n_pushed);  // the gate-order buffer this segment goes to is free again
-          const auto tg = std::chrono::steady_clock::now();
-          rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, seg_records, 0, block, gate_bufs[n_pushed % depth], s->aux_stream.get());
-          if (rc != GSV_OK) break;
-          uint32_t b3_groups = 0;  // the hash kernels follow the gather on the side stream; the buffer is free again when they have finished
-          if (want_b3 && (rc = b3_segment(*s->b3, gate_bufs[n_pushed % depth], seg_records, sg.n_ct, s->aux_stream.get(), &b3_groups)) != GSV_OK) break;
-          if (hipStreamSynchronize(s->aux_stream.get()) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "ciphertext gather failed"); break; }
-          if (want_b3) b3_submit(b3_groups);
-          t_gather += secs(tg);
-          if (s->ct_ring) {
-            __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);  // the calls whose blocks overlap this segment's may write now
-            const double gap = secs(t_last_pub);
-            if (gap > worst_gap) {
-              worst_gap = gap;
-              char buf[256];
-              std::snprintf(buf, sizeof buf, "longest interval between two positions %.2f s, before segment %u (calls [%u, %u)): %.2f s waiting for its calls, %.2f s for a free gate-order buffer, %.2f s gathering", gap, q,
-                            sg.call0, sg.call1, std::chrono::duration<double>(tg - t0).count() - (t_wait_drain - drain_before), t_wait_drain - drain_before, secs(tg));
-              s->ring_diag = buf;
-            }
-            t_last_pub = std::chrono::steady_clock::now();
-          }
-          drained_records += sg.n_ct;
-          if (want_host) push_segment(sg.n_ct, sg.ct0, n_pushed % depth);
-          ++n_pushed;
-        }
-        if (rc != GSV_OK) break;
-      }
-      if (hipStreamSynchronize(gs) != hipSuccess) { rc = fail(GSV_ERR_DEVICE, "kernel failed"); break; }
-      continue;
-    } else {
-      // ring slots are (replay % ct_cap): a segment starts at a multiple of ct_cap, so its replays sit in slots 0..n_rep-1
-      rc = launch(s, gate_id_base, false, r0, r1 - r0);
-      if (rc != GSV_OK) break;
-      wait_buffer(n_pushed);
-      n_records = (r1 - r0) * n_ct;
-      base = r0 * n_ct;
-      if (gsvk_gather_segment(s->CT.get(), s->ct_stride(), s->dp->ct_pos.as<const uint32_t>(), n_ct, uint32_t(r1 - r0), uint32_t(n_inst), gate_bufs[n_pushed % depth], seg_records, 0, s->e->stream.get()) != 0) {
-        rc = fail(GSV_ERR_DEVICE, "ciphertext gather launch failed");
-        break;
-      }
-    }
-    uint32_t b3_groups = 0;
-    if (want_b3 && (rc = b3_segment(*s->b3, gate_bufs[n_pushed % depth], seg_records, n_records, s->e->stream.get(), &b3_groups)) != GSV_OK) break;
-    {
-      // the workers own the cores when there is one chain per core: this thread then sleeps on a blocking-sync event instead of
-      // spinning in hipStreamSynchronize
-      const auto t0 = std::chrono::steady_clock::now();
-      const bool ok = device_done ? hipEventRecord(device_done, s->e->stream.get()) == hipSuccess && hipEventSynchronize(device_done) == hipSuccess : hipStreamSynchronize(s->e->stream.get()) == hipSuccess;
-      if (!ok) { rc = fail(GSV_ERR_DEVICE, "kernel failed"); break; }
-      t_wait_device += secs(t0);
-    }
-    drained_records += n_records;
-    if (want_b3) b3_submit(b3_groups);
-    if (want_host) push_segment(n_records, base, n_pushed % depth);
-    if (want_drain) ++n_pushed;
-  }
+  if (hipEventRecord(s->ev0.get(), gs) != hipSuccess) return fail(GSV_ERR_DEVICE, "hipEventRecord failed");
+  DrainPass p{s, ev, gate_id_base, pw0, n_inst, seg_records, want_drain, want_b3, shape.gate_bufs, workers, want_b3 ? &absorbers : nullptr, stats, gs, device_done.get(), std::chrono::steady_clock::now(), 0.0};
+  int rc = GSV_OK;
+  for (uint64_t r0 = first; r0 < total && rc == GSV_OK; r0 += seg) rc = s->plan ? drain_plan_window(p, size_t(r0)) : drain_program_ring(p, r0, std::min(total, r0 + seg));
   if (s->ct_ring && rc != GSV_OK) {
     // a failed pass: calls of the running window may still wait for room in the ring — let them run out (the results are discarded)
     __atomic_store_n(s->sd.ct_pos.get(), ~0ull, __ATOMIC_RELEASE);
     (void)hipStreamSynchronize(gs);
   }
-  finish_workers();
+  const auto t_finish = std::chrono::steady_clock::now();
+  workers.finish(); absorbers.finish();
+  stats.t_wait_drain += drain_secs(t_finish);
   if (ev && hipStreamSynchronize(s->pair->stream.get()) != hipSuccess && rc == GSV_OK) rc = fail(GSV_ERR_DEVICE, "evaluation kernel failed");
-  if (stats) {
-    const double tot = secs(t_begin);
-    std::fprintf(stderr, "drain: %.2f s for %zu instances x %llu records (%.1f GB/s), %zu MAC workers x %zu chains, %zu gate-order buffers; host thread waited %.2f s for drains, %.2f s for the device and %.2f s for the gathers of running windows\n", tot, n_inst,
-                 (unsigned long long)drained_records, double(drained_records) * double(n_inst) * 16e-9 / tot, T, GROUP, depth, t_wait_drain, t_wait_device, t_gather);
-  }
+  if (s->pass.drain_stats) stats.print(n_inst, T, GROUP, workers.depth());
   if (rc == GSV_OK && s->plan) {
     (void)hipEventRecord(s->ev1.get(), gs);  // (every window on gs has been synchronised: the output gather on the engine's stream follows safely)
     if (c1 == s->plan->calls.size()) {
@@ -607,15 +425,14 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
       if (rc == GSV_OK && ev) rc = gather_plan_outputs(ev, true);
     } else { s->ran = true; s->last_eval = false; }
   }
-  close_files();
   if (rc == GSV_OK && s->plan) rc = check_plan_error(s);
   if (rc == GSV_OK && ev) rc = check_plan_error(ev);
-  if (rc == GSV_OK && err) rc = fail(err == 2 ? GSV_ERR_INVALID : err == 3 ? GSV_ERR_INVALID : err == 4 ? GSV_ERR_INVALID : GSV_ERR_DEVICE,
-                                     err == 2 ? "short write to a gc file" : err == 3 ? "the ciphertext sink reported an error" : err == 4 ? "internal: BLAKE3 group values out of order" : "device copy failed while draining ciphertexts");
+  if (rc == GSV_OK && err != DrainError::None) rc = fail_drain(err);
   // the call that ends the pass finishes the BLAKE3 streams: pending chunk values and the last chunks come to the host (<= 1 KiB + 32 B x 2^k per instance)
   if (rc == GSV_OK && want_b3 && (!s->plan || c1 == s->plan->calls.size())) rc = b3_finish(*s->b3, s->e->stream.get(), sink.b3);
-  if (rc != GSV_OK) { remove_files(); return rc; }
+  if (rc != GSV_OK) return rc;
   if (want_mac) for (size_t i = 0; i < n_inst; ++i) macs[i].digest(sink.hashes + 16 * i);
+  files.keep();
   s->garbled = true;
   return GSV_OK;
 }
@@ -677,24 +494,23 @@ int gsv_session_garble_streaming(gsv_session* s, uint64_t gate_id_base, const ch
   if (dir && !hashes) return fail(GSV_ERR_INVALID, "null hash buffer");
   return garble_streaming_range(s, gate_id_base, 0, s->plan ? s->plan->calls.size() : 1, mac_file_sink(hashes, dir, first_index), n_threads);
 }
-// a slice must start a new pass or continue where the previous one ended
-static int check_slice(gsv_session* s, uint64_t first_call, uint64_t n_calls) {
+// One slice of a plan session's pass, calls [first_call, first_call + n_calls).  Wires, gate ids and the MAC states continue from slice
+// to slice: a slice either starts a new pass or continues where the previous one ended.  `arg_error`: what the entry point found wrong
+// with its own arguments (reported behind a bad call range, as ever).
+static int garble_slice(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const DrainSink& k, int n_threads, const char* arg_error = nullptr) {
   if (!s || !s->plan) return fail(GSV_ERR_INVALID, "null session / not a plan session");
   if (first_call > s->plan->calls.size() || n_calls > s->plan->calls.size() - first_call) return fail(GSV_ERR_INVALID, "call range outside the plan");
-  // wires, gate ids and the MAC states continue from slice to slice: a slice either starts a new pass or continues the previous one
   if (first_call != 0 && first_call != s->next_call && !s->unchecked_slices)
     return fail(GSV_ERR_INVALID, "slice starts at call " + std::to_string(first_call) + " but the previous slice ended at call " + std::to_string(s->next_call) +
                                      " (gsv_session_set_unchecked_slices for timing runs)");
-  return GSV_OK;
+  if (arg_error) return fail(GSV_ERR_INVALID, arg_error);
+  const int rc = garble_streaming_range(s, gate_id_base, size_t(first_call), size_t(first_call + n_calls), k, n_threads);
+  if (rc == GSV_OK) { s->next_call = first_call + n_calls; s->garbled = s->plan_retain && s->next_call == s->plan->calls.size(); }
+  return rc;
 }
 int gsv_session_garble_streaming_calls(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* dir, uint64_t first_index, int n_threads, uint8_t* hashes) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
-  int rc = check_slice(s, first_call, n_calls);
-  if (rc) return rc;
-  if (dir && !hashes) return fail(GSV_ERR_INVALID, "null hash buffer");
-  rc = garble_streaming_range(s, gate_id_base, size_t(first_call), size_t(first_call + n_calls), mac_file_sink(hashes, dir, first_index), n_threads);
-  if (rc == GSV_OK) { s->next_call = first_call + n_calls; s->garbled = s->plan_retain && s->next_call == s->plan->calls.size(); }
-  return rc;
+  return garble_slice(s, gate_id_base, first_call, n_calls, mac_file_sink(hashes, dir, first_index), n_threads, dir && !hashes ? "null hash buffer" : nullptr);
 }
 // Either commitment or both (include/gsv_engine.h, "BLAKE3 commitments"): the CBC-MAC on the host's cores, BLAKE3 where the ciphertexts are.
 int gsv_session_garble_streaming_commit(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* dir, uint64_t first_index, int n_threads,
@@ -708,11 +524,7 @@ int gsv_session_garble_streaming_commit(gsv_session* s, uint64_t gate_id_base, u
     return garble_streaming_range(s, gate_id_base, 0, 1, k, n_threads);
   }
   if (first_call == 0 && n_calls == 0) n_calls = s->plan->calls.size();
-  int rc = check_slice(s, first_call, n_calls);
-  if (rc) return rc;
-  rc = garble_streaming_range(s, gate_id_base, size_t(first_call), size_t(first_call + n_calls), k, n_threads);
-  if (rc == GSV_OK) { s->next_call = first_call + n_calls; s->garbled = s->plan_retain && s->next_call == s->plan->calls.size(); }
-  return rc;
+  return garble_slice(s, gate_id_base, first_call, n_calls, k, n_threads);
 }
 // The generic CiphertextHandler: every drained run of records is handed to `sink` (gate order, per instance in stream order).
 int gsv_session_garble_streaming_sink(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, gsv_ct_sink_fn sink, void* user, int n_threads, uint8_t* hashes) {
@@ -722,11 +534,7 @@ int gsv_session_garble_streaming_sink(gsv_session* s, uint64_t gate_id_base, uin
   k.hashes = hashes; k.fn = sink; k.user = user;
   if (!s->plan) return garble_streaming_range(s, gate_id_base, 0, 1, k, n_threads);
   if (first_call == 0 && n_calls == 0) n_calls = s->plan->calls.size();
-  int rc = check_slice(s, first_call, n_calls);
-  if (rc) return rc;
-  rc = garble_streaming_range(s, gate_id_base, size_t(first_call), size_t(first_call + n_calls), k, n_threads);
-  if (rc == GSV_OK) { s->next_call = first_call + n_calls; s->garbled = s->plan_retain && s->next_call == s->plan->calls.size(); }
-  return rc;
+  return garble_slice(s, gate_id_base, first_call, n_calls, k, n_threads);
 }
 // Garble and evaluate side by side on the device (examples/groth16_garble.rs:171-230: the garbler thread feeds the evaluator thread
 // through a channel; here window k of the garbler's device block is evaluated while window k+1 is garbled).
@@ -745,20 +553,4 @@ int gsv_session_garble_evaluate(gsv_session* gs, gsv_session* es, uint64_t gate_
   int rc = garble_streaming_range(gs, gate_id_base, 0, gs->plan->calls.size(), k, n_threads, es);
   if (rc == GSV_OK) { gs->next_call = gs->plan->calls.size(); gs->garbled = false; }
   return rc;
-}
-int gsv_plan_call_info(const gsv_plan* p, uint64_t call, uint64_t* gate_offset, uint64_t* n_gates, uint64_t* ct_offset, uint64_t* n_ciphertexts, uint64_t* n_steps) {
-  if (!p || call >= p->calls.size()) return fail(GSV_ERR_INVALID, "null plan / call index out of range");
-  const PlanCall& c = p->calls[size_t(call)];
-  if (gate_offset) *gate_offset = c.gid_off;
-  if (n_gates) *n_gates = c.prog->prog.n_gates;
-  if (ct_offset) *ct_offset = c.ct_off;
-  if (n_ciphertexts) *n_ciphertexts = c.prog->prog.n_ct;
-  if (n_steps) *n_steps = c.prog->prog.n_steps;
-  return GSV_OK;
-}
-int gsv_plan_call_record_form(const gsv_plan* p, uint64_t call, uint32_t* and_terms) {
-  if (!p || !and_terms || call >= p->calls.size()) return fail(GSV_ERR_INVALID, "null argument / call index out of range");
-  { int rc = program_ready(p->calls[size_t(call)].prog); if (rc) return rc; }
-  *and_terms = p->calls[size_t(call)].prog->prog.and_terms;
-  return GSV_OK;
 }

@@ -25,6 +25,7 @@
 
 #include "../../../include/gsv_engine.h"
 #include "../gadgets/circuits.hpp"
+#include "drain_pipeline.hpp"
 #include "hip_owned.hpp"
 #include "host_crypto.hpp"
 #include "kernel_api.h"
@@ -195,7 +196,6 @@ struct gsv_engine {
   ~gsv_engine() { (void)hipSetDevice(device); }  // ... then te, then the stream
 };
 
-struct gsv_drain;
 struct PairState;
 struct B3Stream;
 struct gsv_session {
@@ -262,7 +262,7 @@ struct gsv_session {
   std::vector<DevBuf> ct_gate_more;    // further gate-order buffers of the drain pipeline (ct_gate is the first)
   DevBuf ct_alt;                       // garble -> evaluate on the device: the second program-order ciphertext block
   std::unique_ptr<PairState> pair;     // ... and its stream / events (created on first use)
-  gsv_session();   // (both in engine_drain.ipp, where gsv_drain, PairState and B3Stream are complete)
+  gsv_session();   // (both in engine_drain.ipp, where PairState and B3Stream are complete)
   ~gsv_session();  // selects the device and synchronises the engine's stream; the members then release what they hold
   uint64_t ct_stride() const { return plan ? (plan_retain ? plan->n_ct : plan_max_block) : ct_cap * p->prog.n_ct; }  // n_ct does not depend on the variant
 };

@@ -799,3 +799,19 @@ int gsv_plan_load(const char* path, gsv_engine* e, gsv_plan** out) {
   return GSV_OK;
   GSV_CATCH
 }
+int gsv_plan_call_info(const gsv_plan* p, uint64_t call, uint64_t* gate_offset, uint64_t* n_gates, uint64_t* ct_offset, uint64_t* n_ciphertexts, uint64_t* n_steps) {
+  if (!p || call >= p->calls.size()) return fail(GSV_ERR_INVALID, "null plan / call index out of range");
+  const PlanCall& c = p->calls[size_t(call)];
+  if (gate_offset) *gate_offset = c.gid_off;
+  if (n_gates) *n_gates = c.prog->prog.n_gates;
+  if (ct_offset) *ct_offset = c.ct_off;
+  if (n_ciphertexts) *n_ciphertexts = c.prog->prog.n_ct;
+  if (n_steps) *n_steps = c.prog->prog.n_steps;
+  return GSV_OK;
+}
+int gsv_plan_call_record_form(const gsv_plan* p, uint64_t call, uint32_t* and_terms) {
+  if (!p || !and_terms || call >= p->calls.size()) return fail(GSV_ERR_INVALID, "null argument / call index out of range");
+  { int rc = program_ready(p->calls[size_t(call)].prog); if (rc) return rc; }
+  *and_terms = p->calls[size_t(call)].prog->prog.and_terms;
+  return GSV_OK;
+}
