@@ -1,6 +1,6 @@
 // Part of engine.cpp: BLAKE3 commitments — the host hasher behind gsv_blake3_*, and the device tree hash of n equally long streams
 // that arrive in segments of a gate-order buffer (blake3_device.hpp), shared by the streaming drain (engine_drain.ipp), the streaming
-// evaluators and gsv_session_ciphertext_blake3 (engine_evaluate.ipp: the latter feeds ranges of the resident program-order stream) and
+// evaluators (engine_evaluate.ipp), gsv_session_ciphertext_blake3 (engine_readback.ipp: it feeds ranges of the resident program-order stream) and
 // gsv_engine_blake3_streams.
 //
 // Split (DESIGN.md §3 "Commitment stage"): a stream of L records has N = max(1, ceil(L / 64)) chunks.  The device hashes chunks

@@ -33,6 +33,7 @@
 #include "plan_builder.hpp"
 #include "schedule.hpp"
 #include "program.hpp"
+#include "upload_pipeline.hpp"
 
 using namespace gsv;
 
