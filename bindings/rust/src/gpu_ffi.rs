@@ -150,6 +150,15 @@ extern "C" {
     pub fn gsv_session_ciphertext_blake3(s: *mut GsvSession, digests: *mut u8) -> c_int;
     pub fn gsv_blake3_file(path: *const c_char, out: *mut u8) -> c_int;
     pub fn gsv_engine_blake3_streams(e: *mut GsvEngine, data: *const u8, n_streams: u64, records_per_stream: u64, segment_records: *const u64, n_segments: u64, digests: *mut u8) -> c_int;
+    // BLAKE3 outboards (gc_<i>.b3o: one level of the tree, this project's own format, not Bao) and verified receiving.
+    // A return of GSV_ERR_MISMATCH (5) names the place through gsv_session_mismatch_info.  gsv_engine_blake3_files takes arrays of paths
+    // (`const char* const*`): declare it where it is used, as `*const *const c_char`.
+    pub fn gsv_blake3_outboard_root(outboard: *const u8, n_bytes: u64, last_chunk: *const u8, last_chunk_bytes: u64, out: *mut u8) -> c_int;
+    pub fn gsv_blake3_file_outboard(path: *const c_char, k: u32, outboard_path: *const c_char, out: *mut u8) -> c_int;
+    pub fn gsv_session_garble_streaming_commit_outboard(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, dir: *const c_char, first_index: u64, n_threads: c_int, cbcmac_hashes: *mut u8, blake3_digests: *mut u8, outboard_dir: *const c_char) -> c_int;
+    pub fn gsv_session_evaluate_streaming_verified(s: *mut GsvSession, gate_id_base: u64, dir: *const c_char, indexes: *const u64, first_index: u64, outboard_dir: *const c_char, expected: *const u8, expected_len: u64, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int;
+    pub fn gsv_session_mismatch_info(s: *const GsvSession, instance: *mut u64, group: *mut u64, first_record: *mut u64) -> c_int;
+    pub fn gsv_session_windows_launched(s: *const GsvSession, n: *mut u64) -> c_int;
 }
 
 pub fn chk(rc: c_int) {

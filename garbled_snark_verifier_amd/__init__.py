@@ -22,7 +22,8 @@ import numpy as np
 from . import build as _build
 
 __all__ = ["GsvError", "lib", "Program", "Engine", "Session", "CircuitBuilder", "StreamingResult", "labels_from_seed", "GATE_NAMES", "cbcmac", "cbcmac_many",
-           "write_gc_file", "read_gc_file", "gc_file_name", "blake3", "blake3_file", "blake3_streams", "Blake3"]
+           "write_gc_file", "read_gc_file", "gc_file_name", "blake3", "blake3_file", "blake3_streams", "Blake3",
+           "CiphertextMismatch", "outboard_file_name", "blake3_outboard_root", "blake3_file_outboard", "blake3_files"]
 
 GATE_NAMES = ["And", "Nand", "Nimp", "Imp", "Ncimp", "Cimp", "Nor", "Or", "Xor", "Xnor", "Not"]
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -31,6 +32,17 @@ _lib = None
 
 class GsvError(RuntimeError):
     pass
+
+
+class CiphertextMismatch(GsvError):
+    """GSV_ERR_MISMATCH: a received ciphertext stream differs from its BLAKE3 outboard or commitment.  `instance` is the instance of
+    the session (blake3_files: the index into `paths`), `group` the group of 2^k chunks (the tail behind the last complete group
+    counts as the group after it) and `first_record` the first record the differing value covers; `group` and `first_record` are
+    None when the outboard or the last chunk did not match the commitment before the pass."""
+
+    def __init__(self, message, instance=None, group=None, first_record=None):
+        super().__init__(message)
+        self.instance, self.group, self.first_record = instance, group, first_record
 
 
 # Device objects are released in dependency order BEFORE the interpreter tears down: a session collected during interpreter
@@ -126,6 +138,8 @@ EXPORTS = [
     "gsv_session_garble_streaming_commit", "gsv_blake3_create", "gsv_blake3_destroy", "gsv_blake3_update", "gsv_blake3_absorb_subtree", "gsv_blake3_finalize", "gsv_blake3_file",
     "gsv_engine_blake3_streams", "gsv_engine_blake3_streams_seconds",
     "gsv_session_evaluate_streaming_commit", "gsv_session_evaluate_streaming_source_commit", "gsv_session_ciphertext_blake3",
+    "gsv_blake3_outboard_root", "gsv_blake3_file_outboard", "gsv_session_garble_streaming_commit_outboard", "gsv_engine_blake3_files",
+    "gsv_session_evaluate_streaming_verified", "gsv_session_mismatch_info", "gsv_session_windows_launched",
 ]
 
 # CiphertextHandler / CiphertextSource as host callbacks (include/gsv_engine.h: gsv_ct_sink_fn, gsv_ct_source_fn)
@@ -237,6 +251,13 @@ def lib():
         L.gsv_session_evaluate_streaming_commit.argtypes = [vp, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, u8p, u8p]
         L.gsv_session_evaluate_streaming_source_commit.argtypes = [vp, C.c_uint64, CT_SOURCE_FN, vp, u8p, u8p]
         L.gsv_session_ciphertext_blake3.argtypes = [vp, u8p]
+        L.gsv_blake3_outboard_root.argtypes = [u8p, C.c_uint64, u8p, C.c_uint64, u8p]
+        L.gsv_blake3_file_outboard.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, u8p]
+        L.gsv_session_garble_streaming_commit_outboard.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int, u8p, u8p, C.c_char_p]
+        L.gsv_engine_blake3_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(C.c_char_p), u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.gsv_session_evaluate_streaming_verified.argtypes = [vp, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_char_p, u8p, C.c_uint64, u8p, u8p]
+        L.gsv_session_mismatch_info.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3
+        L.gsv_session_windows_launched.argtypes = [vp, C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -321,6 +342,48 @@ def blake3_file(path):
     out = np.zeros(32, np.uint8)
     _chk(lib().gsv_blake3_file(os.fsencode(path), _p(out)))
     return out.tobytes()
+
+
+def outboard_file_name(index):
+    """The BLAKE3 outboard of gc_<index>.bin, beside it (include/gsv_engine.h, "BLAKE3 outboards")."""
+    return "gc_%d.b3o" % index
+
+
+def blake3_outboard_root(outboard, last_chunk):
+    """The root an outboard (bytes) folds to with the stream's last chunk (bytes: what lies behind the last whole KiB-chunk boundary
+    in front of the end, 16 .. 1024 bytes; empty for the empty stream).  A malformed outboard raises GsvError (GSV_ERR_INVALID)."""
+    ob = np.frombuffer(bytes(outboard), np.uint8)
+    last = np.frombuffer(bytes(last_chunk), np.uint8)
+    out = np.zeros(32, np.uint8)
+    _chk(lib().gsv_blake3_outboard_root(_p(ob) if ob.size else _p(np.zeros(1, np.uint8)), ob.size, _p(last) if last.size else None, last.size, _p(out)))
+    return out.tobytes()
+
+
+def blake3_file_outboard(path, k, outboard_path=None):
+    """Writes the outboard of the file at `path` for groups of 2^k chunks to `outboard_path` (None: nowhere), on the host; returns
+    the file's BLAKE3 digest."""
+    out = np.zeros(32, np.uint8)
+    _chk(lib().gsv_blake3_file_outboard(os.fsencode(path), int(k), os.fsencode(outboard_path) if outboard_path is not None else None, _p(out)))
+    return out.tobytes()
+
+
+def blake3_files(engine, paths, outboards=None):
+    """BLAKE3 of equally long files on the device, read in bounded segments (GSV_DRAIN_SEGMENT_RECORDS records per file) without
+    evaluating them: a list of 32-byte digests.  With `outboards` (one path per file) every group of 2^k chunks is compared with
+    the file's outboard as it is hashed; the first difference raises CiphertextMismatch(instance = index into paths, group)."""
+    n = len(paths)
+    arr = (C.c_char_p * max(1, n))(*[os.fsencode(q) for q in paths])
+    obs = None
+    if outboards is not None:
+        assert len(outboards) == n
+        obs = (C.c_char_p * max(1, n))(*[os.fsencode(q) for q in outboards])
+    out = np.zeros((max(1, n), 32), np.uint8)
+    bad_file, bad_group = C.c_uint64(), C.c_uint64()
+    rc = lib().gsv_engine_blake3_files(engine.h, arr, n, obs, _p(out), C.byref(bad_file), C.byref(bad_group))
+    if rc == 5:
+        raise CiphertextMismatch("gsv status 5: %s" % lib().gsv_last_error().decode(errors="replace"), int(bad_file.value), int(bad_group.value))
+    _chk(rc)
+    return [bytes(out[i]) for i in range(n)]
 
 
 def blake3_streams(engine, array, segments, with_seconds=False):
@@ -709,7 +772,7 @@ class Session:
     def garble(self, gate_id_base=0):
         _chk(lib().gsv_session_garble(self.h, gate_id_base))
 
-    def _garble_commit(self, commitment, gate_id_base, first_call, n_calls, directory, first_index, threads):
+    def _garble_commit(self, commitment, gate_id_base, first_call, n_calls, directory, first_index, threads, outboard_dir=None):
         """commitment "blake3" | "both" (gsv_session_garble_streaming_commit): BLAKE3 digests are computed on the device and reported by the
         call that ends the pass (None before); "both" returns (CBC-MACs, digests)."""
         if commitment not in ("blake3", "both"):
@@ -719,18 +782,22 @@ class Session:
         dig = np.zeros((n, 32), np.uint8)
         ends_pass = (first_call == 0 and n_calls == 0) or not isinstance(self.program, Plan) or first_call + n_calls == self.schedule_info()["n_calls"]  # (else the engine leaves `dig` alone)
         with _gc_paused():
-            _chk(lib().gsv_session_garble_streaming_commit(self.h, gate_id_base, first_call, n_calls, directory.encode() if directory else None, first_index, threads, _p(macs), _p(dig)))
+            _chk(lib().gsv_session_garble_streaming_commit_outboard(self.h, gate_id_base, first_call, n_calls, directory.encode() if directory else None, first_index, threads, _p(macs), _p(dig),
+                                                                    os.fsencode(outboard_dir) if outboard_dir is not None else None))
         digests = [bytes(dig[i]) for i in range(n)] if ends_pass else None
         return ([bytes(macs[i]) for i in range(self.n)], digests) if commitment == "both" else digests
 
-    def garble_streaming(self, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False, commitment="cbcmac"):
+    def garble_streaming(self, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False, commitment="cbcmac", outboard_dir=None):
         """Garble all replays while the host drains the stream segment by segment: returns the per-instance ciphertext
         hashes (CBC-MAC, gate order) and, with `directory`, writes gc_<first_index+i>.bin files.  discard=True: garble
         only, the ciphertexts are dropped.  commitment="blake3": 32-byte BLAKE3 digests of the streams instead, computed on the
-        device (nothing of the stream is copied out unless `directory` is given); "both": (CBC-MACs, BLAKE3 digests)."""
+        device (nothing of the stream is copied out unless `directory` is given); "both": (CBC-MACs, BLAKE3 digests).
+        outboard_dir (with "blake3" / "both"): the BLAKE3 outboards gc_<first_index+i>.b3o are written there."""
         _check_commitment(commitment, discard)
+        if outboard_dir is not None and commitment == "cbcmac":
+            raise ValueError("outboard_dir needs commitment='blake3' or 'both': an outboard holds the values of the BLAKE3 commitment")
         if commitment != "cbcmac":
-            return self._garble_commit(commitment, gate_id_base, 0, 0, directory, first_index, threads)
+            return self._garble_commit(commitment, gate_id_base, 0, 0, directory, first_index, threads, outboard_dir)
         if discard:
             with _gc_paused():
                 _chk(lib().gsv_session_garble_streaming(self.h, gate_id_base, None, 0, 0, None))
@@ -740,16 +807,19 @@ class Session:
             _chk(lib().gsv_session_garble_streaming(self.h, gate_id_base, directory.encode() if directory else None, first_index, threads, _p(out)))
         return [bytes(out[i]) for i in range(self.n)]
 
-    def garble_calls(self, first_call, n_calls, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False, commitment="cbcmac"):
+    def garble_calls(self, first_call, n_calls, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False, commitment="cbcmac", outboard_dir=None):
         """Plan sessions: garble calls [first_call, first_call + n_calls) only (a slice of the plan).  Wires, gate ids and the
         CBC-MAC states continue from the previous slice; first_call == 0 starts a new pass.  Returns the MAC states after the
         slice (the commitments once the last slice has run), or None with discard=True.  commitment="blake3" / "both" as for
-        garble_streaming: the BLAKE3 state chains from slice to slice too, the digests are None until the slice that ends the pass."""
+        garble_streaming: the BLAKE3 state chains from slice to slice too, the digests are None until the slice that ends the pass.
+        outboard_dir as for garble_streaming, in every slice of the pass: the first slice truncates the outboards, later ones append."""
         _check_commitment(commitment, discard)
+        if outboard_dir is not None and commitment == "cbcmac":
+            raise ValueError("outboard_dir needs commitment='blake3' or 'both': an outboard holds the values of the BLAKE3 commitment")
         if commitment != "cbcmac":
             if first_call == 0 and n_calls == 0:
                 raise ValueError("an empty slice")  # (0, 0 means the whole pass to the C entry point)
-            return self._garble_commit(commitment, gate_id_base, first_call, n_calls, directory, first_index, threads)
+            return self._garble_commit(commitment, gate_id_base, first_call, n_calls, directory, first_index, threads, outboard_dir)
         if discard:
             with _gc_paused():
                 _chk(lib().gsv_session_garble_streaming_calls(self.h, gate_id_base, first_call, n_calls, None, 0, 0, None))
@@ -801,13 +871,44 @@ class Session:
         d = [bytes(dig[i]) for i in range(self.n)] if dig is not None else None
         return (m, d) if commitment == "both" else m if d is None else d
 
-    def evaluate_streaming_indexed(self, directory, indexes, gate_id_base=0, commitment="cbcmac"):
+    def _verified_call(self, gate_id_base, directory, idx_p, first_index, outboard_dir, expected, commitment):
+        """call(macs, dig) of gsv_session_evaluate_streaming_verified; GSV_ERR_MISMATCH raises CiphertextMismatch with the place."""
+        if commitment == "cbcmac":
+            raise ValueError("outboard_dir / expected need commitment='blake3' or 'both'")
+        if outboard_dir is None or expected is None:
+            raise ValueError("verified streaming takes outboard_dir and expected together")
+        exp = [bytes(e) for e in expected]
+        if len(exp) != self.n or len(set(len(e) for e in exp)) != 1 or len(exp[0]) not in (16, 32):
+            raise ValueError("expected: one commitment of 16 or of 32 bytes per instance")
+        exp_a = np.frombuffer(b"".join(exp), np.uint8)
+
+        def call(macs, dig):
+            with _gc_paused():
+                rc = lib().gsv_session_evaluate_streaming_verified(self.h, gate_id_base, os.fsencode(directory), idx_p, first_index, os.fsencode(outboard_dir), _p(exp_a), len(exp[0]), _p(macs), _p(dig))
+            if rc == 5:
+                msg = "gsv status 5: %s" % lib().gsv_last_error().decode(errors="replace")
+                raise CiphertextMismatch(msg, *self.mismatch_info())
+            _chk(rc)
+
+        return call
+
+    def mismatch_info(self):
+        """(instance, group, first_record) of the mismatch the last verified pass ended with; group and first_record are None when
+        the outboard or the last chunk did not match the commitment before the pass."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _chk(lib().gsv_session_mismatch_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        unknown = (1 << 64) - 1
+        return int(a.value), None if b.value == unknown else int(b.value), None if c.value == unknown else int(c.value)
+
+    def evaluate_streaming_indexed(self, directory, indexes, gate_id_base=0, commitment="cbcmac", outboard_dir=None, expected=None):
         """Evaluate with instance i reading gc_<indexes[i]>.bin: the finalized instances of a cut-and-choose run in one session.
-        commitment as for evaluate_streaming."""
+        commitment, outboard_dir and expected as for evaluate_streaming."""
         _check_commitment(commitment, False)
         idx = np.ascontiguousarray(indexes, np.uint64)
         assert idx.size == self.n
         idx_p = idx.ctypes.data_as(C.POINTER(C.c_uint64))
+        if outboard_dir is not None or expected is not None:
+            return self._evaluate_commit(commitment, self._verified_call(gate_id_base, directory, idx_p, 0, outboard_dir, expected, commitment))
 
         def call(macs, dig):
             with _gc_paused():
@@ -858,7 +959,9 @@ class Session:
         depth in device steps)."""
         i = _PlanScheduleInfo()
         _chk(lib().gsv_session_plan_schedule_info(self.h, C.byref(i)))
-        return {k: int(getattr(i, k)) for k in _SCHED_FIELDS}
+        n = C.c_uint64()
+        _chk(lib().gsv_session_windows_launched(self.h, C.byref(n)))
+        return dict({k: int(getattr(i, k)) for k in _SCHED_FIELDS}, windows_launched=int(n.value))  # (windows the session's last pass launched)
 
     def fallback_count(self):
         """How often this plan session has fallen back to the safe schedule (one call per launch) after a dependency wait gave up."""
@@ -885,11 +988,17 @@ class Session:
         """Timing harnesses only: allow garble_calls slices that do not continue the previous one (stale wires, meaningless MACs)."""
         _chk(lib().gsv_session_set_unchecked_slices(self.h, int(bool(on))))
 
-    def evaluate_streaming(self, directory, first_index=0, gate_id_base=0, commitment="cbcmac"):
+    def evaluate_streaming(self, directory, first_index=0, gate_id_base=0, commitment="cbcmac", outboard_dir=None, expected=None):
         """Evaluate with the ciphertexts read from gc_<first_index+i>.bin segment by segment; returns the files' CBC-MACs.
         commitment="blake3": the files' 32-byte BLAKE3 digests instead, computed on the device from the uploaded segments (no MAC
-        worker runs); "both": (CBC-MACs, BLAKE3 digests).  Comparing them with the garbler's commitments is the caller's part."""
+        worker runs); "both": (CBC-MACs, BLAKE3 digests).  Comparing them with the garbler's commitments is the caller's part —
+        unless outboard_dir and expected are given (verified streaming, with "blake3" / "both"): `expected` holds the commitment of
+        every instance (32 bytes, or the first 16), the outboards gc_<index>.b3o in outboard_dir are checked against them before
+        anything is uploaded, and the pass stops at the first group of 2^k chunks that differs from its outboard: CiphertextMismatch
+        names (instance, group), and read_outputs then fails."""
         _check_commitment(commitment, False)
+        if outboard_dir is not None or expected is not None:
+            return self._evaluate_commit(commitment, self._verified_call(gate_id_base, directory, None, first_index, outboard_dir, expected, commitment))
 
         def call(macs, dig):
             with _gc_paused():

@@ -1,5 +1,6 @@
 // The host side of the streaming drain (engine_drain.ipp): the session's copy streams, pinned chunk buffers and MAC states; where a
-// drained stream goes; the gc_<i>.bin files of a pass; the pool of MAC / copy workers behind a queue of segments; the BLAKE3 absorbers.
+// drained stream goes; the gc_<i>.bin files of a pass and its gc_<i>.b3o outboards; the pool of MAC / copy workers behind a queue of
+// segments; the BLAKE3 absorbers.
 // Each pool owns its threads and joins them in its destructor.  Nothing here knows sessions, schedules, plans or knobs — plain values
 // in — and nothing but the HIP runtime API, hip_owned.hpp, host_crypto.hpp and the standard library is needed: this header compiles
 // alone (tests/drain_pipeline runs it against stand-ins for the HIP calls, also under the thread and address sanitizers).
@@ -22,6 +23,7 @@
 
 #include "hip_owned.hpp"
 #include "host_crypto.hpp"
+#include "outboard.hpp"
 
 namespace gsv {
 // The drain machinery (copy streams, pinned chunk buffers, the per-instance MAC states) lives in the session, so that a plan can
@@ -79,6 +81,7 @@ struct DrainSink {
   DrainSinkFn fn = nullptr;            // CiphertextHandler::handle over a run of records of one instance
   void* user = nullptr;
   uint8_t* b3 = nullptr;               // n_inst x 32: the BLAKE3 digests, written by the call that ends the pass
+  const char* outboard_dir = nullptr;  // gc_<index>.b3o: the values the BLAKE3 absorbers receive, kept (needs b3)
   bool host() const { return hashes || dir || fn; }  // the stream is copied to the host
   bool any() const { return host() || b3; }
 };
@@ -105,6 +108,47 @@ class GcFiles {
     return true;
   }
   FILE* operator[](size_t i) const { return files_[i]; }
+  void keep() { keep_ = true; }
+ private:
+  std::vector<FILE*> files_;
+  std::vector<std::string> paths_;
+  bool keep_ = false;
+};
+
+// The gc_<first_index + i>.b3o files of one call (outboard.hpp): a header, then the 32-byte values in the order the host absorbs them.
+// A new pass writes the header, a later slice appends; closed when the object goes away and REMOVED unless keep() was called, like the
+// gc files beside them.  Instances may be written from different threads, one instance from one thread at a time.
+class OutboardFiles {
+ public:
+  OutboardFiles() = default;
+  OutboardFiles(const OutboardFiles&) = delete;
+  OutboardFiles& operator=(const OutboardFiles&) = delete;
+  ~OutboardFiles() {
+    for (FILE* f : files_) std::fclose(f);
+    if (!keep_) for (const std::string& q : paths_) std::remove(q.c_str());
+  }
+  static std::string path(const char* dir, uint64_t index) { return std::string(dir) + "/gc_" + std::to_string(index) + ".b3o"; }
+  // new_pass: truncate and write the header for a stream of n_records records in groups of 2^k chunks; else append.  False: `*failed`.
+  bool open(const char* dir, uint64_t first_index, size_t n_inst, bool new_pass, uint32_t k, uint64_t n_records, std::string* failed) {
+    uint8_t header[Outboard::HEADER_BYTES];
+    Outboard::put_header(header, k, n_records);
+    for (size_t i = 0; i < n_inst; ++i) {
+      const std::string q = path(dir, first_index + i);
+      FILE* f = std::fopen(q.c_str(), new_pass ? "wb" : "ab");
+      if (!f) { *failed = q; return false; }
+      files_.push_back(f); paths_.push_back(q);
+      if (new_pass && std::fwrite(header, 1, sizeof header, f) != sizeof header) { *failed = q; return false; }
+    }
+    return true;
+  }
+  size_t size() const { return files_.size(); }
+  // `count` values per instance ([instance][value], dense, for all instances) go to the files of instances i0, i0 + step, ...
+  bool append(const uint8_t* vals, uint32_t count, size_t i0, size_t step) {
+    bool ok = true;
+    for (size_t i = i0; i < files_.size(); i += step) ok = std::fwrite(vals + i * size_t(count) * 32, 32, count, files_[i]) == count && ok;
+    return ok;
+  }
+  bool flush() { bool ok = true; for (FILE* f : files_) ok = std::fflush(f) == 0 && ok; return ok; }
   void keep() { keep_ = true; }
  private:
   std::vector<FILE*> files_;

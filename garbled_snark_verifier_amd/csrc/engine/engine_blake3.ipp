@@ -1,7 +1,8 @@
 // Part of engine.cpp: BLAKE3 commitments — the host hasher behind gsv_blake3_*, and the device tree hash of n equally long streams
 // that arrive in segments of a gate-order buffer (blake3_device.hpp), shared by the streaming drain (engine_drain.ipp), the streaming
-// evaluators (engine_evaluate.ipp), gsv_session_ciphertext_blake3 (engine_readback.ipp: it feeds ranges of the resident program-order stream) and
-// gsv_engine_blake3_streams.
+// evaluators (engine_evaluate.ipp), gsv_session_ciphertext_blake3 (engine_readback.ipp: it feeds ranges of the resident program-order stream),
+// gsv_engine_blake3_streams and gsv_engine_blake3_files; and the outboards (outboard.hpp): the values the host absorbs, kept in a file
+// by the drain, checked against a commitment (gsv_blake3_outboard_root) and compared with what a receiver's streams hash to (B3Check).
 //
 // Split (DESIGN.md §3 "Commitment stage"): a stream of L records has N = max(1, ceil(L / 64)) chunks.  The device hashes chunks
 // 0 .. N-2 and reduces aligned groups of G = 2^k of them to one value each; the host absorbs floor((N-1) / G) group values, then the
@@ -75,8 +76,66 @@ static bool b3_absorb(B3Stream& b, const uint8_t* vals, uint32_t groups, unsigne
     for (uint32_t g = 0; g < groups; ++g) ok = b.hashers[i].absorb_subtree(vals + (i * groups + g) * 32, k) && ok;
   return ok;
 }
-// every record has been fed and every group value absorbed: the pending chunk values and the last chunks come to the host
-static int b3_finish(B3Stream& b, hipStream_t st, uint8_t* digests) {
+// The outboards a set of streams is verified against (outboard.hpp), by whoever receives the values the host absorbs: a streaming
+// evaluation in verified mode (engine_evaluate.ipp) and gsv_engine_blake3_files.  Every value is compared, in the order it arrives,
+// with the outboard of its instance; the first difference — the lowest group, then the lowest instance — is kept.
+struct B3Check {
+  std::vector<std::vector<uint8_t>> bytes;  // per instance: a well-formed outboard for `k` and `n_records`
+  uint32_t k = 0;
+  uint64_t n_records = 0, n_groups = 0, n_pending = 0;
+  uint64_t next = 0;                        // group values compared so far, per instance
+  size_t bad_instance = 0;
+  uint64_t bad_group = 0, bad_record = 0;   // the group (the open tail behind the last complete group: n_groups) and the first record the value covers
+  const uint8_t* value(size_t i, uint64_t v) const { return bytes[i].data() + Outboard::HEADER_BYTES + 32 * v; }
+  // `groups` group values per instance, [instance][group] dense
+  bool groups_match(const uint8_t* vals, uint32_t groups) {
+    if (next + groups > n_groups) { bad_instance = 0; bad_group = n_groups; bad_record = (n_groups << k) * 64; return false; }
+    for (uint32_t g = 0; g < groups; ++g)
+      for (size_t i = 0; i < bytes.size(); ++i)
+        if (std::memcmp(vals + (i * groups + g) * 32, value(i, next + g), 32) != 0) { bad_instance = i; bad_group = next + g; bad_record = ((next + g) << k) * 64; return false; }
+    next += groups;
+    return true;
+  }
+  // the chunk values behind the last complete group, [instance][value] dense
+  bool pending_match(const uint8_t* vals, uint32_t pend) {
+    if (next != n_groups || pend != n_pending) { bad_instance = 0; bad_group = std::min(next, n_groups); bad_record = (bad_group << k) * 64; return false; }
+    for (uint32_t c = 0; c < pend; ++c)
+      for (size_t i = 0; i < bytes.size(); ++i)
+        if (std::memcmp(vals + (i * pend + c) * 32, value(i, n_groups + c), 32) != 0) { bad_instance = i; bad_group = n_groups; bad_record = ((n_groups << k) + c) * 64; return false; }
+    return true;
+  }
+  std::string where(const char* what) const {
+    return std::string(what) + " " + std::to_string(bad_instance) + " does not match its outboard in group " + std::to_string(bad_group) + " (from record " + std::to_string(bad_record) + ")";
+  }
+};
+// The whole of `path` (at most `most` bytes are accepted) -> *out.  False: *why.
+static bool read_small_file(const std::string& path, uint64_t most, std::vector<uint8_t>* out, std::string* why) {
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) { *why = "cannot open " + path; return false; }
+  out->resize(size_t(most) + 1);
+  const size_t n = std::fread(out->data(), 1, out->size(), f);
+  const bool bad = std::ferror(f) != 0;
+  std::fclose(f);
+  if (bad) { *why = "read error on " + path; return false; }
+  out->resize(n);
+  return true;
+}
+// The outboard at `path` for a stream of n_records records in groups of 2^k chunks -> *out, parsed and bounds-checked.  A header that
+// says otherwise, and a length that does not follow from it, are refused (*why names both sides).
+static bool load_outboard(const std::string& path, uint32_t k, uint64_t n_records, std::vector<uint8_t>* out, std::string* why) {
+  if (!read_small_file(path, Outboard::file_bytes(n_records, k), out, why)) return false;
+  Outboard o;
+  if (!Outboard::parse_header(out->data(), out->size(), &o, why)) { *why = path + ": " + *why; return false; }
+  if (o.n_records != n_records) { *why = path + " is the outboard of a stream of " + std::to_string(o.n_records) + " records, the stream here holds " + std::to_string(n_records); return false; }
+  if (o.k != k) { *why = path + " was written for groups of 2^" + std::to_string(o.k) + " chunks, this pass reduces groups of 2^" + std::to_string(k) + " (GSV_B3_SUBTREE_LOG2)"; return false; }
+  if (!Outboard::parse(out->data(), out->size(), &o, why)) { *why = path + ": " + *why; return false; }
+  return true;
+}
+
+// every record has been fed and every group value absorbed: the pending chunk values and the last chunks come to the host.
+// `pending` (optional) sees the pending chunk values ([instance][value], dense) before they are absorbed and before anything is
+// written to `digests`; a non-zero return ends the call with it.
+static int b3_finish(B3Stream& b, hipStream_t st, uint8_t* digests, const std::function<int(const uint8_t* vals, uint32_t pend)>& pending = nullptr) {
   if (b.records_done != b.total) return fail(GSV_ERR_INVALID, "internal: BLAKE3 stream ended early");
   // the folding (up to 2^k - 1 parents, the last chunk and the stack per instance) runs on a few threads, not on the caller's
   const size_t T = std::min<size_t>(4, b.n_inst);
@@ -90,9 +149,10 @@ static int b3_finish(B3Stream& b, hipStream_t st, uint8_t* digests) {
   if (b.pend) {
     HIPCHK(hipMemcpy2DAsync(b.pinned.get(), size_t(b.pend) * 32, b.cv[b.vpar].get(), size_t(b.cv_stride) * 32, size_t(b.pend) * 32, b.n_inst, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    if (pending) { const int prc = pending(b.pinned.get(), b.pend); if (prc) return prc; }
     const bool ok = on_pool([&](size_t i) { bool r = true; for (uint32_t g = 0; g < b.pend; ++g) r = b.hashers[i].absorb_subtree(b.pinned.get() + (i * b.pend + g) * 32, 0) && r; return r; });
     if (!ok) return fail(GSV_ERR_INVALID, "internal: BLAKE3 chunk values out of order");
-  }
+  } else if (pending) { const int prc = pending(nullptr, 0); if (prc) return prc; }
   if (b.carry_n) {
     HIPCHK(hipMemcpyAsync(b.pinned.get(), b.carry[b.cpar].get(), b.n_inst * 1024, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -137,6 +197,114 @@ int gsv_blake3_file(const char* path, uint8_t* out) {
   if (bad) return fail(GSV_ERR_INVALID, std::string("read error on ") + path);
   h.finalize(out);
   return GSV_OK;
+}
+// ---- outboards (include/gsv_engine.h "BLAKE3 outboards", outboard.hpp) ----
+int gsv_blake3_outboard_root(const uint8_t* outboard, uint64_t n_bytes, const uint8_t* last_chunk, uint64_t last_chunk_bytes, uint8_t* out) {
+  if (!outboard || !out || (!last_chunk && last_chunk_bytes)) return fail(GSV_ERR_INVALID, "null argument");
+  if (last_chunk_bytes > 1024 || (last_chunk_bytes & 15)) return fail(GSV_ERR_INVALID, "the last chunk holds 16 .. 1024 bytes in whole records (0 only for the empty stream)");
+  Outboard o;
+  std::string why;
+  if (!Outboard::parse(outboard, n_bytes, &o, &why) || !o.root(last_chunk, last_chunk_bytes, out, &why)) return fail(GSV_ERR_INVALID, why);
+  return GSV_OK;
+}
+int gsv_blake3_file_outboard(const char* path, uint32_t k, const char* outboard_path, uint8_t* out) {
+  if (!path || !out) return fail(GSV_ERR_INVALID, "null argument");
+  std::vector<uint8_t> ob, last;
+  std::string why;
+  if (!outboard_of_file(path, k, &ob, &last, &why)) return fail(GSV_ERR_INVALID, why);
+  Outboard o;
+  if (!Outboard::parse(ob.data(), ob.size(), &o, &why) || !o.root(last.data(), last.size(), out, &why)) return fail(GSV_ERR_INVALID, why);
+  if (outboard_path) {
+    FILE* f = std::fopen(outboard_path, "wb");
+    if (!f) return fail(GSV_ERR_INVALID, std::string("cannot create ") + outboard_path);
+    const bool ok = std::fwrite(ob.data(), 1, ob.size(), f) == ob.size();
+    if (std::fclose(f) != 0 || !ok) { std::remove(outboard_path); return fail(GSV_ERR_INVALID, std::string("short write to ") + outboard_path); }
+  }
+  return GSV_OK;
+}
+// Received files hashed where the kernels are: n equally long files are read in segments through two page-locked staging buffers
+// (CtUploader without MAC workers: the read of a piece overlaps the upload of the one before), uploaded to a gate-order buffer of one
+// segment and fed to b3_begin / b3_segment / b3_finish as n streams — the whole input is never resident.  With outboards every value
+// the host receives is compared before it is absorbed; the values of a segment are looked at when the next segment has been enqueued.
+int gsv_engine_blake3_files(gsv_engine* e, const char* const* paths, uint64_t n_files, const char* const* outboard_paths, uint8_t* digests, uint64_t* bad_file_out, uint64_t* bad_group_out) {
+  if (!e || !paths || !digests) return fail(GSV_ERR_INVALID, "null argument");
+  const uint32_t k = knobs::b3_subtree_log2();
+  const uint64_t seg_knob = knobs::at_least_1("GSV_DRAIN_SEGMENT_RECORDS");
+  if (k > 20) return fail(GSV_ERR_INVALID, "GSV_B3_SUBTREE_LOG2 must be an integer in [0, 20]");
+  if (n_files == 0 || n_files > 65535) return fail(GSV_ERR_INVALID, "BLAKE3 commitments take 1 .. 65535 streams at a time");
+  const size_t n = size_t(n_files);
+  std::vector<FILE*> files(n, nullptr);
+  struct Closer { std::vector<FILE*>& f; ~Closer() { for (FILE* q : f) if (q) std::fclose(q); } } closer{files};
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (!paths[i] || (outboard_paths && !outboard_paths[i])) return fail(GSV_ERR_INVALID, "null path");
+    files[i] = std::fopen(paths[i], "rb");
+    struct stat sb;
+    if (!files[i] || fstat(fileno(files[i]), &sb) != 0) return fail(GSV_ERR_INVALID, std::string("cannot open ") + paths[i]);
+    if (sb.st_size < 0 || (uint64_t(sb.st_size) & 15) || uint64_t(sb.st_size) / 16 > Outboard::MAX_RECORDS) return fail(GSV_ERR_INVALID, std::string(paths[i]) + " does not hold whole 16-byte records");
+    if (i == 0) total = uint64_t(sb.st_size) / 16;
+    else if (uint64_t(sb.st_size) / 16 != total)
+      return fail(GSV_ERR_INVALID, "the files must be equally long: " + std::string(paths[0]) + " holds " + std::to_string(total) + " records, " + paths[i] + " " + std::to_string(uint64_t(sb.st_size) / 16));
+  }
+  std::unique_ptr<B3Check> check;
+  if (outboard_paths) {
+    check.reset(new B3Check());
+    check->k = k; check->n_records = total; check->n_groups = (Outboard::chunks(total) - 1) >> k; check->n_pending = (Outboard::chunks(total) - 1) & ((1ull << k) - 1);
+    check->bytes.resize(n);
+    std::string why;
+    for (size_t i = 0; i < n; ++i) if (!load_outboard(outboard_paths[i], k, total, &check->bytes[i], &why)) return fail(GSV_ERR_INVALID, why);
+  }
+  // records per file and segment: the knob, or 16 MiB per file within 256 MiB for all of them
+  const uint64_t seg = std::max<uint64_t>(1, std::min<uint64_t>(total, seg_knob ? seg_knob : std::max<uint64_t>(4096, std::min<uint64_t>(1ull << 20, (1ull << 24) / n))));
+  HIPCHK(hipSetDevice(e->device));
+  const hipStream_t st = e->stream.get();
+  DevBuf gate;
+  DEVALLOC(gate, n * size_t(seg) * 16, "the segment of the files to hash");
+  std::vector<uint64_t> pos(n, 0);
+  CtUploader up(n, seg, std::min<uint64_t>(seg, CT_STAGE_RECORDS), 0, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t m) -> int {
+    if (pos[i] != first) { if (fseeko(files[i], off_t(first * 16), SEEK_SET) != 0) return 1; pos[i] = first; }
+    if (m && std::fread(dst, 16, m, files[i]) != m) return 1;
+    pos[i] += m;
+    return 0;
+  });
+  if (up.alloc() != hipSuccess) return fail(GSV_ERR_DEVICE, "cannot allocate the staging buffers");
+  std::unique_ptr<B3Stream> b;
+  int rc = b3_begin(b, n, total, seg, k);
+  if (rc) return rc;
+  Event ev;
+  HIPCHK(ev.create(hipEventDisableTiming));
+  uint32_t groups = 0;  // group values of the segment in flight
+  auto mismatch = [&]() {
+    if (bad_file_out) *bad_file_out = check->bad_instance;
+    if (bad_group_out) *bad_group_out = check->bad_group;
+    return fail(GSV_ERR_MISMATCH, check->where("file"));
+  };
+  auto flush = [&]() -> int {
+    if (!groups) return GSV_OK;
+    if (hipEventSynchronize(ev.get()) != hipSuccess) return fail(GSV_ERR_DEVICE, "event wait failed");
+    const uint32_t g = groups;
+    groups = 0;
+    if (check && !check->groups_match(b->pinned.get(), g)) return mismatch();
+    return b3_absorb(*b, b->pinned.get(), g, k, 0, 1) ? GSV_OK : fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
+  };
+  for (uint64_t off = 0; off < total && rc == GSV_OK; off += seg) {
+    const uint64_t m = std::min(seg, total - off);
+    switch (up.upload(off, m, gate.get(), st)) {
+      case UploadError::None: break;
+      case UploadError::Dry: rc = fail(GSV_ERR_INVALID, std::string("read error on ") + paths[up.dry_instance()]); break;
+      default: rc = fail(GSV_ERR_DEVICE, "upload of a file segment failed");
+    }
+    if (rc == GSV_OK) rc = flush();  // (the page-locked value buffer is free for this segment's values)
+    if (rc == GSV_OK) rc = b3_segment(*b, gate.get(), seg, m, st, &groups);
+    if (rc == GSV_OK && groups && hipEventRecord(ev.get(), st) != hipSuccess) rc = fail(GSV_ERR_DEVICE, "event record failed");
+  }
+  if (rc == GSV_OK) rc = flush();
+  std::vector<uint8_t> out(n * 32);
+  if (rc == GSV_OK)
+    rc = b3_finish(*b, st, out.data(), check ? std::function<int(const uint8_t*, uint32_t)>([&](const uint8_t* vals, uint32_t pend) { return check->pending_match(vals, pend) ? GSV_OK : mismatch(); }) : nullptr);
+  (void)hipStreamSynchronize(st);  // (nothing of `gate` or the staging buffers is in flight when they are released)
+  if (rc == GSV_OK) std::memcpy(digests, out.data(), out.size());
+  return rc;
 }
 // The kernels alone: n_streams streams of records_per_stream records each (data: [stream][record]) are uploaded and fed to the chunk,
 // reduce and carry code of the drain in the given segmentation; the host finishes them.

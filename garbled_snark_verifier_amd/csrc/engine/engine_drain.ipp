@@ -44,6 +44,7 @@ static int garble_discard(gsv_session* s, uint64_t gate_id_base, size_t c0, size
   if (s->plan) {
     size_t w0 = 0, w1 = 0;
     if (c0 == 0) HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));
+    if (c0 == 0) s->windows_launched = 0;
     if (s->ct_ring) __atomic_store_n(s->sd.ct_pos.get(), ~0ull, __ATOMIC_RELEASE);  // nothing reads the ciphertexts: every block of the ring is free at once
     rc = window_range(s, c0, c1, &w0, &w1);
     for (size_t w = w0; w < w1 && rc == GSV_OK; ++w) rc = launch_plan_window(s, w, gate_id_base, false);
@@ -214,7 +215,7 @@ static std::vector<void*> drain_gate_buffers(gsv_session* s, size_t n_units, siz
 }
 static int fail_drain(DrainError e) {
   switch (e) {
-    case DrainError::FileWrite: return fail(GSV_ERR_INVALID, "short write to a gc file");
+    case DrainError::FileWrite: return fail(GSV_ERR_INVALID, "short write to a gc or outboard file");
     case DrainError::Sink: return fail(GSV_ERR_INVALID, "the ciphertext sink reported an error");
     case DrainError::B3Order: return fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
     default: return fail(GSV_ERR_DEVICE, "device copy failed while draining ciphertexts");
@@ -343,6 +344,8 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   const bool want_host = sink.host();    // ... and copied out by the workers
   const bool want_b3 = sink.b3 != nullptr;
   const bool want_mac = sink.hashes != nullptr;
+  if (sink.outboard_dir && !want_b3) return fail(GSV_ERR_INVALID, "an outboard holds the values of the BLAKE3 commitment: blake3_digests must be given");
+  if (s->plan && new_pass) s->windows_launched = 0;
   const size_t GROUP = size_t(gsv_drain::group_for(n_inst, s->pass.drain_group));
   const size_t n_groups = (n_inst + GROUP - 1) / GROUP;
   // a worker MACs GROUP streams side by side at ~3e8 blocks/s (four chains, AES-NI) or ~1e9 (sixteen, VAES): a dozen / four of them keep
@@ -359,7 +362,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   // A pass that commits with BLAKE3 carries the same commitments in every slice: a slice without MAC workers leaves the MAC states
   // behind, one without the hash kernels the BLAKE3 state, and the commitment returned at the end would cover part of the stream
   {
-    const uint8_t commit = uint8_t((want_mac ? 1 : 0) | (want_b3 ? 2 : 0));
+    const uint8_t commit = uint8_t((want_mac ? 1 : 0) | (want_b3 ? 2 : 0) | (sink.outboard_dir ? 4 : 0));  // (an outboard is part of what a BLAKE3 pass carries)
     if (new_pass || !s->plan) s->pass_commit = commit;
     else if (commit != s->pass_commit && ((commit | s->pass_commit) & 2)) return fail(GSV_ERR_INVALID, "every slice of a pass with a BLAKE3 commitment must ask for the same commitments as its first slice");
   }
@@ -379,6 +382,8 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   std::vector<CbcMacHost>& macs = want_host ? s->drain->macs : no_macs;
   GcFiles files;  // (removed again on every return but the last)
   if (std::string failed; sink.dir && !files.open(sink.dir, sink.first_index, n_inst, new_pass ? "wb" : "ab", &failed)) return fail(GSV_ERR_INVALID, "cannot create " + failed);
+  OutboardFiles outboards;  // (likewise; written by the absorbers' threads, and by this one when the pass ends)
+  if (std::string failed; sink.outboard_dir && !outboards.open(sink.outboard_dir, sink.first_index, n_inst, new_pass, s->b3->k, s->b3->total, &failed)) return fail(GSV_ERR_INVALID, "cannot create " + failed);
   DrainShape shape;
   shape.device = s->e->device; shape.n_inst = n_inst; shape.group = GROUP; shape.n_workers = want_host ? T : 0;
   shape.chunk = want_host ? s->drain->chunk : 0; shape.seg_records = seg_records; shape.blocking_wait = T > 8;
@@ -392,7 +397,11 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   std::atomic<DrainError> err{DrainError::None};
   DrainWorkers workers(s->drain.get(), shape, sink, macs, files, err);
   B3Stream* const b3s = want_b3 ? s->b3.get() : nullptr;
-  B3Absorbers absorbers(want_b3 ? std::min<size_t>(4, n_inst) : 0, [b3s](const uint8_t* vals, uint32_t groups, size_t t, size_t n) { return b3_absorb(*b3s, vals, groups, b3s->k, t, n); }, err);
+  OutboardFiles* const obf = sink.outboard_dir ? &outboards : nullptr;
+  B3Absorbers absorbers(want_b3 ? std::min<size_t>(4, n_inst) : 0, [b3s, obf, &err](const uint8_t* vals, uint32_t groups, size_t t, size_t n) {
+    if (obf && !obf->append(vals, groups, t, n)) drain_set_error(err, DrainError::FileWrite);  // thread t keeps the values of ITS instances as it receives them
+    return b3_absorb(*b3s, vals, groups, b3s->k, t, n);
+  }, err);
   DrainStats stats;
   s->ring_diag.clear();
   Event device_done;
@@ -429,10 +438,14 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   if (rc == GSV_OK && ev) rc = check_plan_error(ev);
   if (rc == GSV_OK && err != DrainError::None) rc = fail_drain(err);
   // the call that ends the pass finishes the BLAKE3 streams: pending chunk values and the last chunks come to the host (<= 1 KiB + 32 B x 2^k per instance)
-  if (rc == GSV_OK && want_b3 && (!s->plan || c1 == s->plan->calls.size())) rc = b3_finish(*s->b3, s->e->stream.get(), sink.b3);
+  if (rc == GSV_OK && want_b3 && (!s->plan || c1 == s->plan->calls.size()))
+    rc = b3_finish(*s->b3, s->e->stream.get(), sink.b3, obf ? std::function<int(const uint8_t*, uint32_t)>([obf](const uint8_t* vals, uint32_t pend) {
+      return !pend || obf->append(vals, pend, 0, 1) ? GSV_OK : fail(GSV_ERR_INVALID, "short write to an outboard file");
+    }) : nullptr);
+  if (rc == GSV_OK && obf && !obf->flush()) rc = fail(GSV_ERR_INVALID, "short write to an outboard file");
   if (rc != GSV_OK) return rc;
   if (want_mac) for (size_t i = 0; i < n_inst; ++i) macs[i].digest(sink.hashes + 16 * i);
-  files.keep();
+  files.keep(); outboards.keep();
   s->garbled = true;
   return GSV_OK;
 }
@@ -515,10 +528,17 @@ int gsv_session_garble_streaming_calls(gsv_session* s, uint64_t gate_id_base, ui
 // Either commitment or both (include/gsv_engine.h, "BLAKE3 commitments"): the CBC-MAC on the host's cores, BLAKE3 where the ciphertexts are.
 int gsv_session_garble_streaming_commit(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* dir, uint64_t first_index, int n_threads,
                                         uint8_t* cbcmac_hashes, uint8_t* blake3_digests) {
+  return gsv_session_garble_streaming_commit_outboard(s, gate_id_base, first_call, n_calls, dir, first_index, n_threads, cbcmac_hashes, blake3_digests, nullptr);
+}
+// ... and with the values the absorbers receive kept as gc_<index>.b3o (include/gsv_engine.h, "BLAKE3 outboards")
+int gsv_session_garble_streaming_commit_outboard(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* dir, uint64_t first_index, int n_threads,
+                                                 uint8_t* cbcmac_hashes, uint8_t* blake3_digests, const char* outboard_dir) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   if (!s) return fail(GSV_ERR_INVALID, "null argument");
+  if (outboard_dir && !blake3_digests) return fail(GSV_ERR_INVALID, "an outboard holds the values of the BLAKE3 commitment: blake3_digests must be given");
   DrainSink k = mac_file_sink(cbcmac_hashes, dir, first_index);
   k.b3 = blake3_digests;
+  k.outboard_dir = outboard_dir;
   if (!s->plan) {
     if (first_call || n_calls) return fail(GSV_ERR_INVALID, "program sessions are garbled in one pass (first_call = n_calls = 0)");
     return garble_streaming_range(s, gate_id_base, 0, 1, k, n_threads);

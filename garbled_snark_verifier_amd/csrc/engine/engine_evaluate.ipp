@@ -22,11 +22,18 @@ struct EvalB3 {
   gsv_session* s;
   uint64_t seg_records;
   bool on;  // digests were asked for
+  B3Check* check;  // verified mode: the instances' outboards, every group value is compared before it is absorbed (else null)
   Event ev;
   uint32_t groups = 0;
+  // the pass ends here: the stream differs from its outboard at the place `check` holds
+  int mismatch() {
+    s->mismatch = true; s->mismatch_instance = check->bad_instance; s->mismatch_group = check->bad_group; s->mismatch_record = check->bad_record;
+    return fail(GSV_ERR_MISMATCH, check->where("the ciphertext stream of instance"));
+  }
   int flush() {
     if (!groups) return GSV_OK;
     if (hipEventSynchronize(ev.get()) != hipSuccess) return fail(GSV_ERR_DEVICE, "event wait failed");
+    if (check && !check->groups_match(s->b3_eval->pinned.get(), groups)) { groups = 0; return mismatch(); }
     const bool ok = b3_absorb(*s->b3_eval, s->b3_eval->pinned.get(), groups, s->b3_eval->k, 0, 1);
     groups = 0;
     return ok ? GSV_OK : fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
@@ -108,6 +115,8 @@ static int evaluate_plan_windows(EvalPass& p) {
       if (rc == GSV_OK) rc = p.b3.feed(sg.n_ct, s->e->stream.get());
       if (rc == GSV_OK) rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, p.seg_records, 1, nullptr, nullptr, nullptr);
     }
+    // verified mode: every group value the segments uploaded so far have produced is compared before the window that reads them is launched
+    if (rc == GSV_OK && p.b3.check) rc = p.b3.flush();
     if (rc == GSV_OK) rc = launch_plan_window(s, w, p.gate_id_base, true);
   }
   return rc;
@@ -121,6 +130,7 @@ static int evaluate_program_rings(EvalPass& p) {
     const uint64_t r1 = std::min(total, r0 + seg);
     rc = p.upload(r0 * n_ct, (r1 - r0) * n_ct, s->e->stream.get());
     if (rc == GSV_OK) rc = p.b3.feed((r1 - r0) * n_ct, s->e->stream.get());
+    if (rc == GSV_OK && p.b3.check) rc = p.b3.flush();  // verified mode: compared before the ring is scattered and launched
     if (rc != GSV_OK) break;
     if (gsvk_gather_segment(s->CT.get(), s->ct_stride(), s->dp->ct_pos.as<const uint32_t>(), n_ct, uint32_t(r1 - r0), uint32_t(s->n_inst), s->ct_gate.get(), p.seg_records, 1, s->e->stream.get()) != 0) { rc = fail(GSV_ERR_DEVICE, "ciphertext scatter launch failed"); break; }
     rc = launch(s, p.gate_id_base, true, r0, r1 - r0);
@@ -134,8 +144,19 @@ static int evaluate_program_rings(EvalPass& p) {
 //   read(instance, first_record, dst, n) -> 0, or non-zero when the source runs dry ("Ciphertext source exhausted", evaluate_mode.rs:139-142)
 // With `digests` the uploaded gate-order segments are also fed to the BLAKE3 kernels of the garbler's drain (engine_blake3.ipp), on the
 // stream that scatters them: what the evaluator compares with commit_i = BLAKE3(gc_<i>.bin) costs the host 32 bytes per group of chunks.
-static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests) {
+// Verified mode (gsv_session_evaluate_streaming_verified): the instances' outboards, already checked against `expected`, and the
+// commitments themselves (n_inst x expected_len bytes) for the last look at the computed digests.
+struct EvalVerify { B3Check check; const uint8_t* expected; uint64_t expected_len; };
+static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests, EvalVerify* vf);
+static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests, EvalVerify* vf = nullptr) {
+  if (vf) { vf->check.next = 0; s->mismatch = false; }  // (the pass the safe-schedule fallback repeats verifies from group 0 again)
+  const int rc = evaluate_streaming_pass_inner(s, gate_id_base, read, hashes, digests, vf);
+  if (rc == GSV_ERR_MISMATCH) s->ran = false;  // no outputs for a stream that did not verify: gsv_session_read_outputs fails as after a pass that never ran
+  return rc;
+}
+static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests, EvalVerify* vf) {
   const Program& g = s->prog();
+  if (s->plan) s->windows_launched = 0;
   // plan sessions: one window of the schedule per launch, its ciphertexts uploaded SEGMENT by segment (schedule.hpp: a gate-order buffer
   // holds the largest segment, the program-order device block the largest window); program sessions: one ring per launch
   const size_t n_inst = s->n_inst;
@@ -147,7 +168,7 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
   const size_t T = hashes ? std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n_inst, 16), gsv_drain::usable_cores() > 1 ? gsv_drain::usable_cores() - 1 : 1)) : 0;
   CtUploader up(n_inst, seg_records, std::min<uint64_t>(std::max<uint64_t>(seg_records, 1), CT_STAGE_RECORDS), T, read);
   if (up.alloc() != hipSuccess) return fail(GSV_ERR_DEVICE, "cannot allocate the ciphertext staging buffers");
-  EvalPass p{s, gate_id_base, up, seg_records, {s, seg_records, digests != nullptr}};
+  EvalPass p{s, gate_id_base, up, seg_records, {s, seg_records, digests != nullptr, vf ? &vf->check : nullptr}};
   if (digests) {  // every pass starts the hash afresh (the pass the safe-schedule fallback repeats too)
     int brc = b3_begin(s->b3_eval, n_inst, s->plan ? s->plan->n_ct : s->replays * g.n_ct, seg_records, s->pass.b3_subtree_log2);
     if (brc) return brc;
@@ -162,7 +183,20 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
   up.finish();
   if (digests) {  // (before the MACs are written: a failure leaves both arrays untouched)
     rc = p.b3.flush();
-    if (rc == GSV_OK) rc = b3_finish(*s->b3_eval, s->e->stream.get(), digests);
+    if (rc == GSV_OK && !vf) rc = b3_finish(*s->b3_eval, s->e->stream.get(), digests);
+    if (rc == GSV_OK && vf) {
+      // the end of a verified pass: the chunk values behind the last complete group against the outboards, then the computed digests
+      // against the commitments (the last chunk was read before the pass; what was uploaded is what counts)
+      std::vector<uint8_t> got(n_inst * 32);
+      B3Check& c = vf->check;
+      rc = b3_finish(*s->b3_eval, s->e->stream.get(), got.data(), [&](const uint8_t* vals, uint32_t pend) { return c.pending_match(vals, pend) ? GSV_OK : p.b3.mismatch(); });
+      for (size_t i = 0; i < n_inst && rc == GSV_OK; ++i)
+        if (std::memcmp(got.data() + 32 * i, vf->expected + vf->expected_len * i, size_t(vf->expected_len)) != 0) {
+          c.bad_instance = i; c.bad_group = c.n_groups; c.bad_record = (Outboard::chunks(c.n_records) - 1) * 64;
+          rc = p.b3.mismatch();
+        }
+      if (rc == GSV_OK) std::memcpy(digests, got.data(), got.size());
+    }
     if (rc) return rc;
   }
   if (hashes) up.digests(hashes);
@@ -171,17 +205,18 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
 // The evaluator's side of the safe-schedule fallback (engine_drain.ipp, fall_back_to_safe_schedule): a pass that ended with a dependency wait
 // giving up switches the session to one call per launch; a source that can be read again from the start (gc files) is then evaluated
 // again at once, any other source gets the error with the remedy (its records have been consumed) and the host's repeat succeeds.
-static int evaluate_streaming_impl(gsv_session* s, uint64_t gate_id_base, const std::function<int(size_t, uint64_t, uint8_t*, uint64_t)>& read, uint8_t* hashes, uint8_t* digests, bool rereadable = false) {
-  int rc = evaluate_streaming_pass(s, gate_id_base, read, hashes, digests);
+static int evaluate_streaming_impl(gsv_session* s, uint64_t gate_id_base, const std::function<int(size_t, uint64_t, uint8_t*, uint64_t)>& read, uint8_t* hashes, uint8_t* digests, bool rereadable = false, EvalVerify* vf = nullptr) {
+  int rc = evaluate_streaming_pass(s, gate_id_base, read, hashes, digests, vf);
   if (rc != GSV_ERR_DEVICE || !s->plan || !s->dep_fault || s->safe_mode) return rc;
   const std::string first_error = g_err;
   if (fall_back_to_safe_schedule(s)) return fail(GSV_ERR_DEVICE, first_error + "; the fall-back to the safe schedule failed too: " + g_err);
   if (!rereadable) return fail(GSV_ERR_DEVICE, first_error + "; the session now runs the safe schedule (one call per launch): repeat the pass from gsv_session_set_evaluate_inputs");
   if (s->pass.drain_debug || s->pass.plan_debug) std::fprintf(stderr, "plan session: %s -- repeating the evaluation on the safe schedule (one call per launch)\n", first_error.c_str());
-  return evaluate_streaming_pass(s, gate_id_base, read, hashes, digests);
+  return evaluate_streaming_pass(s, gate_id_base, read, hashes, digests, vf);
 }
 // FileSource: instance i reads <dir>/gc_<indexes[i]>.bin (indexes == NULL: first_index + i)
-static int evaluate_from_files(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint64_t first_index, uint8_t* hashes, uint8_t* digests) {
+static int evaluate_from_files(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint64_t first_index, uint8_t* hashes, uint8_t* digests,
+                               const char* outboard_dir = nullptr, const uint8_t* expected = nullptr, uint64_t expected_len = 0) {
   if (!s || !dir) return fail(GSV_ERR_INVALID, "null argument");
   std::vector<FILE*> files(s->n_inst, nullptr);
   struct Closer { std::vector<FILE*>& f; ~Closer() { for (FILE*& q : f) if (q) { std::fclose(q); q = nullptr; } } } closer{files};
@@ -192,12 +227,42 @@ static int evaluate_from_files(gsv_session* s, uint64_t gate_id_base, const char
   }
   // the reads of one instance are sequential in the stream, but the instances alternate: seek when the position is not the expected one
   std::vector<uint64_t> pos(s->n_inst, 0);
+  // Verified mode, before anything is uploaded: every instance's outboard is read and bounds-checked against the SESSION's stream length
+  // and this pass's k, and its root — folded with the file's last chunk, which lies where the session's stream length puts it — must be
+  // the commitment.  No kernel has run when this fails.
+  std::unique_ptr<EvalVerify> vf;
+  if (outboard_dir) {
+    const uint32_t k = s->pass.b3_subtree_log2;
+    if (k > 20) return fail(GSV_ERR_INVALID, "GSV_B3_SUBTREE_LOG2 must be an integer in [0, 20]");
+    const uint64_t total = s->plan ? s->plan->n_ct : s->replays * s->prog().n_ct, dev_chunks = Outboard::chunks(total) - 1;
+    vf.reset(new EvalVerify{B3Check(), expected, expected_len});
+    B3Check& c = vf->check;
+    c.k = k; c.n_records = total; c.n_groups = dev_chunks >> k; c.n_pending = dev_chunks & ((1ull << k) - 1);
+    c.bytes.resize(s->n_inst);
+    s->mismatch = false;
+    std::vector<uint8_t> last(size_t(Outboard::last_chunk_bytes(total)));
+    for (size_t i = 0; i < s->n_inst; ++i) {
+      std::string why;
+      if (!load_outboard(OutboardFiles::path(outboard_dir, indexes ? indexes[i] : first_index + i), k, total, &c.bytes[i], &why)) return fail(GSV_ERR_INVALID, why);
+      if (!last.empty() && (fseeko(files[i], off_t(dev_chunks * 1024), SEEK_SET) != 0 || std::fread(last.data(), 1, last.size(), files[i]) != last.size()))
+        return fail(GSV_ERR_EXHAUSTED, "Ciphertext source exhausted: instance " + std::to_string(i) + " holds fewer than " + std::to_string(total) + " ciphertexts");
+      pos[i] = total;  // (where the file's position stands now: the pass seeks back)
+      Outboard o;
+      uint8_t root[32];
+      if (!Outboard::parse(c.bytes[i].data(), c.bytes[i].size(), &o, &why) || !o.root(last.data(), last.size(), root, &why)) return fail(GSV_ERR_INVALID, why);
+      if (std::memcmp(root, expected + expected_len * i, size_t(expected_len)) != 0) {
+        s->mismatch = true; s->mismatch_instance = i; s->mismatch_group = s->mismatch_record = ~0ull;
+        s->ran = false;
+        return fail(GSV_ERR_MISMATCH, "outboard or last chunk of instance " + std::to_string(i) + " does not match the commitment");
+      }
+    }
+  }
   return evaluate_streaming_impl(s, gate_id_base, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t n) -> int {
     if (pos[i] != first) { if (fseeko(files[i], off_t(first * 16), SEEK_SET) != 0) return 1; pos[i] = first; }
     if (n && std::fread(dst, 16, n, files[i]) != n) return 1;
     pos[i] += n;
     return 0;
-  }, hashes, digests, /*rereadable=*/true);
+  }, hashes, digests, /*rereadable=*/true, vf.get());
 }
 int gsv_session_evaluate_streaming(gsv_session* s, uint64_t gate_id_base, const char* dir, uint64_t first_index, uint8_t* hashes) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
@@ -217,6 +282,25 @@ int gsv_session_evaluate_streaming_source(gsv_session* s, uint64_t gate_id_base,
 int gsv_session_evaluate_streaming_commit(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint64_t first_index, uint8_t* cbcmac_hashes, uint8_t* blake3_digests) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   return evaluate_from_files(s, gate_id_base, dir, indexes, first_index, cbcmac_hashes, blake3_digests);
+}
+// ... and verified against outboards and commitments the caller trusts (include/gsv_engine.h, "BLAKE3 outboards")
+int gsv_session_evaluate_streaming_verified(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint64_t first_index, const char* outboard_dir, const uint8_t* expected,
+                                            uint64_t expected_len, uint8_t* cbcmac_hashes, uint8_t* blake3_digests) {
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
+  if (!s || !dir || !outboard_dir || !expected || !blake3_digests) return fail(GSV_ERR_INVALID, "null argument");
+  if (expected_len != 16 && expected_len != 32) return fail(GSV_ERR_INVALID, "expected_len must be 16 (a truncated digest) or 32");
+  if (s->plan && s->ct_ring)
+    return fail(GSV_ERR_INVALID, "verified streaming is not available for plan sessions over a ciphertext ring (retain_stream = GSV_STREAM_RING): their pass is one launch that waits on the device for the host's "
+                                 "stream position, and a host that stops feeding it would leave that launch to the watchdog; use launch windows (retain_stream = 0)");
+  return evaluate_from_files(s, gate_id_base, dir, indexes, first_index, cbcmac_hashes, blake3_digests, outboard_dir, expected, expected_len);
+}
+int gsv_session_mismatch_info(const gsv_session* s, uint64_t* instance, uint64_t* group, uint64_t* first_record) {
+  if (!s) return fail(GSV_ERR_INVALID, "null session");
+  if (!s->mismatch) return fail(GSV_ERR_INVALID, "the session's last verified pass found no mismatch");
+  if (instance) *instance = s->mismatch_instance;
+  if (group) *group = s->mismatch_group;
+  if (first_record) *first_record = s->mismatch_record;
+  return GSV_OK;
 }
 int gsv_session_evaluate_streaming_source_commit(gsv_session* s, uint64_t gate_id_base, gsv_ct_source_fn source, void* user, uint8_t* cbcmac_hashes, uint8_t* blake3_digests) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)

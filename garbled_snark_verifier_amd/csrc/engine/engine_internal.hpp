@@ -260,6 +260,10 @@ struct gsv_session {
   uint8_t pass_commit = 0;             // commitments of the pass in progress (1 CBC-MAC, 2 BLAKE3): a pass with BLAKE3 carries the same ones in every slice
   std::unique_ptr<B3Stream> b3;        // BLAKE3 commitments of the drained streams: device buffers and per-instance hashers, beside drain->macs (engine_blake3.ipp)
   std::unique_ptr<B3Stream> b3_eval;   // ... of the streams a streaming evaluation reads (gsv_session_evaluate_streaming*_commit): apart from `b3`, which a garbling pass chains from slice to slice
+  // verified streaming evaluation (gsv_session_evaluate_streaming_verified): where the last such pass found a stream that differs from its outboard
+  bool mismatch = false;
+  uint64_t mismatch_instance = 0, mismatch_group = 0, mismatch_record = 0;
+  uint64_t windows_launched = 0;       // plan sessions: windows the last pass launched (gsv_session_windows_launched)
   std::vector<DevBuf> ct_gate_more;    // further gate-order buffers of the drain pipeline (ct_gate is the first)
   DevBuf ct_alt;                       // garble -> evaluate on the device: the second program-order ciphertext block
   std::unique_ptr<PairState> pair;     // ... and its stream / events (created on first use)

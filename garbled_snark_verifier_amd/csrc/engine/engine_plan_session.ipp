@@ -427,6 +427,12 @@ static int launch_plan_window(gsv_session* s, size_t w, uint64_t gate_id_base, b
   for (uint32_t k = win.call0; k < win.call1 && !ka.any_four_wire; ++k) ka.any_four_wire = s->call_prog(k).and_terms == 4;
   int lrc = gsvk_launch_batch(&ka, uint32_t(s->n_inst), win.call1 - win.call0, eval ? 1 : 0, stream);
   if (lrc != 0) return fail(GSV_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipError_t(lrc)));
+  ++s->windows_launched;
+  return GSV_OK;
+}
+int gsv_session_windows_launched(const gsv_session* s, uint64_t* n) {
+  if (!s || !s->plan || !n) return fail(GSV_ERR_INVALID, "null argument / not a plan session");
+  *n = s->windows_launched;
   return GSV_OK;
 }
 // after a synchronisation: did a dependency wait give up?
@@ -498,6 +504,7 @@ static int launch_plan(gsv_session* s, uint64_t gate_id_base, bool eval) {
   HIPCHK(hipSetDevice(s->e->device));
   HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));  // every pass starts with a clean dependency-wait flag
   HIPCHK(hipEventRecord(s->ev0.get(), s->e->stream.get()));
+  s->windows_launched = 0;
   for (size_t w = 0; w < s->sched.windows.size(); ++w) {
     int rc = launch_plan_window(s, w, gate_id_base, eval);
     if (rc) return rc;

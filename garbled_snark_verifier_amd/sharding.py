@@ -126,14 +126,17 @@ def _check_commitment(commitment):
         raise ValueError("commitment must be 'cbcmac' or 'blake3'")
 
 
-def garble_and_commit(circuit, seeds, indexes, engine=None, program=None, replays=1, gc_dir=None, session_kw=None, threads=0, commitment="cbcmac"):
+def garble_and_commit(circuit, seeds, indexes, engine=None, program=None, replays=1, gc_dir=None, session_kw=None, threads=0, commitment="cbcmac", outboard_dir=None):
     """Garbler::create + commit (garbler.rs:191-257) for the given (index, seed) pairs in ONE session: returns the
     [len(seeds), record_len] commit records; with gc_dir the ciphertext streams go to gc_<index>.bin
     (ciphertext_repository.rs:94-127).  Indexes must be consecutive when gc_dir is used.  `program` may be a Plan (the
     verifier): the stream is then drained window by window of the session's schedule.  commitment="blake3": the record's 16-byte
-    ciphertext hash is the truncated BLAKE3 digest of the stream, computed on the device (Blake3Hasher truncates the same way)."""
+    ciphertext hash is the truncated BLAKE3 digest of the stream, computed on the device (Blake3Hasher truncates the same way);
+    outboard_dir then receives the streams' BLAKE3 outboards gc_<index>.b3o (consecutive indexes, as for gc_dir)."""
     from . import Engine, Plan, Program, Session, labels_from_seed
     _check_commitment(commitment)
+    if outboard_dir is not None and commitment != "blake3":
+        raise ValueError("outboard_dir needs commitment='blake3'")
     engine = engine or Engine(0)
     program = program or Program.from_circuit(circuit, chain_feedback=replays > 1)
     n_in = program.info["n_inputs"]
@@ -146,9 +149,10 @@ def garble_and_commit(circuit, seeds, indexes, engine=None, program=None, replay
     else:
         sess = Session(engine, program, B, replays, min(replays, 2) if replays > 1 else 1)
     sess.set_garble_inputs(delta, consts, inputs)
-    if gc_dir is not None:
+    if gc_dir is not None or outboard_dir is not None:
         assert list(indexes) == list(range(indexes[0], indexes[0] + B)), "gc files are numbered first_index + i"
-    hashes = sess.garble_streaming(directory=gc_dir, first_index=int(indexes[0]) if B else 0, threads=threads, commitment=commitment)  # threads: host MAC workers (0 = the engine's default)
+    kw = {"outboard_dir": outboard_dir} if outboard_dir is not None else {}
+    hashes = sess.garble_streaming(directory=gc_dir, first_index=int(indexes[0]) if B else 0, threads=threads, commitment=commitment, **kw)  # threads: host MAC workers (0 = the engine's default)
     if commitment == "blake3":
         hashes = [d[:16] for d in hashes]
     outs = sess.read_outputs()
@@ -183,7 +187,75 @@ def cut_and_choose_commit(circuit, master_seed, total, rank, world, engine=None,
     return table.numpy(), seeds
 
 
-def run_regarbling(commits, to_finalize, seeds, circuit, gc_dir, engine=None, program=None, replays=1, commitment="cbcmac"):
+def _outboard_header(ob):
+    """(k, n_records) of an outboard's 24-byte header (include/gsv_engine.h, "BLAKE3 outboards"), or None."""
+    if len(ob) < 24 or ob[:8] != b"GSVB3OB\n" or int.from_bytes(ob[8:12], "little") != 1:
+        return None
+    return int.from_bytes(ob[12:16], "little"), int.from_bytes(ob[16:24], "little")
+
+
+def _last_chunk(path):
+    """The bytes of a gc file behind its last whole-KiB boundary in front of the end: what no outboard represents."""
+    import os
+    size = os.path.getsize(path)
+    start = (max(1, -(-size // 1024)) - 1) * 1024
+    with open(path, "rb") as f:
+        f.seek(start)
+        return f.read()
+
+
+def _host_file_check(path, outboard_path):
+    """blake3_file with an outboard, on the host: (digest, None) when the file matches its outboard, (digest, group) with the first
+    group of 2^k chunks that differs (the tail behind the last complete group counts as the group after it)."""
+    import os
+    import tempfile
+    from . import GsvError, blake3_file_outboard
+    want = open(outboard_path, "rb").read()
+    head = _outboard_header(want)
+    if head is None or head[0] > 20:
+        raise GsvError("%s is not an outboard" % outboard_path)
+    k = head[0]
+    with tempfile.TemporaryDirectory() as td:
+        mine = os.path.join(td, "file.b3o")
+        digest = blake3_file_outboard(path, k, mine)
+        got = open(mine, "rb").read()
+    if got == want:
+        return digest, None
+    if got[:24] != want[:24] or len(got) != len(want):
+        raise GsvError("%s is not the outboard of a file of this length" % outboard_path)
+    n_groups = (max(1, -(-head[1] // 64)) - 1) >> k
+    v = next(j for j in range((len(got) - 24) // 32) if got[24 + 32 * j:56 + 32 * j] != want[24 + 32 * j:56 + 32 * j])
+    return digest, min(v, n_groups)
+
+
+def _device_file_hashes(engine, paths, outboards):
+    """blake3_files over the received files of the finalized instances: {position: 16-byte hash | "message"}.  A file that differs from
+    its outboard is named and the rest is hashed again without it; a file the device call cannot take (another length than the
+    others, an outboard that is none) goes through the host."""
+    from . import CiphertextMismatch, GsvError, blake3_file, blake3_files
+    out, todo = {}, list(range(len(paths)))
+    while todo:
+        try:
+            got = blake3_files(engine, [paths[j] for j in todo], None if outboards is None else [outboards[j] for j in todo])
+            out.update({j: d[:16] for j, d in zip(todo, got)})
+            break
+        except CiphertextMismatch as e:
+            out[todo.pop(e.instance)] = "ciphertext corrupted (group %d)" % e.group
+        except GsvError:
+            for j in todo:
+                try:
+                    if outboards is None:
+                        out[j] = blake3_file(paths[j])[:16]
+                    else:
+                        d, group = _host_file_check(paths[j], outboards[j])
+                        out[j] = d[:16] if group is None else "ciphertext corrupted (group %d)" % group
+                except Exception as e:  # noqa: BLE001
+                    out[j] = "failed to get ciphertext source: %s" % e
+            break
+    return out
+
+
+def run_regarbling(commits, to_finalize, seeds, circuit, gc_dir, engine=None, program=None, replays=1, commitment="cbcmac", outboard_dir=None):
     """Evaluator::run_regarbling (cut_and_choose/evaluator.rs:83-181).  `commits`: [total, record_len] table of the
     garbler's commit records; `to_finalize`: indexes kept for evaluation; `seeds`: {index: seed} of the OPENED instances.
       * finalized index: its gc_<index>.bin is streamed through the CBC-MAC and compared with the committed ciphertext
@@ -191,21 +263,40 @@ def run_regarbling(commits, to_finalize, seeds, circuit, gc_dir, engine=None, pr
       * opened index: the circuit is garbled again from the revealed seed — all opened instances in one GPU launch —
         and the whole commit record must match ("regarbling failed"); a missing seed is an error ("failed to find seed").
     commitment="blake3": the committed hash is the truncated BLAKE3 digest — the file is hashed with blake3_file, the re-garbling
-    commits the same way.  Returns (ok, errors) with errors = {index: message}; the reference returns Err(()) as soon as any instance fails."""
+    commits the same way.  With an `engine` the finalized instances' files are hashed on the device instead (blake3_files: read in
+    bounded segments, never evaluated); outboard_dir (the outboards gc_<index>.b3o the garbler sent) makes either path compare every
+    group of 2^k chunks with the file's outboard, and a file that differs is reported as "ciphertext corrupted (group g)" — the part
+    to fetch again.  Returns (ok, errors) with errors = {index: message}; the reference returns Err(()) as soon as any instance fails."""
     import os
-    from . import blake3_file, gc_file_name, read_gc_file
+    from . import blake3_file, gc_file_name, outboard_file_name, read_gc_file
     _check_commitment(commitment)
+    if outboard_dir is not None and commitment != "blake3":
+        raise ValueError("outboard_dir needs commitment='blake3'")
     commits = np.asarray(commits, np.uint8)
     errors = {}
     fin = set(int(i) for i in to_finalize)
+    device = {}
+    if commitment == "blake3" and engine is not None:
+        there = [i for i in sorted(fin) if os.path.exists(os.path.join(gc_dir, gc_file_name(i))) and (outboard_dir is None or os.path.exists(os.path.join(outboard_dir, outboard_file_name(i))))]
+        got = _device_file_hashes(engine, [os.path.join(gc_dir, gc_file_name(i)) for i in there],
+                                  None if outboard_dir is None else [os.path.join(outboard_dir, outboard_file_name(i)) for i in there])
+        device = {i: got[j] for j, i in enumerate(there)}
     for index in sorted(fin):
         path = os.path.join(gc_dir, gc_file_name(index))
         try:
-            h = blake3_file(path)[:16] if commitment == "blake3" else read_gc_file(path)[1]
+            if index in device:
+                h = device[index]
+            elif commitment == "blake3" and outboard_dir is not None:
+                h, group = _host_file_check(path, os.path.join(outboard_dir, outboard_file_name(index)))
+                h = h[:16] if group is None else "ciphertext corrupted (group %d)" % group
+            else:
+                h = blake3_file(path)[:16] if commitment == "blake3" else read_gc_file(path)[1]
         except Exception as e:  # FileSource::from_path failing (ciphertext_source.rs:36-60)
             errors[index] = "failed to get ciphertext source: %s" % e
             continue
-        if bytes(h) != bytes(commits[index, 8:24]):
+        if isinstance(h, str):
+            errors[index] = h
+        elif bytes(h) != bytes(commits[index, 8:24]):
             errors[index] = "ciphertext corrupted"
     opened = [i for i in range(commits.shape[0]) if i not in fin]
     missing = [i for i in opened if i not in seeds]
@@ -228,25 +319,28 @@ class ConsistencyError(Exception):
         self.kind, self.index, self.details = kind, index, details
 
 
-def _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment="cbcmac"):
+def _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment="cbcmac", outboard_dir=None):
     """Default evaluation backend of evaluate_from: EvaluateMode over FileSources on the GPU, ALL finalized instances in one session —
     one launch per window of the stream for the whole batch (gsv_session_evaluate_streaming_indexed).  The reference evaluates the
     cases side by side on a rayon pool (`into_par_iter`, cut_and_choose/evaluator.rs:354-475); a one-instance session per case would
     use one CU of 256 and pay a session per case.  The files' CBC-MACs (the CiphertextMismatch check) are folded while reading, instance i on
     worker i mod T of the engine's pool, beside the uploads (engine.cpp, evaluate_streaming_impl).  commitment="blake3": the hash of a
-    case is the first 16 bytes of its file's BLAKE3 digest instead, computed on the device from the uploaded segments (no MAC worker)."""
+    case is the first 16 bytes of its file's BLAKE3 digest instead, computed on the device from the uploaded segments (no MAC worker).
+    outboard_dir: verified streaming — `run` then takes expected= (the committed 16-byte hashes) and raises CiphertextMismatch, with the
+    position in the batch as its instance, at the first group that differs from its outboard."""
     from . import Engine, Plan, Program, Session
     _check_commitment(commitment)
     eng = engine or Engine(0)
     prog = program or Program.from_circuit(circuit)
 
-    def run(indexes, true_active, false_active, input_active, input_bits):
+    def run(indexes, true_active, false_active, input_active, input_bits, expected=None):
         B = len(indexes)
         sess = Session(eng, prog, B, retain_stream=False) if isinstance(prog, Plan) else Session(eng, prog, B)
         try:
             consts = np.stack([np.asarray(false_active, np.uint8).reshape(B, 16), np.asarray(true_active, np.uint8).reshape(B, 16)], axis=1)
             sess.set_evaluate_inputs(consts, np.asarray(input_active, np.uint8).reshape(B, -1, 16), np.asarray(input_bits, np.uint8).reshape(B, -1))
-            hashes = [h[:16] for h in sess.evaluate_streaming_indexed(gc_dir, [int(i) for i in indexes], commitment=commitment)]
+            kw = {"outboard_dir": outboard_dir, "expected": expected} if outboard_dir is not None else {}
+            hashes = [h[:16] for h in sess.evaluate_streaming_indexed(gc_dir, [int(i) for i in indexes], commitment=commitment, **kw)]
             labels, bits = sess.read_outputs(with_bits=True)
             return [(labels[k], bits[k], hashes[k]) for k in range(B)]
         finally:
@@ -254,7 +348,7 @@ def _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment="cbcmac"):
     return run
 
 
-def evaluate_from(commits, cases, circuit, gc_dir, n_outputs, engine=None, program=None, evaluate=None, evaluate_batch=None, commitment="cbcmac"):
+def evaluate_from(commits, cases, circuit, gc_dir, n_outputs, engine=None, program=None, evaluate=None, evaluate_batch=None, commitment="cbcmac", outboard_dir=None):
     """Evaluator::evaluate_from (cut_and_choose/evaluator.rs:338-476): evaluate the finalized instances from their gc_<i>.bin and
     check everything the evaluator was handed against the garbler's commit record BEFORE trusting the result.
     `cases`: list of dicts {index, true_constant_wire[16], false_constant_wire[16], input_active[n_in,16], input_bits[n_in]}
@@ -270,16 +364,32 @@ def evaluate_from(commits, cases, circuit, gc_dir, n_outputs, engine=None, progr
     case-by-case form tests without a GPU pass (the CPU oracle's).
     commitment="blake3": the table was written with commitment="blake3" (garble_and_commit), the record's hash field is the first 16
     bytes of BLAKE3(gc_<i>.bin), and the default GPU evaluator returns that of the file it read; the stand-ins keep their signature
-    and return whatever hash they choose."""
+    and return whatever hash they choose.
+    outboard_dir (with commitment="blake3"): the garbler's BLAKE3 outboards gc_<i>.b3o lie there and the evaluation is VERIFIED — each
+    outboard, folded with the last chunk of its file, must give the committed hash before anything is evaluated, and the default GPU
+    evaluator stops at the first group of 2^k chunks that differs from its outboard (Session.evaluate_streaming_indexed(outboard_dir=,
+    expected=)).  Either is ConsistencyError("CiphertextMismatch", index) with the group in its message; the checks of the cases in
+    front of that one which need no evaluation still come first.  With a stand-in the up-front check runs here on the host, and the
+    stand-in may raise CiphertextMismatch itself (a batch stand-in: with the position in the batch as its instance)."""
     import os
-    from . import gc_file_name
+    from . import CiphertextMismatch, blake3_outboard_root, gc_file_name, outboard_file_name
     _check_commitment(commitment)
+    if outboard_dir is not None and commitment != "blake3":
+        raise ValueError("outboard_dir needs commitment='blake3'")
     commits = np.asarray(commits, np.uint8)
+    gpu_default = evaluate_batch is None and evaluate is None
     if evaluate_batch is None:
         if evaluate is not None:
-            evaluate_batch = lambda idx, t, f, a, b: [evaluate(idx[k], t[k], f[k], a[k], b[k]) for k in range(len(idx))]  # noqa: E731
+            def evaluate_batch(idx, t, f, a, b):
+                out = []
+                for k in range(len(idx)):
+                    try:
+                        out.append(evaluate(idx[k], t[k], f[k], a[k], b[k]))
+                    except CiphertextMismatch as e:
+                        raise CiphertextMismatch(str(e), k, e.group, e.first_record)
+                return out
         else:
-            evaluate_batch = _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment)
+            evaluate_batch = _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment, outboard_dir)
     n_in_committed = (commits.shape[1] - record_len(n_outputs, 0)) // 32
     parsed, first_error = [], None
     for case in cases:
@@ -303,16 +413,38 @@ def evaluate_from(commits, cases, circuit, gc_dir, n_outputs, engine=None, progr
             break
         parsed.append((index, t_act, f_act, in_act, in_bits, ct_commit, in_commits, out_commits))
     results = []
+
+    def check_input_labels(index, in_act, in_bits, in_commits):
+        actual = commit_labels(in_act)
+        expected = in_commits[np.arange(n_in_committed), in_bits.astype(np.int64) & 1]  # commit_for_value(value)
+        bad = np.nonzero((actual != expected).any(axis=1))[0]
+        if bad.size:
+            k = int(bad[0])
+            raise ConsistencyError("InputLabelsMismatch", index, label_index=k, expected=bytes(expected[k]), actual=bytes(actual[k]))
+
+    def ciphertext_mismatch(pos, **details):
+        """a verified evaluation found case `pos` of the batch bad: the cases in front of it first get the check that needs no evaluation"""
+        for c in parsed[:pos + 1]:
+            check_input_labels(c[0], c[3], c[4], c[6])
+        return ConsistencyError("CiphertextMismatch", parsed[pos][0], **details)
+
+    if parsed and outboard_dir is not None and not gpu_default:
+        for pos, c in enumerate(parsed):  # (the default GPU evaluator makes this check itself, before it uploads anything)
+            try:
+                root = blake3_outboard_root(open(os.path.join(outboard_dir, outboard_file_name(c[0])), "rb").read(), _last_chunk(os.path.join(gc_dir, gc_file_name(c[0]))))
+            except Exception as e:  # noqa: BLE001 - no outboard, or a malformed one
+                raise ciphertext_mismatch(pos, outboard=str(e))
+            if root[:16] != bytes(c[5]):
+                raise ciphertext_mismatch(pos, outboard="outboard or last chunk does not match the commitment")
     if parsed:
-        evaluated = evaluate_batch([c[0] for c in parsed], np.stack([c[1] for c in parsed]), np.stack([c[2] for c in parsed]),
-                                   np.stack([c[3] for c in parsed]), np.stack([c[4] for c in parsed]))
+        kw = {"expected": [bytes(c[5]) for c in parsed]} if gpu_default and outboard_dir is not None else {}
+        try:
+            evaluated = evaluate_batch([c[0] for c in parsed], np.stack([c[1] for c in parsed]), np.stack([c[2] for c in parsed]),
+                                       np.stack([c[3] for c in parsed]), np.stack([c[4] for c in parsed]), **kw)
+        except CiphertextMismatch as e:
+            raise ciphertext_mismatch(e.instance, group=e.group, first_record=e.first_record, message=str(e))
         for (index, _t, _f, in_act, in_bits, ct_commit, in_commits, out_commits), (out_act, out_bits, file_hash) in zip(parsed, evaluated):
-            actual = commit_labels(in_act)
-            expected = in_commits[np.arange(n_in_committed), in_bits.astype(np.int64) & 1]  # commit_for_value(value)
-            bad = np.nonzero((actual != expected).any(axis=1))[0]
-            if bad.size:
-                k = int(bad[0])
-                raise ConsistencyError("InputLabelsMismatch", index, label_index=k, expected=bytes(expected[k]), actual=bytes(actual[k]))
+            check_input_labels(index, in_act, in_bits, in_commits)
             if bytes(file_hash) != bytes(ct_commit):
                 raise ConsistencyError("CiphertextMismatch", index, expected=bytes(ct_commit), actual=bytes(file_hash))
             out_act = np.asarray(out_act, np.uint8).reshape(-1, 16)

@@ -37,7 +37,8 @@ typedef enum gsv_status {
   GSV_ERR_INVALID = 1,   /* bad argument / state */
   GSV_ERR_CIRCUIT = 2,   /* what the reference would panic! on (missing wire, arity mismatch, ...) */
   GSV_ERR_DEVICE = 3,    /* HIP failure or no gfx950 device: the engine has NO CPU fallback */
-  GSV_ERR_EXHAUSTED = 4  /* ciphertext source exhausted (evaluate_mode.rs:141) */
+  GSV_ERR_EXHAUSTED = 4, /* ciphertext source exhausted (evaluate_mode.rs:141) */
+  GSV_ERR_MISMATCH = 5   /* a received ciphertext stream does not match its BLAKE3 outboard / commitment ("BLAKE3 outboards" below) */
 } gsv_status;
 
 /* Gate record = reference `Gate` (src/core/gate.rs:7-12) with u64 wire ids; `gate_type` is the
@@ -498,6 +499,86 @@ int gsv_engine_blake3_streams(gsv_engine* e, const uint8_t* data, uint64_t n_str
  * hash kernel to the last (HIP events on the engine's stream: the upload in front and the host's finish behind are outside; with
  * several segments the host's folding between them is inside). */
 int gsv_engine_blake3_streams_seconds(const gsv_engine* e, double* seconds);
+
+/* ---- BLAKE3 outboards ----------------------------------------------------------------------------------------------------------
+ * The values the host absorbs when a stream is hashed on the device, kept instead of thrown away: for a stream of L records,
+ * N = max(1, ceil(L / 64)) chunks and groups of G = 2^k chunks, the outboard of one instance is the file gc_<i>.b3o beside gc_<i>.bin:
+ *
+ *     bytes  0 ..  7   magic: the eight bytes "GSVB3OB\n" (47 53 56 42 33 4f 42 0a)
+ *     bytes  8 .. 11   format version, 1, little-endian
+ *     bytes 12 .. 15   k (0 .. 20), little-endian
+ *     bytes 16 .. 23   n_records = L, little-endian
+ *     then             floor((N - 1) / G) group values, 32 bytes each, in stream order: the chaining value of the subtree over
+ *                      chunks [g G, (g + 1) G) (k = 0: the chunk's own chaining value)
+ *     then             (N - 1) mod G chunk values, 32 bytes each: the chunks behind the last complete group
+ *
+ * and nothing else: 24 + 32 (floor((N - 1) / G) + (N - 1) mod G) bytes, 1.5 MB for a 47.7 GB stream at k = 10.  The last chunk is not
+ * represented; it is always given as bytes, as for gsv_blake3_finalize.  This is a format of this project's own, ONE level of the
+ * tree; it is NOT Bao and no Bao tool reads it.  An outboard is checked against the 32-byte commitment by folding it with the last
+ * chunk (microseconds); after that every value vouches for its 2^k KiB of the stream on its own, so a received stream is verified
+ * group by group, a bad one is named by (instance, group), and that part of the file can be fetched again.
+ *
+ * gsv_blake3_outboard_root: parses and bounds-checks `outboard` and folds it with the last chunk's bytes into the root.  Refused with
+ * GSV_ERR_INVALID and a message that names what is wrong, before anything is sized by a header field: a wrong magic or version, k above
+ * 20, a byte length other than the one k and n_records make, and a last chunk that is not the 16 .. 1024 bytes (whole records) the
+ * stream's n_records leave behind its chunks (0 bytes for the empty stream only).
+ * gsv_blake3_file_outboard: the host writer for a file that already exists (whole 16-byte records): writes its outboard for groups of
+ * 2^k chunks to outboard_path (NULL: nowhere) and returns the file's digest — for a receiver whose peer sent no outboard, and the twin
+ * the device paths are tested against. */
+int gsv_blake3_outboard_root(const uint8_t* outboard, uint64_t n_bytes, const uint8_t* last_chunk, uint64_t last_chunk_bytes, uint8_t* out /* 32 */);
+int gsv_blake3_file_outboard(const char* path, uint32_t k, const char* outboard_path, uint8_t* out /* 32 */);
+/* gsv_session_garble_streaming_commit that also writes <outboard_dir>/gc_<first_index + i>.b3o for the drained instances
+ * (gsv_session_set_drain_instances: for those only), k = GSV_B3_SUBTREE_LOG2 of the pass: the group values as the host's absorbers
+ * receive them, the pending chunk values when the pass ends.  Needs blake3_digests (GSV_ERR_INVALID otherwise); outboard_dir == NULL
+ * is gsv_session_garble_streaming_commit.  A slice that starts at call 0 truncates the files and writes their headers, later slices
+ * append; a failed call removes them as it removes its gc files, and the pass the safe-schedule fallback repeats writes them anew. */
+int gsv_session_garble_streaming_commit_outboard(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* dir, uint64_t first_index, int n_threads,
+                                                 uint8_t* cbcmac_hashes, uint8_t* blake3_digests, const char* outboard_dir);
+/* Received files verified on the device, without evaluating them: n_files files of the same length (GSV_ERR_INVALID otherwise; whole
+ * 16-byte records) are read in bounded segments through two page-locked staging buffers — the read of a piece overlaps the upload of
+ * the piece before, the whole input is never resident — and hashed as n streams by the chunk and reduce kernels of the drain.  A
+ * segment holds GSV_DRAIN_SEGMENT_RECORDS records per file (default: 16 MiB per file, within 256 MiB for all of them).  digests
+ * receives n_files x 32 bytes.  With outboard_paths (n_files paths, or NULL) every outboard is first checked to be well-formed for
+ * the files' length and this engine's k (GSV_B3_SUBTREE_LOG2; GSV_ERR_INVALID otherwise); every group value is then compared with it
+ * as it arrives, the pending chunk values at the end.  The first difference ends the call with GSV_ERR_MISMATCH, *bad_file_out = the
+ * index into `paths` and *bad_group_out = the group (the tail behind the last complete group counts as the group after it); digests
+ * is written only when everything matched.  The last chunk of a file is vouched for by its digest alone: compare it with the commitment. */
+int gsv_engine_blake3_files(gsv_engine* e, const char* const* paths, uint64_t n_files, const char* const* outboard_paths /* or NULL */, uint8_t* digests /* n_files x 32 */,
+                            uint64_t* bad_file_out /* or NULL */, uint64_t* bad_group_out /* or NULL */);
+/* Verified streaming evaluation: gsv_session_evaluate_streaming_commit over files whose outboards lie in outboard_dir
+ * (<outboard_dir>/gc_<index>.b3o), against commitments the caller already trusts: expected = n_instances x expected_len bytes,
+ * expected_len 32 or 16 (the first 16 bytes of the digest, as a CiphertextCommit holds them).  blake3_digests is required.
+ *
+ * Before anything is uploaded, for every instance: the outboard and the last chunk of gc_<index>.bin (at the place the SESSION's stream
+ * length puts it) are read; a header whose n_records is not the session's stream length, or whose k is not this pass's
+ * GSV_B3_SUBTREE_LOG2, is GSV_ERR_INVALID (the message names both values); the root of gsv_blake3_outboard_root must equal the first
+ * expected_len bytes of expected[i], else the call ends with GSV_ERR_MISMATCH, "outboard or last chunk of instance i does not match the
+ * commitment", and no kernel has run.
+ * During the pass the group values of every uploaded segment are absorbed as ever — the digests returned are computed, not copied —
+ * and compared with the outboards: before a window (program sessions: a ring) is launched the host has compared every group value the
+ * segments uploaded so far have produced.  The first difference ends the pass: nothing further is uploaded or launched, the status is
+ * GSV_ERR_MISMATCH, gsv_session_mismatch_info names the place, gsv_session_read_outputs fails as after a pass that never ran, and both
+ * digest arrays stay untouched (as for GSV_ERR_EXHAUSTED).
+ * THE GUARANTEE.  Groups straddle segments and windows.  When a window is launched, the records of the ONE group per instance that is
+ * still open at that point — fewer than 2^k chunks — are evaluated before they are verified; they are verified with the next
+ * segment, or, at the end of the pass, with the pending chunk values and the digest (compared with `expected` once more).  Every other
+ * record a launch reads has been verified before the launch.  No output is ever RETURNED for a stream that did not verify: a
+ * difference found at the end of the pass ends the call like any other.
+ * Plan sessions over a ciphertext ring (retain_stream = GSV_STREAM_RING) are refused with GSV_ERR_INVALID: their whole pass is one
+ * launch that waits on the device for the host's stream position, and a host that stopped feeding it would leave that launch to the
+ * watchdog.  The pass the safe-schedule fallback repeats restarts the verification from group 0.  The generic source
+ * (gsv_session_evaluate_streaming_source*) has no verified form: its last chunk is not available up front. */
+int gsv_session_evaluate_streaming_verified(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes /* NULL: first_index + i */, uint64_t first_index,
+                                            const char* outboard_dir, const uint8_t* expected, uint64_t expected_len /* 16 or 32 */,
+                                            uint8_t* cbcmac_hashes /* or NULL */, uint8_t* blake3_digests);
+/* Where the session's last verified pass ended with GSV_ERR_MISMATCH: the instance, the group (2^k chunks; the tail behind the last
+ * complete group counts as the group after it) and the first record the differing value covers.  A difference found before the pass
+ * (the outboard or the last chunk against the commitment) has no place: *group = *first_record = UINT64_MAX.  GSV_ERR_INVALID when
+ * the last verified pass found nothing. */
+int gsv_session_mismatch_info(const gsv_session* s, uint64_t* instance, uint64_t* group, uint64_t* first_record);
+/* Plan sessions: windows of the schedule launched by the session's last pass (a verified pass that ended early launched fewer than
+ * gsv_plan_schedule_info.n_windows). */
+int gsv_session_windows_launched(const gsv_session* s, uint64_t* n);
 
 #ifdef __cplusplus
 }

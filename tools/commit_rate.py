@@ -4,6 +4,7 @@ device with BLAKE3 (DESIGN.md §3 "Commitment stage", §6), and the stand-alone 
 
     python tools/commit_rate.py [--instances 64,1024] [--rounds 2] [--kernel-gib 1] [--out profiles/commit_blake3]
     python tools/commit_rate.py --evaluator [--resident-instances 4] [--evaluate-instances 16] [--out profiles/commit_blake3]
+    python tools/commit_rate.py --receive [--rounds 3] [--evaluate-instances 16] [--parent-so <the parent commit's libgsv_engine.so>] [--out profiles/verified_receive]
 
 The driver touches no GPU.  Every GPU step is a child process of this file under its own `timeout`:
   kernel   gsv.blake3_streams on 16 streams of --kernel-gib GiB each, one segment: device seconds from the first hash kernel to the last
@@ -21,6 +22,10 @@ The driver touches no GPU.  Every GPU step is a child process of this file under
   evaluate (--evaluator) fq12_mix, --batch instances: gc files written by a garbling pass, then evaluate_streaming with
            commitment="cbcmac" and "blake3" in turn: wall seconds and host CPU seconds (user + system of the process) per pass;
            digests and MACs equal the garbler's.
+  receive  (--receive) the receiving side, fq12_mix, --evaluate-instances instances: gc files and outboards written once by a garbling pass,
+           then --rounds times, alternating, the parent library's evaluate_streaming(commitment="blake3") (--parent-so: the yardstick of
+           the verified mode) and this library's legs — blake3_file over all files on the host, blake3_files on the device with and
+           without outboards, evaluate_streaming unverified and verified: wall and host CPU seconds per leg, into <out>/receive_rate.{json,log}.
 --evaluator runs these two only (the evaluator's and the resident halves), into <out>/evaluator_rate.{json,log}.
 A child that fails, is killed at its time limit or dies ends the run: nothing more is started on the GPU.  At most 16 host threads
 (--threads) serve a drain.  Results: <out>/commit_rate.json and <out>/commit_rate.log.  Batches run in ascending order; one whose CBC-MAC
@@ -267,7 +272,157 @@ def child_evaluate(a):
     return 0 if ok else 1
 
 
+def _receive_case(np, gsv, B):
+    plan = gsv.Plan.from_circuit("fq12_mix", ["fq12::mul_montgomery", "fq12::square_montgomery"])
+    n_in = plan.info["n_inputs"]
+    labs = [gsv.labels_from_seed(s, n_in) for s in range(1, B + 1)]
+    delta = np.stack([x[0] for x in labs]); consts = np.stack([np.stack([x[1], x[2]]) for x in labs]); inputs = np.stack([x[3] for x in labs])
+    bits = np.random.default_rng(1).integers(0, 2, (B, n_in)).astype(np.uint8)
+    return plan, delta, consts, inputs, bits
+
+
+def child_receive_files(a):
+    """--receive: the gc files and outboards every leg reads, written once into --dir by a garbling pass of this library."""
+    np, bs, gsv, eng = _child_setup()
+    B = a.batch
+    plan, delta, consts, inputs, _ = _receive_case(np, gsv, B)
+    g = gsv.Session(eng, plan, B, retain_stream=False)
+    g.set_garble_inputs(delta, consts, inputs)
+    t0 = time.perf_counter()
+    digests = g.garble_streaming(directory=a.dir, threads=a.threads, commitment="blake3", outboard_dir=a.dir)
+    dt = time.perf_counter() - t0
+    np.save(os.path.join(a.dir, "out0.npy"), g.read_outputs())
+    g.close()
+    json.dump([x.hex() for x in digests], open(os.path.join(a.dir, "digests.json"), "w"))
+    sizes = [os.path.getsize(os.path.join(a.dir, gsv.outboard_file_name(i))) for i in range(B)]
+    same = all(open(os.path.join(a.dir, gsv.outboard_file_name(i)), "rb").read() == _host_outboard(gsv, a.dir, i) for i in (0, B - 1))
+    print(json.dumps({"step": "receive_files", "circuit": "fq12_mix", "instances": B, "ciphertexts_per_instance": plan.info["n_ciphertexts"], "file_bytes": B * plan.info["n_ciphertexts"] * 16,
+                      "outboard_bytes_per_instance": sizes[0], "garble_seconds": dt, "files_in": a.dir, "outboards_equal_the_host_writers": same}), flush=True)
+    return 0 if same else 1
+
+
+def _host_outboard(gsv, d, i):
+    path = os.path.join(d, "host_%d.b3o" % i)
+    gsv.blake3_file_outboard(os.path.join(d, gsv.gc_file_name(i)), 10, path)
+    data = open(path, "rb").read()
+    os.remove(path)
+    return data
+
+
+def child_receive_legs(a):
+    """--receive: one round of the legs over the files in --dir, each after a warm run of its own: the host loop (blake3_file over all
+    files), blake3_files on the device with and without outboards, evaluate_streaming(commitment="blake3") unverified and verified.
+    With the parent commit's library (--parent-so) the unverified evaluation alone runs (the yardstick of the verified mode)."""
+    import ctypes
+    import resource
+    parent = os.environ.get("GSV_RECEIVE_PARENT") == "1"  # (set by the driver, with GSV_ENGINE_SO naming that library)
+    if parent:
+        # the parent's library lacks the entry points this change adds: they get a stand-in that is never called
+        import garbled_snark_verifier_amd as g0
+
+        class _Missing:
+            argtypes = restype = None
+
+        class _Compat:
+            def __init__(self, so):
+                self._l = ctypes.CDLL(so)
+
+            def __getattr__(self, name):
+                try:
+                    return getattr(self._l, name)
+                except AttributeError:
+                    return _Missing()
+        g0.C = type("C", (), dict(vars(ctypes), CDLL=_Compat))
+    np, bs, gsv, eng = _child_setup()
+    B = a.batch
+    plan, delta, consts, inputs, bits = _receive_case(np, gsv, B)
+    active = np.where(bits[:, :, None] == 1, inputs ^ delta[:, None, :], inputs)
+    consts_active = np.stack([consts[:, 0], consts[:, 1] ^ delta], axis=1)
+    digests = [bytes.fromhex(x) for x in json.load(open(os.path.join(a.dir, "digests.json")))]
+    out0 = np.load(os.path.join(a.dir, "out0.npy"))
+    files = [os.path.join(a.dir, gsv.gc_file_name(i)) for i in range(B)]
+    obs = [os.path.join(a.dir, "gc_%d.b3o" % i) for i in range(B)]
+    ev = gsv.Session(eng, plan, B, retain_stream=False)
+
+    def evaluate(**kw):
+        ev.set_evaluate_inputs(consts_active, active, bits)
+        return ev.evaluate_streaming(a.dir, commitment="blake3", **kw)
+
+    legs = {"evaluate_unverified": lambda: evaluate()}
+    if not parent:
+        legs = {"host_blake3_file": lambda: [gsv.blake3_file(f) for f in files],
+                "device_blake3_files_outboards": lambda: gsv.blake3_files(eng, files, obs),
+                "device_blake3_files": lambda: gsv.blake3_files(eng, files),
+                "evaluate_unverified": lambda: evaluate(),
+                "evaluate_verified": lambda: evaluate(outboard_dir=a.dir, expected=digests)}
+    out, ok = {}, True
+    for name, run in legs.items():
+        if name != "host_blake3_file":
+            ok = ok and run() == digests  # warm: first launches, allocations, the page cache
+        r0, t0 = resource.getrusage(resource.RUSAGE_SELF), time.perf_counter()
+        got = run()
+        dt, r1 = time.perf_counter() - t0, resource.getrusage(resource.RUSAGE_SELF)
+        ok = ok and got == digests
+        out[name] = {"wall_seconds": dt, "cpu_seconds": (r1.ru_utime + r1.ru_stime) - (r0.ru_utime + r0.ru_stime)}
+        if name.startswith("evaluate"):
+            act, ob = ev.read_outputs(with_bits=True)
+            ok = ok and bool((act == np.where(ob[:, :, None] == 1, out0 ^ delta[:, None, :], out0)).all())
+    ev.close()
+    print(json.dumps({"step": "receive_legs", "library": "parent" if parent else "this", "instances": B, "file_bytes": sum(os.path.getsize(f) for f in files), "legs": out,
+                      "digests_equal_the_garblers_and_outputs_select": ok}), flush=True)
+    return 0 if ok else 1
+
+
+def driver_receive(a):
+    """--receive: the files once, then --rounds times the parent library's unverified evaluation (with --parent-so) and this library's
+    legs, alternating; medians, and for the evaluator the parent's own run-to-run spread, go to <out>/receive_rate.json."""
+    import shutil
+    import tempfile
+    os.makedirs(a.out, exist_ok=True)
+    log_f = open(os.path.join(a.out, "receive_rate.log"), "w")
+    root = "/dev/shm" if os.path.isdir("/dev/shm") else tempfile.gettempdir()
+    d = tempfile.mkdtemp(prefix="gsv_receive_rate_", dir=root)
+    results, stopped = [], None
+
+    def step(name, seconds, env=None):
+        nonlocal stopped
+        if stopped:
+            return None
+        cmd = ["timeout", "-k", "10", str(seconds), sys.executable, os.path.relpath(os.path.abspath(__file__), ROOT), "--child", name, "--threads", str(a.threads), "--batch", str(a.evaluate_instances), "--dir", d]
+        log_f.write("$ " + " ".join(["python"] + cmd[5:]) + (" (parent library)" if env else "") + "\n"); log_f.flush()
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=log_f, text=True, cwd=ROOT, env=dict(os.environ, **(env or {})))
+        log_f.write(p.stdout); log_f.flush()
+        results.extend(json.loads(l) for l in p.stdout.splitlines() if l.startswith("{"))
+        if p.returncode != 0:
+            stopped = "%s ended with status %d: nothing more was started" % (name, p.returncode)
+
+    try:
+        step("receive_files", 600)
+        for _ in range(a.rounds):
+            if a.parent_so:
+                step("receive_legs", 300, {"GSV_ENGINE_SO": os.path.abspath(a.parent_so), "GSV_RECEIVE_PARENT": "1"})
+            step("receive_legs", 600)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    summary = {}
+    for r in results:
+        if r.get("step") == "receive_legs":
+            for k, v in r["legs"].items():
+                s = summary.setdefault(r["library"] + ":" + k, {"wall_seconds": [], "cpu_seconds": []})
+                s["wall_seconds"].append(v["wall_seconds"]); s["cpu_seconds"].append(v["cpu_seconds"])
+    n_bytes = next((r["file_bytes"] for r in results if r.get("step") == "receive_files"), 0)
+    for s in summary.values():
+        s["wall_seconds_median"], s["cpu_seconds_median"] = _median(s["wall_seconds"]), _median(s["cpu_seconds"])
+        s["wall_seconds_spread"] = max(s["wall_seconds"]) - min(s["wall_seconds"])
+        s["bytes_per_s_median"] = n_bytes / s["wall_seconds_median"] if s["wall_seconds_median"] else None
+    json.dump({"results": results, "summary": summary, "stopped": stopped}, open(os.path.join(a.out, "receive_rate.json"), "w"), indent=1)
+    print(json.dumps({"summary": summary, "stopped": stopped}))
+    return 1 if stopped else 0
+
+
 def driver(a):
+    if a.receive:
+        return driver_receive(a)
     os.makedirs(a.out, exist_ok=True)
     log_f = open(os.path.join(a.out, "evaluator_rate.log" if a.evaluator else "commit_rate.log"), "w")
     results, stopped = [], None
@@ -341,8 +496,12 @@ if __name__ == "__main__":
     ap.add_argument("--evaluator", action="store_true")
     ap.add_argument("--resident-instances", type=int, default=4)
     ap.add_argument("--evaluate-instances", type=int, default=16)
-    ap.add_argument("--child", choices=["kernel", "check", "round", "file", "resident", "evaluate"])
+    ap.add_argument("--receive", action="store_true")
+    ap.add_argument("--parent-so", default=None)
+    ap.add_argument("--dir", default=None)
+    ap.add_argument("--child", choices=["kernel", "check", "round", "file", "resident", "evaluate", "receive_files", "receive_legs"])
     ap.add_argument("--batch", type=int, default=64)
     a = ap.parse_args()
     a.threads = max(1, min(16, a.threads))
-    sys.exit({"kernel": child_kernel, "check": child_check, "round": child_round, "file": child_file, "resident": child_resident, "evaluate": child_evaluate, None: driver}[a.child](a))
+    sys.exit({"kernel": child_kernel, "check": child_check, "round": child_round, "file": child_file, "resident": child_resident, "evaluate": child_evaluate, "receive_files": child_receive_files,
+              "receive_legs": child_receive_legs, None: driver}[a.child](a))
