@@ -31,6 +31,18 @@ pub struct GpuEvaluateMode<SRC: CiphertextSource> {
     output_index: HashMap<WireId, usize>,
     results: Vec<EvaluatedWire>,
     device: i32,
+    verify: Option<GpuVerification>,
+}
+
+/// What `with_verification` checks the received stream against (gsv_session_evaluate_streaming_source_verified): the peer's outboard
+/// and the commitment this side already trusts (32 bytes, or the first 16).  With `last_chunk` the outboard is authenticated against the
+/// commitment before the source is asked for anything; without it the outboard is checked for form only and the commitment is compared
+/// at the end of the pass — until then a forged outboard with a matching forged stream is evaluated, and rejected only then.
+#[derive(Debug, Clone)]
+pub struct GpuVerification {
+    pub outboard: Vec<u8>,
+    pub expected: Vec<u8>,
+    pub last_chunk: Option<Vec<u8>>,
 }
 
 impl<SRC: CiphertextSource> std::fmt::Debug for GpuEvaluateMode<SRC> {
@@ -48,8 +60,11 @@ impl<SRC: CiphertextSource> GpuEvaluateMode<SRC> {
         Self::over(GpuRecorder::plan(units, window_div, plan_file), true_wire, false_wire, source)
     }
     fn over(rec: GpuRecorder, true_wire: S, false_wire: S, source: SRC) -> Self {
-        Self { rec, source, false_wire, true_wire, inputs: vec![], input_index: HashMap::new(), output_index: HashMap::new(), results: vec![], device: 0 }
+        Self { rec, source, false_wire, true_wire, inputs: vec![], input_index: HashMap::new(), output_index: HashMap::new(), results: vec![], device: 0, verify: None }
     }
+    /// Verify the stream per group of chunks while it arrives: the pass stops at the first group that differs from the outboard, and
+    /// no output is returned for a stream that did not verify (the panic names instance, group and first record).
+    pub fn with_verification(mut self, v: GpuVerification) -> Self { self.verify = Some(v); self }
 
     fn run(&mut self, outputs: &[WireId]) {
         let (mut engine, mut sess, mut plan, mut prog) = (std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut());
@@ -79,7 +94,25 @@ impl<SRC: CiphertextSource> GpuEvaluateMode<SRC> {
             }
             0
         }
-        chk(unsafe { gsv_session_evaluate_streaming_source(sess, 0, pull::<SRC>, &mut self.source as *mut SRC as *mut std::ffi::c_void, std::ptr::null_mut()) });
+        let user = &mut self.source as *mut SRC as *mut std::ffi::c_void;
+        if let Some(v) = self.verify.as_ref() {
+            let mut last = [0u8; 1024];
+            if let Some(l) = v.last_chunk.as_ref() { last[..l.len()].copy_from_slice(l); }
+            let (ob_ptr, ob_len, mut digest) = ([v.outboard.as_ptr()], [v.outboard.len() as u64], [0u8; 32]);
+            let rc = unsafe {
+                evaluate_streaming_source_verified(sess, 0, pull::<SRC>, user, ob_ptr.as_ptr(), ob_len.as_ptr(), if v.last_chunk.is_some() { last.as_ptr() } else { std::ptr::null() },
+                                                   v.expected.as_ptr(), v.expected.len() as u64, std::ptr::null_mut(), digest.as_mut_ptr())
+            };
+            if rc == GSV_ERR_MISMATCH {
+                let msg = unsafe { std::ffi::CStr::from_ptr(gsv_last_error()) }.to_string_lossy().into_owned();
+                let (mut inst, mut group, mut record) = (0u64, 0u64, 0u64);
+                chk(unsafe { gsv_session_mismatch_info(sess, &mut inst, &mut group, &mut record) });
+                panic!("ciphertext stream does not verify (instance {inst}, group {group}, from record {record}): {msg}"); // group = u64::MAX: the outboard itself
+            }
+            chk(rc);
+        } else {
+            chk(unsafe { gsv_session_evaluate_streaming_source(sess, 0, pull::<SRC>, user, std::ptr::null_mut()) });
+        }
         let (mut out, mut ob) = (vec![0u8; outputs.len() * 16], vec![0u8; outputs.len()]);
         chk(unsafe { gsv_session_read_outputs(sess, out.as_mut_ptr(), ob.as_mut_ptr()) });
         self.results = out.chunks_exact(16).zip(ob.iter()).map(|(b, v)| EvaluatedWire { active_label: S::from_bytes(b.try_into().unwrap()), value: *v != 0 }).collect();

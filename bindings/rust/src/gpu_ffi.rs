@@ -72,7 +72,10 @@ pub struct GsvPlanRecorderOpts {
 pub type GsvCtSinkFn = unsafe extern "C" fn(user: *mut std::ffi::c_void, instance: usize, first_record: u64, records: *const u8, n_records: u64) -> c_int;
 /// CiphertextSource::recv for a run of records (gsv_ct_source_fn): non-zero = the source has run dry.
 pub type GsvCtSourceFn = unsafe extern "C" fn(user: *mut std::ffi::c_void, instance: usize, first_record: u64, records: *mut u8, n_records: u64) -> c_int;
+/// An instance's BLAKE3 outboard as it is produced (gsv_outboard_sink_fn): `bytes` belong at `byte_offset`; offsets only grow, so appending is enough.
+pub type GsvOutboardSinkFn = unsafe extern "C" fn(user: *mut std::ffi::c_void, instance: usize, byte_offset: u64, bytes: *const u8, n_bytes: u64) -> c_int;
 
+pub const GSV_ERR_MISMATCH: c_int = 5; // a received stream differs from its BLAKE3 outboard / commitment (gsv_session_mismatch_info names the place)
 pub const GSV_STREAM_RING: c_int = 2; // GsvPlanSessionOpts::retain_stream: the whole pass as one launch over a ciphertext ring (gsv_engine.h)
 pub const GSV_HASHER_AES: c_int = 0; // AesNiHasher   (src/hashers/mod.rs:54-96)
 pub const GSV_HASHER_BLAKE3: c_int = 1; // Blake3Hasher  (src/hashers/mod.rs:22-51)
@@ -159,6 +162,31 @@ extern "C" {
     pub fn gsv_session_evaluate_streaming_verified(s: *mut GsvSession, gate_id_base: u64, dir: *const c_char, indexes: *const u64, first_index: u64, outboard_dir: *const c_char, expected: *const u8, expected_len: u64, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int;
     pub fn gsv_session_mismatch_info(s: *const GsvSession, instance: *mut u64, group: *mut u64, first_record: *mut u64) -> c_int;
     pub fn gsv_session_windows_launched(s: *const GsvSession, n: *mut u64) -> c_int;
+    // Commitments on the callback paths (include/gsv_engine.h): sizes here, the two session calls below
+    pub fn gsv_blake3_outboard_size(n_records: u64, k: u32, outboard_bytes: *mut u64, last_chunk_bytes: *mut u64) -> c_int;
+}
+
+/// The two session calls of "Commitments on the callback paths".  Their callbacks may be NULL, which a Rust `fn` pointer cannot be —
+/// they are `Option<fn>` here, where gsv_session_garble_streaming_sink takes a plain `GsvCtSinkFn` — and the outboards come as an array
+/// of pointers (`const uint8_t* const*`); the wrappers below are what the modes call.
+mod callback_commit {
+    use super::*;
+    extern "C" {
+        pub(super) fn gsv_session_garble_streaming_sink_commit(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, sink: Option<GsvCtSinkFn>, user: *mut std::ffi::c_void, n_threads: c_int, cbcmac_hashes: *mut u8, blake3_digests: *mut u8, outboard_sink: Option<GsvOutboardSinkFn>, outboard_user: *mut std::ffi::c_void, last_chunks: *mut u8) -> c_int;
+        pub(super) fn gsv_session_evaluate_streaming_source_verified(s: *mut GsvSession, gate_id_base: u64, source: GsvCtSourceFn, user: *mut std::ffi::c_void, outboards: *const *const u8, outboard_bytes: *const u64, last_chunks: *const u8, expected: *const u8, expected_len: u64, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int;
+    }
+}
+/// gsv_session_garble_streaming_sink_commit: the handler's pass with either commitment or both; `outboard_sink` receives every drained
+/// instance's outboard (needs `blake3_digests`), `last_chunks` (n x 1024) the streams' last chunks, zero-padded.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn garble_streaming_sink_commit(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, sink: Option<GsvCtSinkFn>, user: *mut std::ffi::c_void, n_threads: c_int, cbcmac_hashes: *mut u8, blake3_digests: *mut u8, outboard_sink: Option<GsvOutboardSinkFn>, outboard_user: *mut std::ffi::c_void, last_chunks: *mut u8) -> c_int {
+    callback_commit::gsv_session_garble_streaming_sink_commit(s, gate_id_base, first_call, n_calls, sink, user, n_threads, cbcmac_hashes, blake3_digests, outboard_sink, outboard_user, last_chunks)
+}
+/// gsv_session_evaluate_streaming_source_verified: one outboard per instance in memory; `last_chunks` (n x 1024) selects up-front mode,
+/// null the deferred one.  Returns GSV_ERR_MISMATCH for a stream that does not verify: no output is returned for it.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn evaluate_streaming_source_verified(s: *mut GsvSession, gate_id_base: u64, source: GsvCtSourceFn, user: *mut std::ffi::c_void, outboards: *const *const u8, outboard_bytes: *const u64, last_chunks: *const u8, expected: *const u8, expected_len: u64, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int {
+    callback_commit::gsv_session_evaluate_streaming_source_verified(s, gate_id_base, source, user, outboards, outboard_bytes, last_chunks, expected, expected_len, cbcmac_hashes, blake3_digests)
 }
 
 pub fn chk(rc: c_int) {

@@ -40,6 +40,18 @@ pub struct GpuGarbleMode<CTH: CiphertextHandler> {
     results: Vec<S>,                     // label0 per declared output once the GPU has run
     handler: Option<CTH>,
     device: i32,
+    commit_blake3: bool,                 // with_blake3_commitment: commit on the device while the handler receives the stream
+    commitment: Option<GpuCommitment>,
+}
+
+/// What a pass with `with_blake3_commitment` leaves behind: the 32-byte BLAKE3 of the ciphertext stream, computed on the device, its
+/// outboard (this project's one-level format, include/gsv_engine.h "BLAKE3 outboards") and the stream's last chunk — what a peer needs
+/// to verify the stream per MiB while it receives it (`GpuEvaluateMode::with_verification`).
+#[derive(Debug, Clone)]
+pub struct GpuCommitment {
+    pub blake3: [u8; 32],
+    pub outboard: Vec<u8>,
+    pub last_chunk: Vec<u8>,
 }
 
 impl<CTH: CiphertextHandler> std::fmt::Debug for GpuGarbleMode<CTH> {
@@ -61,8 +73,12 @@ impl<CTH: CiphertextHandler> GpuGarbleMode<CTH> {
         let mut rng = ChaChaRng::seed_from_u64(seed);
         let delta = Delta::generate(&mut rng);
         let [false_wire, true_wire] = std::array::from_fn(|_| GarbledWire::random(&mut rng, &delta));
-        Self { rec, rng, delta, false_wire, true_wire, inputs: vec![], input_index: HashMap::new(), output_index: HashMap::new(), results: vec![], handler: Some(handler), device: 0 }
+        Self { rec, rng, delta, false_wire, true_wire, inputs: vec![], input_index: HashMap::new(), output_index: HashMap::new(), results: vec![], handler: Some(handler), device: 0, commit_blake3: false, commitment: None }
     }
+    /// Commit to the stream with BLAKE3 on the device, beside whatever the handler does with it (gsv_session_garble_streaming_sink_commit):
+    /// the host's cores hash nothing but the last chunk.
+    pub fn with_blake3_commitment(mut self) -> Self { self.commit_blake3 = true; self }
+    pub fn commitment(&self) -> Option<&GpuCommitment> { self.commitment.as_ref() }
     pub fn issue_garbled_wire(&mut self) -> GarbledWire { GarbledWire::random(&mut self.rng, &self.delta) } // garble_mode.rs:116-118
 
     /// Compile, garble on the GPU, stream the ciphertexts (gate order) through the handler, fetch the output labels.
@@ -95,7 +111,27 @@ impl<CTH: CiphertextHandler> GpuGarbleMode<CTH> {
             0
         }
         let mut handler = self.handler.take().expect("already finalised");
-        chk(unsafe { gsv_session_garble_streaming_sink(sess, 0, 0, 0, sink::<CTH>, &mut handler as *mut CTH as *mut std::ffi::c_void, 1, std::ptr::null_mut()) });
+        let user = &mut handler as *mut CTH as *mut std::ffi::c_void;
+        if self.commit_blake3 {
+            // the outboard arrives in offset order (one instance: from one thread at a time), so appending is all there is to do
+            unsafe extern "C" fn keep(user: *mut std::ffi::c_void, _instance: usize, offset: u64, bytes: *const u8, n: u64) -> std::os::raw::c_int {
+                let ob = &mut *(user as *mut Vec<u8>);
+                if offset as usize != ob.len() { return 1; }
+                ob.extend_from_slice(std::slice::from_raw_parts(bytes, n as usize));
+                0
+            }
+            let (mut blake3, mut outboard, mut last) = ([0u8; 32], Vec::<u8>::new(), vec![0u8; 1024]);
+            chk(unsafe { garble_streaming_sink_commit(sess, 0, 0, 0, Some(sink::<CTH>), user, 1, std::ptr::null_mut(), blake3.as_mut_ptr(), Some(keep), &mut outboard as *mut Vec<u8> as *mut std::ffi::c_void, last.as_mut_ptr()) });
+            // header: k at bytes 12..16, n_records at 16..24 (little-endian)
+            let (k, n_records) = (u32::from_le_bytes(outboard[12..16].try_into().unwrap()), u64::from_le_bytes(outboard[16..24].try_into().unwrap()));
+            let (mut ob_bytes, mut last_bytes) = (0u64, 0u64);
+            chk(unsafe { gsv_blake3_outboard_size(n_records, k, &mut ob_bytes, &mut last_bytes) });
+            assert_eq!(ob_bytes as usize, outboard.len());
+            last.truncate(last_bytes as usize);
+            self.commitment = Some(GpuCommitment { blake3, outboard, last_chunk: last });
+        } else {
+            chk(unsafe { gsv_session_garble_streaming_sink(sess, 0, 0, 0, sink::<CTH>, user, 1, std::ptr::null_mut()) });
+        }
         self.handler = Some(handler);
         let mut out = vec![0u8; outputs.len() * 16];
         chk(unsafe { gsv_session_read_outputs(sess, out.as_mut_ptr(), std::ptr::null_mut()) });

@@ -12,6 +12,7 @@ reference's entry points for the hot path
 There is no CPU fallback: every garble/evaluate call runs on a HIP device or raises ``GsvError``.
 """
 import atexit
+import collections
 import ctypes as C
 import os
 import sys
@@ -23,7 +24,7 @@ from . import build as _build
 
 __all__ = ["GsvError", "lib", "Program", "Engine", "Session", "CircuitBuilder", "StreamingResult", "labels_from_seed", "GATE_NAMES", "cbcmac", "cbcmac_many",
            "write_gc_file", "read_gc_file", "gc_file_name", "blake3", "blake3_file", "blake3_streams", "Blake3",
-           "CiphertextMismatch", "outboard_file_name", "blake3_outboard_root", "blake3_file_outboard", "blake3_files"]
+           "CiphertextMismatch", "outboard_file_name", "blake3_outboard_root", "blake3_file_outboard", "blake3_files", "blake3_outboard_size", "SinkCommit"]
 
 GATE_NAMES = ["And", "Nand", "Nimp", "Imp", "Ncimp", "Cimp", "Nor", "Or", "Xor", "Xnor", "Not"]
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -140,11 +141,16 @@ EXPORTS = [
     "gsv_session_evaluate_streaming_commit", "gsv_session_evaluate_streaming_source_commit", "gsv_session_ciphertext_blake3",
     "gsv_blake3_outboard_root", "gsv_blake3_file_outboard", "gsv_session_garble_streaming_commit_outboard", "gsv_engine_blake3_files",
     "gsv_session_evaluate_streaming_verified", "gsv_session_mismatch_info", "gsv_session_windows_launched",
+    "gsv_blake3_outboard_size", "gsv_session_garble_streaming_sink_commit", "gsv_session_evaluate_streaming_source_verified",
 ]
 
 # CiphertextHandler / CiphertextSource as host callbacks (include/gsv_engine.h: gsv_ct_sink_fn, gsv_ct_source_fn)
 CT_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64)
 CT_SOURCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64)
+# an instance's BLAKE3 outboard as it is produced (gsv_outboard_sink_fn): (user, instance, byte_offset, bytes, n_bytes)
+OUTBOARD_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64)
+# what Session.garble_to_sink returns with a commitment: lists with one entry per drained instance, or None (see there)
+SinkCommit = collections.namedtuple("SinkCommit", "cbcmac blake3 outboards last_chunks")
 
 
 def lib():
@@ -258,6 +264,9 @@ def lib():
         L.gsv_session_evaluate_streaming_verified.argtypes = [vp, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_char_p, u8p, C.c_uint64, u8p, u8p]
         L.gsv_session_mismatch_info.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3
         L.gsv_session_windows_launched.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.gsv_blake3_outboard_size.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.gsv_session_garble_streaming_sink_commit.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, CT_SINK_FN, vp, C.c_int, u8p, u8p, OUTBOARD_SINK_FN, vp, u8p]
+        L.gsv_session_evaluate_streaming_source_verified.argtypes = [vp, C.c_uint64, CT_SOURCE_FN, vp, C.POINTER(u8p), C.POINTER(C.c_uint64), u8p, u8p, C.c_uint64, u8p, u8p]
         _lib = L
     return _lib
 
@@ -357,6 +366,14 @@ def blake3_outboard_root(outboard, last_chunk):
     out = np.zeros(32, np.uint8)
     _chk(lib().gsv_blake3_outboard_root(_p(ob) if ob.size else _p(np.zeros(1, np.uint8)), ob.size, _p(last) if last.size else None, last.size, _p(out)))
     return out.tobytes()
+
+
+def blake3_outboard_size(n_records, k):
+    """(outboard_bytes, last_chunk_bytes) of a stream of n_records records in groups of 2^k chunks (k <= 20): how many bytes an
+    outboard callback will receive per instance, and how many bytes of a last_chunks entry are the last chunk."""
+    a, b = C.c_uint64(), C.c_uint64()
+    _chk(lib().gsv_blake3_outboard_size(int(n_records), int(k), C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
 
 
 def blake3_file_outboard(path, k, outboard_path=None):
@@ -829,11 +846,26 @@ class Session:
             _chk(lib().gsv_session_garble_streaming_calls(self.h, gate_id_base, first_call, n_calls, directory.encode() if directory else None, first_index, threads, _p(out)))
         return [bytes(out[i]) for i in range(self.n)]
 
-    def garble_to_sink(self, handler, gate_id_base=0, first_call=0, n_calls=0, threads=0, with_hashes=False):
+    def garble_to_sink(self, handler, gate_id_base=0, first_call=0, n_calls=0, threads=0, with_hashes=False, commitment=None, outboards=False):
         """Garble with every ciphertext handed to `handler(instance, first_record, records)` — the generic CiphertextHandler
         (circuit/mod.rs:140-178): `records` is an [n,16] uint8 array in gate order, valid during the call only; the runs of one
         instance arrive in stream order.  Exceptions raised by the handler abort the pass.  Returns the CBC-MACs with
-        with_hashes=True."""
+        with_hashes=True.
+        commitment="cbcmac" | "blake3" | "both" (gsv_session_garble_streaming_sink_commit) returns a SinkCommit(cbcmac, blake3,
+        outboards, last_chunks) instead, one entry per drained instance: `cbcmac` the MAC states after this call (None with
+        "blake3"); `blake3` the 32-byte digests, computed on the device, and `last_chunks` the streams' last chunks as bytes — both
+        None with "cbcmac", and None until the slice that ends the pass; `outboards` (outboards=True, with "blake3" / "both") the
+        BLAKE3 outboards as bytes, accumulated on the session from slice to slice and returned by the slice that ends the pass,
+        None before.  `handler` may then be None: with "blake3" nothing of the stream is copied to the host."""
+        if commitment is None:
+            if outboards:
+                raise ValueError("outboards=True needs commitment='blake3' or 'both': an outboard holds the values of the BLAKE3 commitment")
+            if handler is None:
+                raise ValueError("a handler, a commitment, or both")
+        elif commitment not in ("cbcmac", "blake3", "both"):
+            raise ValueError("commitment must be None, 'cbcmac', 'blake3' or 'both'")
+        elif outboards and commitment == "cbcmac":
+            raise ValueError("outboards=True needs commitment='blake3' or 'both': an outboard holds the values of the BLAKE3 commitment")
         failure = []
 
         def _cb(_user, inst, first, ptr, n):
@@ -844,14 +876,52 @@ class Session:
                 failure.append(e)
                 return 1
 
-        cb = CT_SINK_FN(_cb)
-        out = np.zeros((self.n, 16), np.uint8) if with_hashes else None
+        cb = CT_SINK_FN(_cb) if handler is not None else CT_SINK_FN()
+        if commitment is None:
+            out = np.zeros((self.n, 16), np.uint8) if with_hashes else None
+            with _gc_paused():
+                rc = lib().gsv_session_garble_streaming_sink(self.h, gate_id_base, first_call, n_calls, cb, None, threads, _p(out))
+            if failure:
+                raise failure[0]
+            _chk(rc)
+            return [bytes(out[i]) for i in range(self.n)] if with_hashes else None
+        n = getattr(self, "n_drain", self.n)
+        plan = isinstance(self.program, Plan)
+        ends_pass = (first_call == 0 and n_calls == 0) or not plan or first_call + n_calls == self.schedule_info()["n_calls"]  # (else the engine leaves the digests alone)
+        b3 = commitment != "cbcmac"
+        macs = np.zeros((n, 16), np.uint8) if commitment != "blake3" else None
+        dig = np.zeros((n, 32), np.uint8) if b3 else None
+        last = np.zeros((n, 1024), np.uint8) if b3 else None
+        if outboards and first_call == 0:
+            self._sink_outboards = [bytearray() for _ in range(n)]  # a slice that starts at call 0 starts every outboard again
+        acc = getattr(self, "_sink_outboards", None)
+
+        def _ob(_user, inst, offset, ptr, n_bytes):
+            try:
+                buf = acc[int(inst)]
+                if int(offset) != len(buf):
+                    raise GsvError("outboard of instance %d: bytes at offset %d, %d were expected" % (inst, offset, len(buf)))
+                buf += C.string_at(ptr, int(n_bytes))
+                return 0
+            except BaseException as e:  # noqa: BLE001
+                failure.append(e)
+                return 1
+
+        if outboards and (acc is None or len(acc) != n):
+            raise GsvError("this slice continues a pass whose earlier slices collected no outboards for these instances")
+        ob_cb = OUTBOARD_SINK_FN(_ob) if outboards else OUTBOARD_SINK_FN()
         with _gc_paused():
-            rc = lib().gsv_session_garble_streaming_sink(self.h, gate_id_base, first_call, n_calls, cb, None, threads, _p(out))
+            rc = lib().gsv_session_garble_streaming_sink_commit(self.h, gate_id_base, first_call, n_calls, cb, None, threads, _p(macs), _p(dig), ob_cb, None, _p(last))
         if failure:
             raise failure[0]
         _chk(rc)
-        return [bytes(out[i]) for i in range(self.n)] if with_hashes else None
+        if b3 and ends_pass:
+            total = self.program.info["n_ciphertexts"] * (1 if plan else self.replays)
+            last_bytes = blake3_outboard_size(total, 0)[1]
+        return SinkCommit([bytes(macs[i]) for i in range(n)] if macs is not None else None,
+                          [bytes(dig[i]) for i in range(n)] if b3 and ends_pass else None,
+                          [bytes(x) for x in acc] if outboards and ends_pass else None,
+                          [bytes(last[i, :last_bytes]) for i in range(n)] if b3 and ends_pass else None)
 
     def garble_evaluate(self, evaluator, gate_id_base=0, threads=0, with_hashes=False):
         """Garble this (plan, retain_stream=False) session while `evaluator` — a session of the same plan and options with its inputs
@@ -919,11 +989,41 @@ class Session:
 
         return self._evaluate_commit(commitment, call)
 
-    def evaluate_from_source(self, source, gate_id_base=0, commitment="cbcmac"):
+    def evaluate_from_source(self, source, gate_id_base=0, commitment="cbcmac", outboards=None, expected=None, last_chunks=None):
         """Evaluate with the ciphertexts pulled from `source(instance, first_record, n) -> [n,16] uint8` (None / short = exhausted):
         the generic CiphertextSource (ciphertext_source.rs:14-34).  Returns the CBC-MACs of what was read; commitment as for
-        evaluate_streaming."""
+        evaluate_streaming.
+        Verified (gsv_session_evaluate_streaming_source_verified, with "blake3" / "both"): `outboards` (one bytes object per instance)
+        and `expected` (the commitments, 32 bytes each or the first 16) together.  With `last_chunks` (the streams' last chunks as
+        bytes, as garble_to_sink returns them) the outboards are checked against the commitments before `source` is called at all;
+        without, they are checked for form only and the commitments are compared at the end of the pass — until then the outboards
+        are unauthenticated.  Either way the pass stops at the first group that differs from its outboard: CiphertextMismatch names
+        (instance, group, first_record), and read_outputs then fails."""
         _check_commitment(commitment, False)
+        verified = outboards is not None or expected is not None or last_chunks is not None
+        if verified:
+            if commitment == "cbcmac":
+                raise ValueError("outboards / expected / last_chunks need commitment='blake3' or 'both'")
+            if outboards is None or expected is None:
+                raise ValueError("verified evaluation takes outboards and expected together")
+            obs = [np.frombuffer(bytes(o), np.uint8) for o in outboards]
+            exp = [bytes(e) for e in expected]
+            if len(obs) != self.n:
+                raise ValueError("outboards: one per instance")
+            if len(exp) != self.n or len(set(len(e) for e in exp)) != 1 or len(exp[0]) not in (16, 32):
+                raise ValueError("expected: one commitment of 16 or of 32 bytes per instance")
+            exp_a = np.frombuffer(b"".join(exp), np.uint8)
+            last_a = None
+            if last_chunks is not None:
+                lc = [bytes(x) for x in last_chunks]
+                if len(lc) != self.n or any(len(x) > 1024 for x in lc):
+                    raise ValueError("last_chunks: one per instance, at most 1024 bytes each")
+                last_a = np.zeros((self.n, 1024), np.uint8)
+                for i, x in enumerate(lc):
+                    last_a[i, :len(x)] = np.frombuffer(x, np.uint8)
+            nothing = np.zeros(1, np.uint8)
+            ob_p = (C.POINTER(C.c_uint8) * self.n)(*[_p(o) if o.size else _p(nothing) for o in obs])
+            ob_n = (C.c_uint64 * self.n)(*[o.size for o in obs])
         failure = []
 
         def _cb(_user, inst, first, ptr, n):
@@ -944,12 +1044,16 @@ class Session:
 
         def call(macs, dig):
             with _gc_paused():
-                if dig is None:
+                if verified:
+                    rc = lib().gsv_session_evaluate_streaming_source_verified(self.h, gate_id_base, cb, None, ob_p, ob_n, _p(last_a), _p(exp_a), len(exp[0]), _p(macs), _p(dig))
+                elif dig is None:
                     rc = lib().gsv_session_evaluate_streaming_source(self.h, gate_id_base, cb, None, _p(macs))
                 else:
                     rc = lib().gsv_session_evaluate_streaming_source_commit(self.h, gate_id_base, cb, None, _p(macs), _p(dig))
             if failure:
                 raise failure[0]
+            if rc == 5:
+                raise CiphertextMismatch("gsv status 5: %s" % lib().gsv_last_error().decode(errors="replace"), *self.mismatch_info())
             _chk(rc)
 
         return self._evaluate_commit(commitment, call)

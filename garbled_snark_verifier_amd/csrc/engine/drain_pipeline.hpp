@@ -1,5 +1,5 @@
 // The host side of the streaming drain (engine_drain.ipp): the session's copy streams, pinned chunk buffers and MAC states; where a
-// drained stream goes; the gc_<i>.bin files of a pass and its gc_<i>.b3o outboards; the pool of MAC / copy workers behind a queue of
+// drained stream goes; the gc_<i>.bin files of a pass and its outboards (gc_<i>.b3o files, or a host callback); the pool of MAC / copy workers behind a queue of
 // segments; the BLAKE3 absorbers.
 // Each pool owns its threads and joins them in its destructor.  Nothing here knows sessions, schedules, plans or knobs — plain values
 // in — and nothing but the HIP runtime API, hip_owned.hpp, host_crypto.hpp and the standard library is needed: this header compiles
@@ -74,6 +74,7 @@ struct gsv_drain {
 // Where a drained stream goes (any combination): the per-instance CBC-MAC (AESAccumulatingHash), gc_<index>.bin files, a host callback,
 // the per-instance BLAKE3 tree hash on the device (engine_blake3.ipp) — the one destination for which no ciphertext leaves the device.
 using DrainSinkFn = int (*)(void* user, size_t instance, uint64_t first_record, const uint8_t* records, uint64_t n_records);  // (gsv_ct_sink_fn of include/gsv_engine.h)
+using OutboardSinkFn = int (*)(void* user, size_t instance, uint64_t byte_offset, const uint8_t* bytes, uint64_t n_bytes);  // (gsv_outboard_sink_fn)
 struct DrainSink {
   uint8_t* hashes = nullptr;           // n_inst x 16: the MAC states after this call
   const char* dir = nullptr;           // gc_<index>.bin, index = indexes ? indexes[i] : first_index + i
@@ -82,6 +83,10 @@ struct DrainSink {
   void* user = nullptr;
   uint8_t* b3 = nullptr;               // n_inst x 32: the BLAKE3 digests, written by the call that ends the pass
   const char* outboard_dir = nullptr;  // gc_<index>.b3o: the values the BLAKE3 absorbers receive, kept (needs b3)
+  OutboardSinkFn ob_fn = nullptr;      // ... or handed to the host as they are produced (needs b3)
+  void* ob_user = nullptr;
+  uint8_t* last_chunks = nullptr;      // n_inst x 1024: the streams' last chunks, zero-padded, written with b3 (needs b3)
+  bool outboard() const { return outboard_dir || ob_fn; }
   bool host() const { return hashes || dir || fn; }  // the stream is copied to the host
   bool any() const { return host() || b3; }
 };
@@ -115,15 +120,18 @@ class GcFiles {
   bool keep_ = false;
 };
 
-// The gc_<first_index + i>.b3o files of one call (outboard.hpp): a header, then the 32-byte values in the order the host absorbs them.
-// A new pass writes the header, a later slice appends; closed when the object goes away and REMOVED unless keep() was called, like the
-// gc files beside them.  Instances may be written from different threads, one instance from one thread at a time.
-class OutboardFiles {
+// The outboards of one call (outboard.hpp): a header, then the 32-byte values in the order the host absorbs them.  One writer, two
+// back ends.  FILES: gc_<first_index + i>.b3o — a new pass writes the header, a later slice appends; closed when the object goes away
+// and REMOVED unless keep() was called, like the gc files beside them.  CALLBACK (gsv_outboard_sink_fn of include/gsv_engine.h): the
+// same bytes handed to the host as they are produced, per instance at increasing byte offsets — the header at offset 0 by the slice
+// that starts a pass, a later slice goes on behind the values the earlier ones delivered; once a call has returned non-zero no
+// further call is started.  Instances may be written from different threads, one instance from one thread at a time.
+class OutboardWriter {
  public:
-  OutboardFiles() = default;
-  OutboardFiles(const OutboardFiles&) = delete;
-  OutboardFiles& operator=(const OutboardFiles&) = delete;
-  ~OutboardFiles() {
+  OutboardWriter() = default;
+  OutboardWriter(const OutboardWriter&) = delete;
+  OutboardWriter& operator=(const OutboardWriter&) = delete;
+  ~OutboardWriter() {
     for (FILE* f : files_) std::fclose(f);
     if (!keep_) for (const std::string& q : paths_) std::remove(q.c_str());
   }
@@ -132,6 +140,7 @@ class OutboardFiles {
   bool open(const char* dir, uint64_t first_index, size_t n_inst, bool new_pass, uint32_t k, uint64_t n_records, std::string* failed) {
     uint8_t header[Outboard::HEADER_BYTES];
     Outboard::put_header(header, k, n_records);
+    n_ = n_inst;
     for (size_t i = 0; i < n_inst; ++i) {
       const std::string q = path(dir, first_index + i);
       FILE* f = std::fopen(q.c_str(), new_pass ? "wb" : "ab");
@@ -141,24 +150,53 @@ class OutboardFiles {
     }
     return true;
   }
-  size_t size() const { return files_.size(); }
-  // `count` values per instance ([instance][value], dense, for all instances) go to the files of instances i0, i0 + step, ...
+  // The callback back end.  new_pass: every instance receives the header at offset 0, here, on the calling thread; else the slice goes
+  // on behind the `values_before` values per instance that the pass's earlier slices delivered.  False: the callback refused a header.
+  bool open(OutboardSinkFn fn, void* user, size_t n_inst, bool new_pass, uint32_t k, uint64_t n_records, uint64_t values_before) {
+    fn_ = fn; user_ = user; n_ = n_inst;
+    offset_.assign(n_inst, new_pass ? 0 : Outboard::HEADER_BYTES + 32 * values_before);
+    if (!new_pass) return true;
+    uint8_t header[Outboard::HEADER_BYTES];
+    Outboard::put_header(header, k, n_records);
+    for (size_t i = 0; i < n_inst; ++i) if (!deliver(i, header, sizeof header)) return false;
+    return true;
+  }
+  size_t size() const { return n_; }
+  bool to_callback() const { return fn_ != nullptr; }
+  bool callback_failed() const { return refused_.load(); }
+  // `count` values per instance ([instance][value], dense, for all instances) go to instances i0, i0 + step, ...
   bool append(const uint8_t* vals, uint32_t count, size_t i0, size_t step) {
     bool ok = true;
-    for (size_t i = i0; i < files_.size(); i += step) ok = std::fwrite(vals + i * size_t(count) * 32, 32, count, files_[i]) == count && ok;
+    for (size_t i = i0; i < n_; i += step) {
+      const uint8_t* const v = vals + i * size_t(count) * 32;
+      if (fn_) { if (count) ok = deliver(i, v, uint64_t(count) * 32) && ok; }
+      else ok = std::fwrite(v, 32, count, files_[i]) == count && ok;
+    }
     return ok;
   }
   bool flush() { bool ok = true; for (FILE* f : files_) ok = std::fflush(f) == 0 && ok; return ok; }
   void keep() { keep_ = true; }
  private:
+  bool deliver(size_t i, const uint8_t* bytes, uint64_t n) {
+    if (refused_.load()) return false;
+    if (fn_(user_, i, offset_[i], bytes, n) != 0) { refused_.store(true); return false; }
+    offset_[i] += n;
+    return true;
+  }
   std::vector<FILE*> files_;
   std::vector<std::string> paths_;
   bool keep_ = false;
+  OutboardSinkFn fn_ = nullptr;
+  void* user_ = nullptr;
+  std::vector<uint64_t> offset_;     // callback: the next byte of every instance's outboard
+  std::atomic<bool> refused_{false};
+  size_t n_ = 0;
 };
+using OutboardFiles = OutboardWriter;  // (the name from before the callback back end)
 
 // What went wrong on the host side of a drain.  The pools of one pass share one slot, the first error stays: a worker that sees one
 // set stops copying and hashing.
-enum class DrainError { None, Copy, FileWrite, Sink, B3Order };
+enum class DrainError { None, Copy, FileWrite, Sink, B3Order, OutboardSink };
 inline void drain_set_error(std::atomic<DrainError>& slot, DrainError e) { DrainError none = DrainError::None; slot.compare_exchange_strong(none, e); }
 
 inline double drain_secs(std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); }

@@ -122,20 +122,31 @@ static bool read_small_file(const std::string& path, uint64_t most, std::vector<
 }
 // The outboard at `path` for a stream of n_records records in groups of 2^k chunks -> *out, parsed and bounds-checked.  A header that
 // says otherwise, and a length that does not follow from it, are refused (*why names both sides).
+// ... `name` being the file's path, or what else the message should call an outboard that came in memory
+static bool check_outboard(const std::string& name, const uint8_t* p, uint64_t n_bytes, uint32_t k, uint64_t n_records, std::string* why) {
+  Outboard o;
+  if (!Outboard::parse_header(p, n_bytes, &o, why)) { *why = name + ": " + *why; return false; }
+  if (o.n_records != n_records) { *why = name + " is the outboard of a stream of " + std::to_string(o.n_records) + " records, the stream here holds " + std::to_string(n_records); return false; }
+  if (o.k != k) { *why = name + " was written for groups of 2^" + std::to_string(o.k) + " chunks, this pass reduces groups of 2^" + std::to_string(k) + " (GSV_B3_SUBTREE_LOG2)"; return false; }
+  if (!Outboard::parse(p, n_bytes, &o, why)) { *why = name + ": " + *why; return false; }
+  return true;
+}
 static bool load_outboard(const std::string& path, uint32_t k, uint64_t n_records, std::vector<uint8_t>* out, std::string* why) {
   if (!read_small_file(path, Outboard::file_bytes(n_records, k), out, why)) return false;
-  Outboard o;
-  if (!Outboard::parse_header(out->data(), out->size(), &o, why)) { *why = path + ": " + *why; return false; }
-  if (o.n_records != n_records) { *why = path + " is the outboard of a stream of " + std::to_string(o.n_records) + " records, the stream here holds " + std::to_string(n_records); return false; }
-  if (o.k != k) { *why = path + " was written for groups of 2^" + std::to_string(o.k) + " chunks, this pass reduces groups of 2^" + std::to_string(k) + " (GSV_B3_SUBTREE_LOG2)"; return false; }
-  if (!Outboard::parse(out->data(), out->size(), &o, why)) { *why = path + ": " + *why; return false; }
-  return true;
+  return check_outboard(path, out->data(), out->size(), k, n_records, why);
+}
+// a B3Check for n_inst streams of n_records records in groups of 2^k chunks, its outboards still to be filled in
+static void b3_check_shape(B3Check& c, size_t n_inst, uint32_t k, uint64_t n_records) {
+  const uint64_t dev_chunks = Outboard::chunks(n_records) - 1;
+  c.k = k; c.n_records = n_records; c.n_groups = dev_chunks >> k; c.n_pending = dev_chunks & ((1ull << k) - 1);
+  c.bytes.resize(n_inst);
 }
 
 // every record has been fed and every group value absorbed: the pending chunk values and the last chunks come to the host.
 // `pending` (optional) sees the pending chunk values ([instance][value], dense) before they are absorbed and before anything is
-// written to `digests`; a non-zero return ends the call with it.
-static int b3_finish(B3Stream& b, hipStream_t st, uint8_t* digests, const std::function<int(const uint8_t* vals, uint32_t pend)>& pending = nullptr) {
+// written to `digests`; a non-zero return ends the call with it.  `last_chunks` (optional, n_inst x 1024) receives the last chunks
+// themselves — the carries the host hashes — each padded with zeros.
+static int b3_finish(B3Stream& b, hipStream_t st, uint8_t* digests, const std::function<int(const uint8_t* vals, uint32_t pend)>& pending = nullptr, uint8_t* last_chunks = nullptr) {
   if (b.records_done != b.total) return fail(GSV_ERR_INVALID, "internal: BLAKE3 stream ended early");
   // the folding (up to 2^k - 1 parents, the last chunk and the stack per instance) runs on a few threads, not on the caller's
   const size_t T = std::min<size_t>(4, b.n_inst);
@@ -159,6 +170,11 @@ static int b3_finish(B3Stream& b, hipStream_t st, uint8_t* digests, const std::f
   }
   if (!on_pool([&](size_t i) { b.hashers[i].update(b.pinned.get() + i * 1024, uint64_t(b.carry_n) * 16); return b.hashers[i].finalize(digests + 32 * i); }))
     return fail(GSV_ERR_INVALID, "internal: BLAKE3 stream without a last chunk");
+  if (last_chunks) {
+    const size_t have = size_t(b.carry_n) * 16;
+    std::memset(last_chunks, 0, b.n_inst * 1024);
+    for (size_t i = 0; i < b.n_inst && have; ++i) std::memcpy(last_chunks + i * 1024, b.pinned.get() + i * 1024, have);
+  }
   return GSV_OK;
 }
 
@@ -207,6 +223,13 @@ int gsv_blake3_outboard_root(const uint8_t* outboard, uint64_t n_bytes, const ui
   if (!Outboard::parse(outboard, n_bytes, &o, &why) || !o.root(last_chunk, last_chunk_bytes, out, &why)) return fail(GSV_ERR_INVALID, why);
   return GSV_OK;
 }
+int gsv_blake3_outboard_size(uint64_t n_records, uint32_t k, uint64_t* outboard_bytes, uint64_t* last_chunk_bytes) {
+  if (k > Outboard::MAX_K) return fail(GSV_ERR_INVALID, "the group size must be 2^k chunks with k in [0, 20]");
+  if (n_records > Outboard::MAX_RECORDS) return fail(GSV_ERR_INVALID, "n_records " + std::to_string(n_records) + " is out of range");
+  if (outboard_bytes) *outboard_bytes = Outboard::file_bytes(n_records, k);
+  if (last_chunk_bytes) *last_chunk_bytes = Outboard::last_chunk_bytes(n_records);
+  return GSV_OK;
+}
 int gsv_blake3_file_outboard(const char* path, uint32_t k, const char* outboard_path, uint8_t* out) {
   if (!path || !out) return fail(GSV_ERR_INVALID, "null argument");
   std::vector<uint8_t> ob, last;
@@ -249,8 +272,7 @@ int gsv_engine_blake3_files(gsv_engine* e, const char* const* paths, uint64_t n_
   std::unique_ptr<B3Check> check;
   if (outboard_paths) {
     check.reset(new B3Check());
-    check->k = k; check->n_records = total; check->n_groups = (Outboard::chunks(total) - 1) >> k; check->n_pending = (Outboard::chunks(total) - 1) & ((1ull << k) - 1);
-    check->bytes.resize(n);
+    b3_check_shape(*check, n, k, total);
     std::string why;
     for (size_t i = 0; i < n; ++i) if (!load_outboard(outboard_paths[i], k, total, &check->bytes[i], &why)) return fail(GSV_ERR_INVALID, why);
   }

@@ -217,6 +217,7 @@ static int fail_drain(DrainError e) {
   switch (e) {
     case DrainError::FileWrite: return fail(GSV_ERR_INVALID, "short write to a gc or outboard file");
     case DrainError::Sink: return fail(GSV_ERR_INVALID, "the ciphertext sink reported an error");
+    case DrainError::OutboardSink: return fail(GSV_ERR_INVALID, "the outboard sink reported an error");
     case DrainError::B3Order: return fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
     default: return fail(GSV_ERR_DEVICE, "device copy failed while draining ciphertexts");
   }
@@ -344,7 +345,8 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   const bool want_host = sink.host();    // ... and copied out by the workers
   const bool want_b3 = sink.b3 != nullptr;
   const bool want_mac = sink.hashes != nullptr;
-  if (sink.outboard_dir && !want_b3) return fail(GSV_ERR_INVALID, "an outboard holds the values of the BLAKE3 commitment: blake3_digests must be given");
+  if (sink.outboard() && !want_b3) return fail(GSV_ERR_INVALID, "an outboard holds the values of the BLAKE3 commitment: blake3_digests must be given");
+  if (sink.last_chunks && !want_b3) return fail(GSV_ERR_INVALID, "the last chunks come with the BLAKE3 commitment: blake3_digests must be given");
   if (s->plan && new_pass) s->windows_launched = 0;
   const size_t GROUP = size_t(gsv_drain::group_for(n_inst, s->pass.drain_group));
   const size_t n_groups = (n_inst + GROUP - 1) / GROUP;
@@ -362,7 +364,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   // A pass that commits with BLAKE3 carries the same commitments in every slice: a slice without MAC workers leaves the MAC states
   // behind, one without the hash kernels the BLAKE3 state, and the commitment returned at the end would cover part of the stream
   {
-    const uint8_t commit = uint8_t((want_mac ? 1 : 0) | (want_b3 ? 2 : 0) | (sink.outboard_dir ? 4 : 0));  // (an outboard is part of what a BLAKE3 pass carries)
+    const uint8_t commit = uint8_t((want_mac ? 1 : 0) | (want_b3 ? 2 : 0) | (sink.outboard() ? 4 : 0));  // (an outboard, to files or to a callback, is part of what a BLAKE3 pass carries)
     if (new_pass || !s->plan) s->pass_commit = commit;
     else if (commit != s->pass_commit && ((commit | s->pass_commit) & 2)) return fail(GSV_ERR_INVALID, "every slice of a pass with a BLAKE3 commitment must ask for the same commitments as its first slice");
   }
@@ -382,8 +384,11 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   std::vector<CbcMacHost>& macs = want_host ? s->drain->macs : no_macs;
   GcFiles files;  // (removed again on every return but the last)
   if (std::string failed; sink.dir && !files.open(sink.dir, sink.first_index, n_inst, new_pass ? "wb" : "ab", &failed)) return fail(GSV_ERR_INVALID, "cannot create " + failed);
-  OutboardFiles outboards;  // (likewise; written by the absorbers' threads, and by this one when the pass ends)
+  OutboardWriter outboards;  // (likewise; written by the absorbers' threads, and by this one when the pass ends)
   if (std::string failed; sink.outboard_dir && !outboards.open(sink.outboard_dir, sink.first_index, n_inst, new_pass, s->b3->k, s->b3->total, &failed)) return fail(GSV_ERR_INVALID, "cannot create " + failed);
+  // (a later slice goes on behind the group values of the earlier ones: every chunk hashed so far but the pending ones is in a group)
+  if (sink.ob_fn && !sink.outboard_dir && !outboards.open(sink.ob_fn, sink.ob_user, n_inst, new_pass, s->b3->k, s->b3->total, (s->b3->chunks_done - s->b3->pend) >> s->b3->k))
+    return fail_drain(DrainError::OutboardSink);
   DrainShape shape;
   shape.device = s->e->device; shape.n_inst = n_inst; shape.group = GROUP; shape.n_workers = want_host ? T : 0;
   shape.chunk = want_host ? s->drain->chunk : 0; shape.seg_records = seg_records; shape.blocking_wait = T > 8;
@@ -397,9 +402,9 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   std::atomic<DrainError> err{DrainError::None};
   DrainWorkers workers(s->drain.get(), shape, sink, macs, files, err);
   B3Stream* const b3s = want_b3 ? s->b3.get() : nullptr;
-  OutboardFiles* const obf = sink.outboard_dir ? &outboards : nullptr;
+  OutboardWriter* const obf = sink.outboard() ? &outboards : nullptr;
   B3Absorbers absorbers(want_b3 ? std::min<size_t>(4, n_inst) : 0, [b3s, obf, &err](const uint8_t* vals, uint32_t groups, size_t t, size_t n) {
-    if (obf && !obf->append(vals, groups, t, n)) drain_set_error(err, DrainError::FileWrite);  // thread t keeps the values of ITS instances as it receives them
+    if (obf && !obf->append(vals, groups, t, n)) drain_set_error(err, obf->to_callback() ? DrainError::OutboardSink : DrainError::FileWrite);  // thread t keeps the values of ITS instances as it receives them
     return b3_absorb(*b3s, vals, groups, b3s->k, t, n);
   }, err);
   DrainStats stats;
@@ -440,8 +445,8 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   // the call that ends the pass finishes the BLAKE3 streams: pending chunk values and the last chunks come to the host (<= 1 KiB + 32 B x 2^k per instance)
   if (rc == GSV_OK && want_b3 && (!s->plan || c1 == s->plan->calls.size()))
     rc = b3_finish(*s->b3, s->e->stream.get(), sink.b3, obf ? std::function<int(const uint8_t*, uint32_t)>([obf](const uint8_t* vals, uint32_t pend) {
-      return !pend || obf->append(vals, pend, 0, 1) ? GSV_OK : fail(GSV_ERR_INVALID, "short write to an outboard file");
-    }) : nullptr);
+      return !pend || obf->append(vals, pend, 0, 1) ? GSV_OK : obf->to_callback() ? fail_drain(DrainError::OutboardSink) : fail(GSV_ERR_INVALID, "short write to an outboard file");
+    }) : nullptr, sink.last_chunks);
   if (rc == GSV_OK && obf && !obf->flush()) rc = fail(GSV_ERR_INVALID, "short write to an outboard file");
   if (rc != GSV_OK) return rc;
   if (want_mac) for (size_t i = 0; i < n_inst; ++i) macs[i].digest(sink.hashes + 16 * i);
@@ -484,9 +489,9 @@ int gsv_session_fallback_count(const gsv_session* s, uint64_t* n) {
   return GSV_OK;
 }
 // A whole pass whose results the engine alone has seen (discarded, MAC'ed, written to gc files) is repeated on the safe schedule by
-// itself; a pass that fed a host callback or an evaluator session, or a slice of a pass, fails as before — the host has consumed a
-// prefix of a stream that is invalid, and a slice's call range follows the old schedule's windows — but leaves the session on the
-// safe schedule, so that the host's own repeat of the pass (from gsv_session_set_garble_inputs on) succeeds.
+// itself; a pass that fed a host callback (ciphertexts or outboard values) or an evaluator session, or a slice of a pass, fails as
+// before — the host has consumed a prefix of a stream that is invalid, and a slice's call range follows the old schedule's windows —
+// but leaves the session on the safe schedule, so that the host's own repeat of the pass (from gsv_session_set_garble_inputs on) succeeds.
 static int garble_streaming_range(gsv_session* s, uint64_t gate_id_base, size_t c0, size_t c1, const DrainSink& sink, int n_threads, gsv_session* ev = nullptr) {
   int rc = garble_streaming_pass(s, gate_id_base, c0, c1, sink, n_threads, ev);
   if (rc != GSV_ERR_DEVICE || !s->plan || !(s->dep_fault || (ev && ev->dep_fault)) || s->safe_mode) return rc;
@@ -495,7 +500,7 @@ static int garble_streaming_range(gsv_session* s, uint64_t gate_id_base, size_t 
   int frc = fall_back_to_safe_schedule(s);
   if (frc) return fail(GSV_ERR_DEVICE, first_error + "; the fall-back to the safe schedule failed too: " + g_err);
   if (ev) { frc = fall_back_to_safe_schedule(ev); if (frc) return fail(GSV_ERR_DEVICE, first_error + "; the evaluator's fall-back to the safe schedule failed: " + g_err); }
-  if (!whole || sink.fn || ev)
+  if (!whole || sink.fn || sink.ob_fn || ev)
     return fail(GSV_ERR_DEVICE, first_error + "; the session now runs the safe schedule (one call per launch): repeat the pass from gsv_session_set_garble_inputs");
   if (s->pass.drain_debug || s->pass.plan_debug) std::fprintf(stderr, "plan session: %s -- repeating the pass on the safe schedule (one call per launch)\n", first_error.c_str());
   return garble_streaming_pass(s, gate_id_base, 0, s->plan->calls.size(), sink, n_threads, nullptr);
@@ -553,6 +558,24 @@ int gsv_session_garble_streaming_sink(gsv_session* s, uint64_t gate_id_base, uin
   DrainSink k;
   k.hashes = hashes; k.fn = sink; k.user = user;
   if (!s->plan) return garble_streaming_range(s, gate_id_base, 0, 1, k, n_threads);
+  if (first_call == 0 && n_calls == 0) n_calls = s->plan->calls.size();
+  return garble_slice(s, gate_id_base, first_call, n_calls, k, n_threads);
+}
+// ... with either commitment or both, the outboards handed to a second callback and the last chunks returned (include/gsv_engine.h,
+// "Commitments on the callback paths"): gsv_session_garble_streaming_commit_outboard with the handler in place of `dir`, the callback in place of `outboard_dir`.
+int gsv_session_garble_streaming_sink_commit(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, gsv_ct_sink_fn sink, void* user, int n_threads,
+                                             uint8_t* cbcmac_hashes, uint8_t* blake3_digests, gsv_outboard_sink_fn outboard_sink, void* outboard_user, uint8_t* last_chunks) {
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
+  if (!s) return fail(GSV_ERR_INVALID, "null argument");
+  if (outboard_sink && !blake3_digests) return fail(GSV_ERR_INVALID, "an outboard holds the values of the BLAKE3 commitment: blake3_digests must be given");
+  if (last_chunks && !blake3_digests) return fail(GSV_ERR_INVALID, "the last chunks come with the BLAKE3 commitment: blake3_digests must be given");
+  DrainSink k;
+  k.hashes = cbcmac_hashes; k.fn = sink; k.user = user;
+  k.b3 = blake3_digests; k.ob_fn = outboard_sink; k.ob_user = outboard_user; k.last_chunks = last_chunks;
+  if (!s->plan) {
+    if (first_call || n_calls) return fail(GSV_ERR_INVALID, "program sessions are garbled in one pass (first_call = n_calls = 0)");
+    return garble_streaming_range(s, gate_id_base, 0, 1, k, n_threads);
+  }
   if (first_call == 0 && n_calls == 0) n_calls = s->plan->calls.size();
   return garble_slice(s, gate_id_base, first_call, n_calls, k, n_threads);
 }

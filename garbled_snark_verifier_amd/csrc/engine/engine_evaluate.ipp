@@ -214,6 +214,20 @@ static int evaluate_streaming_impl(gsv_session* s, uint64_t gate_id_base, const 
   if (s->pass.drain_debug || s->pass.plan_debug) std::fprintf(stderr, "plan session: %s -- repeating the evaluation on the safe schedule (one call per launch)\n", first_error.c_str());
   return evaluate_streaming_pass(s, gate_id_base, read, hashes, digests, vf);
 }
+// In front of a verified pass: the (well-formed) outboard of instance i, folded with the last chunk, must be the commitment.  A
+// difference has no place in the stream: the mismatch names the instance alone.
+static int check_outboard_root(gsv_session* s, const B3Check& c, size_t i, const uint8_t* last, uint64_t last_bytes, const uint8_t* expected, uint64_t expected_len) {
+  Outboard o;
+  uint8_t root[32];
+  std::string why;
+  if (!Outboard::parse(c.bytes[i].data(), c.bytes[i].size(), &o, &why) || !o.root(last, last_bytes, root, &why)) return fail(GSV_ERR_INVALID, why);
+  if (std::memcmp(root, expected + expected_len * i, size_t(expected_len)) != 0) {
+    s->mismatch = true; s->mismatch_instance = i; s->mismatch_group = s->mismatch_record = ~0ull;
+    s->ran = false;
+    return fail(GSV_ERR_MISMATCH, "outboard or last chunk of instance " + std::to_string(i) + " does not match the commitment");
+  }
+  return GSV_OK;
+}
 // FileSource: instance i reads <dir>/gc_<indexes[i]>.bin (indexes == NULL: first_index + i)
 static int evaluate_from_files(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint64_t first_index, uint8_t* hashes, uint8_t* digests,
                                const char* outboard_dir = nullptr, const uint8_t* expected = nullptr, uint64_t expected_len = 0) {
@@ -237,24 +251,16 @@ static int evaluate_from_files(gsv_session* s, uint64_t gate_id_base, const char
     const uint64_t total = s->plan ? s->plan->n_ct : s->replays * s->prog().n_ct, dev_chunks = Outboard::chunks(total) - 1;
     vf.reset(new EvalVerify{B3Check(), expected, expected_len});
     B3Check& c = vf->check;
-    c.k = k; c.n_records = total; c.n_groups = dev_chunks >> k; c.n_pending = dev_chunks & ((1ull << k) - 1);
-    c.bytes.resize(s->n_inst);
+    b3_check_shape(c, s->n_inst, k, total);
     s->mismatch = false;
     std::vector<uint8_t> last(size_t(Outboard::last_chunk_bytes(total)));
     for (size_t i = 0; i < s->n_inst; ++i) {
       std::string why;
-      if (!load_outboard(OutboardFiles::path(outboard_dir, indexes ? indexes[i] : first_index + i), k, total, &c.bytes[i], &why)) return fail(GSV_ERR_INVALID, why);
+      if (!load_outboard(OutboardWriter::path(outboard_dir, indexes ? indexes[i] : first_index + i), k, total, &c.bytes[i], &why)) return fail(GSV_ERR_INVALID, why);
       if (!last.empty() && (fseeko(files[i], off_t(dev_chunks * 1024), SEEK_SET) != 0 || std::fread(last.data(), 1, last.size(), files[i]) != last.size()))
         return fail(GSV_ERR_EXHAUSTED, "Ciphertext source exhausted: instance " + std::to_string(i) + " holds fewer than " + std::to_string(total) + " ciphertexts");
       pos[i] = total;  // (where the file's position stands now: the pass seeks back)
-      Outboard o;
-      uint8_t root[32];
-      if (!Outboard::parse(c.bytes[i].data(), c.bytes[i].size(), &o, &why) || !o.root(last.data(), last.size(), root, &why)) return fail(GSV_ERR_INVALID, why);
-      if (std::memcmp(root, expected + expected_len * i, size_t(expected_len)) != 0) {
-        s->mismatch = true; s->mismatch_instance = i; s->mismatch_group = s->mismatch_record = ~0ull;
-        s->ran = false;
-        return fail(GSV_ERR_MISMATCH, "outboard or last chunk of instance " + std::to_string(i) + " does not match the commitment");
-      }
+      if (int rrc = check_outboard_root(s, c, i, last.data(), last.size(), expected, expected_len)) return rrc;
     }
   }
   return evaluate_streaming_impl(s, gate_id_base, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t n) -> int {
@@ -284,14 +290,15 @@ int gsv_session_evaluate_streaming_commit(gsv_session* s, uint64_t gate_id_base,
   return evaluate_from_files(s, gate_id_base, dir, indexes, first_index, cbcmac_hashes, blake3_digests);
 }
 // ... and verified against outboards and commitments the caller trusts (include/gsv_engine.h, "BLAKE3 outboards")
+static const char* const VERIFIED_OVER_A_RING =
+    "verified streaming is not available for plan sessions over a ciphertext ring (retain_stream = GSV_STREAM_RING): their pass is one launch that waits on the device for the host's "
+    "stream position, and a host that stops feeding it would leave that launch to the watchdog; use launch windows (retain_stream = 0)";
 int gsv_session_evaluate_streaming_verified(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint64_t first_index, const char* outboard_dir, const uint8_t* expected,
                                             uint64_t expected_len, uint8_t* cbcmac_hashes, uint8_t* blake3_digests) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   if (!s || !dir || !outboard_dir || !expected || !blake3_digests) return fail(GSV_ERR_INVALID, "null argument");
   if (expected_len != 16 && expected_len != 32) return fail(GSV_ERR_INVALID, "expected_len must be 16 (a truncated digest) or 32");
-  if (s->plan && s->ct_ring)
-    return fail(GSV_ERR_INVALID, "verified streaming is not available for plan sessions over a ciphertext ring (retain_stream = GSV_STREAM_RING): their pass is one launch that waits on the device for the host's "
-                                 "stream position, and a host that stops feeding it would leave that launch to the watchdog; use launch windows (retain_stream = 0)");
+  if (s->plan && s->ct_ring) return fail(GSV_ERR_INVALID, VERIFIED_OVER_A_RING);
   return evaluate_from_files(s, gate_id_base, dir, indexes, first_index, cbcmac_hashes, blake3_digests, outboard_dir, expected, expected_len);
 }
 int gsv_session_mismatch_info(const gsv_session* s, uint64_t* instance, uint64_t* group, uint64_t* first_record) {
@@ -306,4 +313,31 @@ int gsv_session_evaluate_streaming_source_commit(gsv_session* s, uint64_t gate_i
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   if (!s || !source) return fail(GSV_ERR_INVALID, "null argument");
   return evaluate_streaming_impl(s, gate_id_base, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t n) -> int { return source(user, i, first, dst, n); }, cbcmac_hashes, blake3_digests);
+}
+// The generic source, verified (include/gsv_engine.h, "Commitments on the callback paths"): the outboards come in memory.  With the last
+// chunks (up-front mode) they are authenticated against `expected` before the source is called at all; without (deferred mode) they are
+// checked for form only, and the computed digests meet `expected` at the end of the pass.
+int gsv_session_evaluate_streaming_source_verified(gsv_session* s, uint64_t gate_id_base, gsv_ct_source_fn source, void* user, const uint8_t* const* outboards, const uint64_t* outboard_bytes,
+                                                   const uint8_t* last_chunks, const uint8_t* expected, uint64_t expected_len, uint8_t* cbcmac_hashes, uint8_t* blake3_digests) {
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
+  if (!s || !source || !outboards || !outboard_bytes || !expected || !blake3_digests) return fail(GSV_ERR_INVALID, "null argument");
+  if (expected_len != 16 && expected_len != 32) return fail(GSV_ERR_INVALID, "expected_len must be 16 (a truncated digest) or 32");
+  if (s->plan && s->ct_ring) return fail(GSV_ERR_INVALID, VERIFIED_OVER_A_RING);
+  const uint32_t k = s->pass.b3_subtree_log2;
+  if (k > 20) return fail(GSV_ERR_INVALID, "GSV_B3_SUBTREE_LOG2 must be an integer in [0, 20]");
+  const uint64_t total = s->plan ? s->plan->n_ct : s->replays * s->prog().n_ct, last_bytes = Outboard::last_chunk_bytes(total);
+  EvalVerify vf{B3Check(), expected, expected_len};
+  B3Check& c = vf.check;
+  b3_check_shape(c, s->n_inst, k, total);
+  s->mismatch = false;
+  // every outboard is parsed and bounds-checked before any of them is folded, and all of that before the source is called
+  for (size_t i = 0; i < s->n_inst; ++i) {
+    std::string why;
+    if (!outboards[i]) return fail(GSV_ERR_INVALID, "null outboard");
+    if (!check_outboard("outboards[" + std::to_string(i) + "]", outboards[i], outboard_bytes[i], k, total, &why)) return fail(GSV_ERR_INVALID, why);
+    c.bytes[i].assign(outboards[i], outboards[i] + outboard_bytes[i]);
+  }
+  for (size_t i = 0; last_chunks && i < s->n_inst; ++i)
+    if (int rrc = check_outboard_root(s, c, i, last_chunks + 1024 * i, last_bytes, expected, expected_len)) return rrc;
+  return evaluate_streaming_impl(s, gate_id_base, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t n) -> int { return source(user, i, first, dst, n); }, cbcmac_hashes, blake3_digests, /*rereadable=*/false, &vf);
 }

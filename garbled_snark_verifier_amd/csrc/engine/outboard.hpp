@@ -1,8 +1,8 @@
 // The BLAKE3 outboard of a ciphertext stream (include/gsv_engine.h, "BLAKE3 outboards"): the values the host absorbs when a stream is
 // hashed on the device — one 32-byte value per aligned group of 2^k chunks, then the chunk values behind the last complete group —
-// kept in a file beside gc_<i>.bin instead of thrown away.  One level of the tree, a format of this project's own: NOT Bao.  This
+// kept in a file beside gc_<i>.bin, or handed to a host callback, instead of thrown away.  One level of the tree, a format of this project's own: NOT Bao.  This
 // header parses and folds an outboard and computes one on the host for a file that already exists; it needs host_crypto.hpp and the
-// standard library only (the drain-side writer is OutboardFiles, drain_pipeline.hpp).
+// standard library only (the drain-side writer is OutboardWriter, drain_pipeline.hpp).
 #pragma once
 #include <sys/types.h>
 

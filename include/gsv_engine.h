@@ -567,7 +567,8 @@ int gsv_engine_blake3_files(gsv_engine* e, const char* const* paths, uint64_t n_
  * Plan sessions over a ciphertext ring (retain_stream = GSV_STREAM_RING) are refused with GSV_ERR_INVALID: their whole pass is one
  * launch that waits on the device for the host's stream position, and a host that stopped feeding it would leave that launch to the
  * watchdog.  The pass the safe-schedule fallback repeats restarts the verification from group 0.  The generic source
- * (gsv_session_evaluate_streaming_source*) has no verified form: its last chunk is not available up front. */
+ * has a verified form of its own, gsv_session_evaluate_streaming_source_verified ("Commitments on the callback paths" below): the
+ * outboards come in memory, and the last chunks either come with them or are done without until the end of the pass. */
 int gsv_session_evaluate_streaming_verified(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes /* NULL: first_index + i */, uint64_t first_index,
                                             const char* outboard_dir, const uint8_t* expected, uint64_t expected_len /* 16 or 32 */,
                                             uint8_t* cbcmac_hashes /* or NULL */, uint8_t* blake3_digests);
@@ -579,6 +580,74 @@ int gsv_session_mismatch_info(const gsv_session* s, uint64_t* instance, uint64_t
 /* Plan sessions: windows of the schedule launched by the session's last pass (a verified pass that ended early launched fewer than
  * gsv_plan_schedule_info.n_windows). */
 int gsv_session_windows_launched(const gsv_session* s, uint64_t* n);
+
+/* ---- Commitments on the callback paths -------------------------------------------------------------------------------------------
+ * The commitments, outboards and verified evaluation above for hosts that plug in through gsv_ct_sink_fn / gsv_ct_source_fn instead
+ * of gc_<i>.bin directories: nothing here needs a file.
+ *
+ * gsv_blake3_outboard_size: the byte length of the outboard (24 + 32 x values, as in the format above) and of the last chunk (0 for
+ * the empty stream, else 16 .. 1024) of a stream of n_records records at group size 2^k.  k above 20 is GSV_ERR_INVALID.  Either
+ * output may be NULL. */
+int gsv_blake3_outboard_size(uint64_t n_records, uint32_t k, uint64_t* outboard_bytes, uint64_t* last_chunk_bytes);
+/* The outboard of one instance, handed over as it is produced: the 24-byte header at offset 0 by the slice that starts at call 0, then
+ * the values at increasing offsets — the group values as the host's absorbers receive them, the pending chunk values when the pass
+ * ends.  Per instance the calls never overlap and come in offset order, so appending is enough; different instances may be served from
+ * different threads (the header from the thread that made the call).  `bytes` is only valid during the call.  A non-zero return aborts
+ * the pass like a failing ciphertext sink (GSV_ERR_INVALID): no call is started once it has returned (calls for other instances that
+ * other threads were in at that moment finish), and nothing is written to the caller's arrays. */
+typedef int (*gsv_outboard_sink_fn)(void* user, size_t instance, uint64_t byte_offset, const uint8_t* bytes, uint64_t n_bytes);
+/* gsv_session_garble_streaming_commit_outboard with the handler in place of `dir` and the outboard callback in place of
+ * `outboard_dir`; slices chain as they do there (first_call = n_calls = 0: the whole pass, the only form program sessions accept).
+ * n = the drained instances (gsv_session_set_drain_instances).
+ *   sink            or NULL: nothing is handed over.  With sink == NULL and blake3_digests alone nothing of the stream is copied to the
+ *                   host and no MAC worker starts.
+ *   cbcmac_hashes   n x 16 or NULL: the MAC states after this call.
+ *   blake3_digests  n x 32 or NULL: written by the call that ends the pass, left untouched otherwise.
+ *   outboard_sink   or NULL; needs blake3_digests.  The bytes it receives for an instance, concatenated, are byte for byte the
+ *                   gc_<i>.b3o the directory path writes; k is the pass's GSV_B3_SUBTREE_LOG2, the total is what
+ *                   gsv_blake3_outboard_size says.
+ *   last_chunks     n x 1024 or NULL; needs blake3_digests.  Written with blake3_digests: entry i holds the stream's last chunk in its
+ *                   first last_chunk_bytes bytes, the rest is zero.  (The host hashes that chunk anyway: it is the carry the device
+ *                   returns at the end of the pass.)
+ * Every slice must ask for the same commitments as the first, an outboard sink being one of them (GSV_ERR_INVALID otherwise).
+ * Safe-schedule fallback: a pass with an outboard callback follows the rule of a pass with a ciphertext sink.  The engine does not
+ * repeat it silently — the host has consumed a prefix of values that no longer belong to anything — the call fails with the remedy in
+ * its message, the session is left on the safe schedule, and the host's own repeat (from gsv_session_set_garble_inputs on) starts
+ * every outboard again at offset 0.
+ * gsv_session_garble_streaming_sink above is unchanged: it is this call with the CBC-MAC alone and a sink that must not be NULL. */
+int gsv_session_garble_streaming_sink_commit(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, gsv_ct_sink_fn sink /* or NULL */, void* user, int n_threads,
+                                             uint8_t* cbcmac_hashes /* n x 16 or NULL */, uint8_t* blake3_digests /* n x 32 or NULL */,
+                                             gsv_outboard_sink_fn outboard_sink /* or NULL; needs blake3_digests */, void* outboard_user,
+                                             uint8_t* last_chunks /* n x 1024 or NULL; needs blake3_digests */);
+/* Verified streaming evaluation from a generic source: gsv_session_evaluate_streaming_verified with memory in place of files.
+ * outboards[i] / outboard_bytes[i]: the outboard of instance i; expected = n_instances x expected_len bytes, expected_len 32 or 16;
+ * blake3_digests is required.  Before the source is called at all, every outboard is parsed and bounds-checked: its n_records must be
+ * the session's stream length and its k this pass's GSV_B3_SUBTREE_LOG2, else GSV_ERR_INVALID (the message names both values).
+ *
+ * UP-FRONT MODE, last_chunks != NULL (n_instances x 1024, entry i holding the last chunk in its first last_chunk_bytes bytes, as
+ * gsv_session_garble_streaming_sink_commit returns them): still before the source is called, the root of every outboard folded with
+ * its last chunk must equal the first expected_len bytes of expected[i], else GSV_ERR_MISMATCH, "outboard or last chunk of instance i
+ * does not match the commitment", and no place.  During the pass THE GUARANTEE, the points of comparison and the last look at the
+ * computed digests are those of the file path; in particular a source whose last chunk differs from the one handed in up front is
+ * caught by that last look.
+ *
+ * DEFERRED MODE, last_chunks == NULL: for a receiver whose peer sends only the outboard ahead of the stream.  The outboards are
+ * checked for form, k and n_records up front; group values and pending chunk values are compared as they arrive, exactly as above;
+ * the commitment is checked once, at the end: the computed digests against `expected`, and a difference is GSV_ERR_MISMATCH, reported
+ * as the file path reports a digest that differs at the end of a pass.  WHAT THIS WEAKENS: until the end of the pass the outboard
+ * itself is unauthenticated.  A forged outboard with a stream forged to match it is evaluated IN FULL and rejected only at the end;
+ * a mismatch in the middle of the pass says that stream and outboard disagree, not which of them is wrong.  No output is ever
+ * returned for such a stream: gsv_session_read_outputs fails after every GSV_ERR_MISMATCH, early or late.
+ *
+ * BOTH MODES.  On any mismatch nothing further is pulled from the source or launched, gsv_session_mismatch_info names the place,
+ * gsv_session_read_outputs fails as after a pass that never ran, and both digest arrays stay untouched.  A source that runs dry is
+ * GSV_ERR_EXHAUSTED.  Plan sessions over a ciphertext ring are refused with GSV_ERR_INVALID, for the reason given above.  A source
+ * cannot be read again, so after a safe-schedule fallback the call fails with the remedy and the host's repeat verifies from group 0. */
+int gsv_session_evaluate_streaming_source_verified(gsv_session* s, uint64_t gate_id_base, gsv_ct_source_fn source, void* user,
+                                                   const uint8_t* const* outboards, const uint64_t* outboard_bytes,
+                                                   const uint8_t* last_chunks /* n x 1024, or NULL: deferred mode */,
+                                                   const uint8_t* expected, uint64_t expected_len /* 16 or 32 */,
+                                                   uint8_t* cbcmac_hashes /* or NULL */, uint8_t* blake3_digests);
 
 #ifdef __cplusplus
 }
