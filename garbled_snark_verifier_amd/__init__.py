@@ -276,8 +276,28 @@ def _chk(rc):
         raise GsvError("gsv status %d: %s" % (rc, lib().gsv_last_error().decode(errors="replace")))
 
 
+def _chk_mismatch(rc, place):
+    """_chk, but GSV_ERR_MISMATCH raises CiphertextMismatch at place() = (instance, group[, first_record])."""
+    if rc == 5:
+        raise CiphertextMismatch("gsv status 5: %s" % lib().gsv_last_error().decode(errors="replace"), *place())
+    _chk(rc)
+
+
 def _p(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint8)) if a is not None else None
+
+
+def _rows(a, n=None):
+    """The first n (default: all) rows of a 2-D uint8 array as a list of bytes; None stays None."""
+    return None if a is None else [bytes(r) for r in a[:n]]
+
+
+def _pack_expected(expected, n):
+    """The commitments a verified evaluation trusts, one per instance -> (one uint8 array, bytes per commitment)."""
+    exp = [bytes(e) for e in expected]
+    if len(exp) != n or len(set(len(e) for e in exp)) != 1 or len(exp[0]) not in (16, 32):
+        raise ValueError("expected: one commitment of 16 or of 32 bytes per instance")
+    return np.frombuffer(b"".join(exp), np.uint8), len(exp[0])
 
 
 def _u8(a, shape=None):
@@ -397,10 +417,8 @@ def blake3_files(engine, paths, outboards=None):
     out = np.zeros((max(1, n), 32), np.uint8)
     bad_file, bad_group = C.c_uint64(), C.c_uint64()
     rc = lib().gsv_engine_blake3_files(engine.h, arr, n, obs, _p(out), C.byref(bad_file), C.byref(bad_group))
-    if rc == 5:
-        raise CiphertextMismatch("gsv status 5: %s" % lib().gsv_last_error().decode(errors="replace"), int(bad_file.value), int(bad_group.value))
-    _chk(rc)
-    return [bytes(out[i]) for i in range(n)]
+    _chk_mismatch(rc, lambda: (int(bad_file.value), int(bad_group.value)))
+    return _rows(out, n)
 
 
 def blake3_streams(engine, array, segments, with_seconds=False):
@@ -412,7 +430,7 @@ def blake3_streams(engine, array, segments, with_seconds=False):
     seg = (C.c_uint64 * max(1, len(segments)))(*[int(x) for x in segments])
     out = np.zeros((a.shape[0], 32), np.uint8)
     _chk(lib().gsv_engine_blake3_streams(engine.h, _p(a) if a.size else None, a.shape[0], a.shape[1], seg, len(segments), _p(out)))
-    digests = [bytes(out[i]) for i in range(a.shape[0])]
+    digests = _rows(out)
     if not with_seconds:
         return digests
     s = C.c_double()
@@ -746,11 +764,13 @@ class PlanRecorder:
             pass
 
 
-def _check_commitment(commitment, discard):
+def _check_commitment(commitment, discard, outboard_dir=None):
     if commitment not in ("cbcmac", "blake3", "both"):
         raise ValueError("commitment must be 'cbcmac', 'blake3' or 'both'")
     if discard and commitment != "cbcmac":
         raise ValueError("discard=True drops the ciphertexts: it cannot be combined with commitment=%r" % commitment)
+    if outboard_dir is not None and commitment == "cbcmac":
+        raise ValueError("outboard_dir needs commitment='blake3' or 'both': an outboard holds the values of the BLAKE3 commitment")
 
 
 class Session:
@@ -797,12 +817,15 @@ class Session:
         n = getattr(self, "n_drain", self.n)
         macs = np.zeros((self.n, 16), np.uint8) if commitment == "both" else None
         dig = np.zeros((n, 32), np.uint8)
-        ends_pass = (first_call == 0 and n_calls == 0) or not isinstance(self.program, Plan) or first_call + n_calls == self.schedule_info()["n_calls"]  # (else the engine leaves `dig` alone)
         with _gc_paused():
             _chk(lib().gsv_session_garble_streaming_commit_outboard(self.h, gate_id_base, first_call, n_calls, directory.encode() if directory else None, first_index, threads, _p(macs), _p(dig),
                                                                     os.fsencode(outboard_dir) if outboard_dir is not None else None))
-        digests = [bytes(dig[i]) for i in range(n)] if ends_pass else None
-        return ([bytes(macs[i]) for i in range(self.n)], digests) if commitment == "both" else digests
+        digests = _rows(dig) if self._ends_pass(first_call, n_calls) else None  # (else the engine leaves `dig` alone)
+        return (_rows(macs), digests) if commitment == "both" else digests
+
+    def _ends_pass(self, first_call, n_calls):
+        """Does the slice [first_call, first_call + n_calls) of a streaming garble (0, 0: all of it) end its pass?"""
+        return (first_call == 0 and n_calls == 0) or not isinstance(self.program, Plan) or first_call + n_calls == self.schedule_info()["n_calls"]
 
     def garble_streaming(self, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False, commitment="cbcmac", outboard_dir=None):
         """Garble all replays while the host drains the stream segment by segment: returns the per-instance ciphertext
@@ -810,19 +833,15 @@ class Session:
         only, the ciphertexts are dropped.  commitment="blake3": 32-byte BLAKE3 digests of the streams instead, computed on the
         device (nothing of the stream is copied out unless `directory` is given); "both": (CBC-MACs, BLAKE3 digests).
         outboard_dir (with "blake3" / "both"): the BLAKE3 outboards gc_<first_index+i>.b3o are written there."""
-        _check_commitment(commitment, discard)
-        if outboard_dir is not None and commitment == "cbcmac":
-            raise ValueError("outboard_dir needs commitment='blake3' or 'both': an outboard holds the values of the BLAKE3 commitment")
+        _check_commitment(commitment, discard, outboard_dir)
         if commitment != "cbcmac":
             return self._garble_commit(commitment, gate_id_base, 0, 0, directory, first_index, threads, outboard_dir)
         if discard:
-            with _gc_paused():
-                _chk(lib().gsv_session_garble_streaming(self.h, gate_id_base, None, 0, 0, None))
-            return None
-        out = np.zeros((self.n, 16), np.uint8)
+            directory, first_index, threads = None, 0, 0
+        out = None if discard else np.zeros((self.n, 16), np.uint8)
         with _gc_paused():
             _chk(lib().gsv_session_garble_streaming(self.h, gate_id_base, directory.encode() if directory else None, first_index, threads, _p(out)))
-        return [bytes(out[i]) for i in range(self.n)]
+        return _rows(out)
 
     def garble_calls(self, first_call, n_calls, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False, commitment="cbcmac", outboard_dir=None):
         """Plan sessions: garble calls [first_call, first_call + n_calls) only (a slice of the plan).  Wires, gate ids and the
@@ -830,21 +849,17 @@ class Session:
         slice (the commitments once the last slice has run), or None with discard=True.  commitment="blake3" / "both" as for
         garble_streaming: the BLAKE3 state chains from slice to slice too, the digests are None until the slice that ends the pass.
         outboard_dir as for garble_streaming, in every slice of the pass: the first slice truncates the outboards, later ones append."""
-        _check_commitment(commitment, discard)
-        if outboard_dir is not None and commitment == "cbcmac":
-            raise ValueError("outboard_dir needs commitment='blake3' or 'both': an outboard holds the values of the BLAKE3 commitment")
+        _check_commitment(commitment, discard, outboard_dir)
         if commitment != "cbcmac":
             if first_call == 0 and n_calls == 0:
                 raise ValueError("an empty slice")  # (0, 0 means the whole pass to the C entry point)
             return self._garble_commit(commitment, gate_id_base, first_call, n_calls, directory, first_index, threads, outboard_dir)
         if discard:
-            with _gc_paused():
-                _chk(lib().gsv_session_garble_streaming_calls(self.h, gate_id_base, first_call, n_calls, None, 0, 0, None))
-            return None
-        out = np.zeros((self.n, 16), np.uint8)
+            directory, first_index, threads = None, 0, 0
+        out = None if discard else np.zeros((self.n, 16), np.uint8)
         with _gc_paused():
             _chk(lib().gsv_session_garble_streaming_calls(self.h, gate_id_base, first_call, n_calls, directory.encode() if directory else None, first_index, threads, _p(out)))
-        return [bytes(out[i]) for i in range(self.n)]
+        return _rows(out)
 
     def garble_to_sink(self, handler, gate_id_base=0, first_call=0, n_calls=0, threads=0, with_hashes=False, commitment=None, outboards=False):
         """Garble with every ciphertext handed to `handler(instance, first_record, records)` — the generic CiphertextHandler
@@ -884,10 +899,9 @@ class Session:
             if failure:
                 raise failure[0]
             _chk(rc)
-            return [bytes(out[i]) for i in range(self.n)] if with_hashes else None
+            return _rows(out)
         n = getattr(self, "n_drain", self.n)
-        plan = isinstance(self.program, Plan)
-        ends_pass = (first_call == 0 and n_calls == 0) or not plan or first_call + n_calls == self.schedule_info()["n_calls"]  # (else the engine leaves the digests alone)
+        ends_pass = self._ends_pass(first_call, n_calls)  # (else the engine leaves the digests alone)
         b3 = commitment != "cbcmac"
         macs = np.zeros((n, 16), np.uint8) if commitment != "blake3" else None
         dig = np.zeros((n, 32), np.uint8) if b3 else None
@@ -916,12 +930,12 @@ class Session:
             raise failure[0]
         _chk(rc)
         if b3 and ends_pass:
-            total = self.program.info["n_ciphertexts"] * (1 if plan else self.replays)
+            total = self.program.info["n_ciphertexts"] * (1 if isinstance(self.program, Plan) else self.replays)
             last_bytes = blake3_outboard_size(total, 0)[1]
-        return SinkCommit([bytes(macs[i]) for i in range(n)] if macs is not None else None,
-                          [bytes(dig[i]) for i in range(n)] if b3 and ends_pass else None,
+        return SinkCommit(_rows(macs),
+                          _rows(dig) if b3 and ends_pass else None,
                           [bytes(x) for x in acc] if outboards and ends_pass else None,
-                          [bytes(last[i, :last_bytes]) for i in range(n)] if b3 and ends_pass else None)
+                          _rows(last[:, :last_bytes]) if b3 and ends_pass else None)
 
     def garble_evaluate(self, evaluator, gate_id_base=0, threads=0, with_hashes=False):
         """Garble this (plan, retain_stream=False) session while `evaluator` — a session of the same plan and options with its inputs
@@ -929,7 +943,7 @@ class Session:
         out = np.zeros((self.n, 16), np.uint8) if with_hashes else None
         with _gc_paused():
             _chk(lib().gsv_session_garble_evaluate(self.h, evaluator.h, gate_id_base, threads, _p(out)))
-        return [bytes(out[i]) for i in range(self.n)] if with_hashes else None
+        return _rows(out)
 
     def _evaluate_commit(self, commitment, call):
         """The streaming evaluators' commitments: `call(macs, digests)` runs the C entry point with the arrays this commitment asks for
@@ -937,30 +951,33 @@ class Session:
         macs = np.zeros((self.n, 16), np.uint8) if commitment != "blake3" else None
         dig = np.zeros((self.n, 32), np.uint8) if commitment != "cbcmac" else None
         call(macs, dig)
-        m = [bytes(macs[i]) for i in range(self.n)] if macs is not None else None
-        d = [bytes(dig[i]) for i in range(self.n)] if dig is not None else None
+        m, d = _rows(macs), _rows(dig)
         return (m, d) if commitment == "both" else m if d is None else d
 
-    def _verified_call(self, gate_id_base, directory, idx_p, first_index, outboard_dir, expected, commitment):
-        """call(macs, dig) of gsv_session_evaluate_streaming_verified; GSV_ERR_MISMATCH raises CiphertextMismatch with the place."""
-        if commitment == "cbcmac":
-            raise ValueError("outboard_dir / expected need commitment='blake3' or 'both'")
-        if outboard_dir is None or expected is None:
-            raise ValueError("verified streaming takes outboard_dir and expected together")
-        exp = [bytes(e) for e in expected]
-        if len(exp) != self.n or len(set(len(e) for e in exp)) != 1 or len(exp[0]) not in (16, 32):
-            raise ValueError("expected: one commitment of 16 or of 32 bytes per instance")
-        exp_a = np.frombuffer(b"".join(exp), np.uint8)
+    def _evaluate_files(self, commitment, gate_id_base, directory, idx_p, first_index, outboard_dir, expected):
+        """evaluate_streaming / evaluate_streaming_indexed (idx_p: the index list, or None for first_index + i); with outboard_dir or
+        expected gsv_session_evaluate_streaming_verified, where GSV_ERR_MISMATCH raises CiphertextMismatch with the place."""
+        verified = outboard_dir is not None or expected is not None
+        if verified:
+            if commitment == "cbcmac":
+                raise ValueError("outboard_dir / expected need commitment='blake3' or 'both'")
+            if outboard_dir is None or expected is None:
+                raise ValueError("verified streaming takes outboard_dir and expected together")
+            exp_a, exp_len = _pack_expected(expected, self.n)
 
         def call(macs, dig):
             with _gc_paused():
-                rc = lib().gsv_session_evaluate_streaming_verified(self.h, gate_id_base, os.fsencode(directory), idx_p, first_index, os.fsencode(outboard_dir), _p(exp_a), len(exp[0]), _p(macs), _p(dig))
-            if rc == 5:
-                msg = "gsv status 5: %s" % lib().gsv_last_error().decode(errors="replace")
-                raise CiphertextMismatch(msg, *self.mismatch_info())
-            _chk(rc)
+                if verified:
+                    rc = lib().gsv_session_evaluate_streaming_verified(self.h, gate_id_base, os.fsencode(directory), idx_p, first_index, os.fsencode(outboard_dir), _p(exp_a), exp_len, _p(macs), _p(dig))
+                elif dig is not None:
+                    rc = lib().gsv_session_evaluate_streaming_commit(self.h, gate_id_base, directory.encode(), idx_p, first_index, _p(macs), _p(dig))
+                elif idx_p is not None:
+                    rc = lib().gsv_session_evaluate_streaming_indexed(self.h, gate_id_base, directory.encode(), idx_p, _p(macs))
+                else:
+                    rc = lib().gsv_session_evaluate_streaming(self.h, gate_id_base, directory.encode(), first_index, _p(macs))
+            _chk_mismatch(rc, self.mismatch_info)
 
-        return call
+        return self._evaluate_commit(commitment, call)
 
     def mismatch_info(self):
         """(instance, group, first_record) of the mismatch the last verified pass ended with; group and first_record are None when
@@ -977,17 +994,7 @@ class Session:
         idx = np.ascontiguousarray(indexes, np.uint64)
         assert idx.size == self.n
         idx_p = idx.ctypes.data_as(C.POINTER(C.c_uint64))
-        if outboard_dir is not None or expected is not None:
-            return self._evaluate_commit(commitment, self._verified_call(gate_id_base, directory, idx_p, 0, outboard_dir, expected, commitment))
-
-        def call(macs, dig):
-            with _gc_paused():
-                if dig is None:
-                    _chk(lib().gsv_session_evaluate_streaming_indexed(self.h, gate_id_base, directory.encode(), idx_p, _p(macs)))
-                else:
-                    _chk(lib().gsv_session_evaluate_streaming_commit(self.h, gate_id_base, directory.encode(), idx_p, 0, _p(macs), _p(dig)))
-
-        return self._evaluate_commit(commitment, call)
+        return self._evaluate_files(commitment, gate_id_base, directory, idx_p, 0, outboard_dir, expected)
 
     def evaluate_from_source(self, source, gate_id_base=0, commitment="cbcmac", outboards=None, expected=None, last_chunks=None):
         """Evaluate with the ciphertexts pulled from `source(instance, first_record, n) -> [n,16] uint8` (None / short = exhausted):
@@ -1007,12 +1014,9 @@ class Session:
             if outboards is None or expected is None:
                 raise ValueError("verified evaluation takes outboards and expected together")
             obs = [np.frombuffer(bytes(o), np.uint8) for o in outboards]
-            exp = [bytes(e) for e in expected]
             if len(obs) != self.n:
                 raise ValueError("outboards: one per instance")
-            if len(exp) != self.n or len(set(len(e) for e in exp)) != 1 or len(exp[0]) not in (16, 32):
-                raise ValueError("expected: one commitment of 16 or of 32 bytes per instance")
-            exp_a = np.frombuffer(b"".join(exp), np.uint8)
+            exp_a, exp_len = _pack_expected(expected, self.n)
             last_a = None
             if last_chunks is not None:
                 lc = [bytes(x) for x in last_chunks]
@@ -1045,16 +1049,14 @@ class Session:
         def call(macs, dig):
             with _gc_paused():
                 if verified:
-                    rc = lib().gsv_session_evaluate_streaming_source_verified(self.h, gate_id_base, cb, None, ob_p, ob_n, _p(last_a), _p(exp_a), len(exp[0]), _p(macs), _p(dig))
+                    rc = lib().gsv_session_evaluate_streaming_source_verified(self.h, gate_id_base, cb, None, ob_p, ob_n, _p(last_a), _p(exp_a), exp_len, _p(macs), _p(dig))
                 elif dig is None:
                     rc = lib().gsv_session_evaluate_streaming_source(self.h, gate_id_base, cb, None, _p(macs))
                 else:
                     rc = lib().gsv_session_evaluate_streaming_source_commit(self.h, gate_id_base, cb, None, _p(macs), _p(dig))
             if failure:
                 raise failure[0]
-            if rc == 5:
-                raise CiphertextMismatch("gsv status 5: %s" % lib().gsv_last_error().decode(errors="replace"), *self.mismatch_info())
-            _chk(rc)
+            _chk_mismatch(rc, self.mismatch_info)
 
         return self._evaluate_commit(commitment, call)
 
@@ -1101,17 +1103,7 @@ class Session:
         anything is uploaded, and the pass stops at the first group of 2^k chunks that differs from its outboard: CiphertextMismatch
         names (instance, group), and read_outputs then fails."""
         _check_commitment(commitment, False)
-        if outboard_dir is not None or expected is not None:
-            return self._evaluate_commit(commitment, self._verified_call(gate_id_base, directory, None, first_index, outboard_dir, expected, commitment))
-
-        def call(macs, dig):
-            with _gc_paused():
-                if dig is None:
-                    _chk(lib().gsv_session_evaluate_streaming(self.h, gate_id_base, directory.encode(), first_index, _p(macs)))
-                else:
-                    _chk(lib().gsv_session_evaluate_streaming_commit(self.h, gate_id_base, directory.encode(), None, first_index, _p(macs), _p(dig)))
-
-        return self._evaluate_commit(commitment, call)
+        return self._evaluate_files(commitment, gate_id_base, directory, None, first_index, outboard_dir, expected)
 
     def set_evaluate_inputs(self, const_active, input_active, input_bits):
         c = _u8(const_active, (self.n, 32))

@@ -1,8 +1,9 @@
 // Part of engine.cpp: BLAKE3 commitments — the host hasher behind gsv_blake3_*, and the device tree hash of n equally long streams
-// that arrive in segments of a gate-order buffer (blake3_device.hpp), shared by the streaming drain (engine_drain.ipp), the streaming
-// evaluators (engine_evaluate.ipp), gsv_session_ciphertext_blake3 (engine_readback.ipp: it feeds ranges of the resident program-order stream),
-// gsv_engine_blake3_streams and gsv_engine_blake3_files; and the outboards (outboard.hpp): the values the host absorbs, kept in a file
-// by the drain, checked against a commitment (gsv_blake3_outboard_root) and compared with what a receiver's streams hash to (B3Check).
+// that arrive in segments of a gate-order buffer (blake3_device.hpp: B3Stream, b3_begin / b3_segment / b3_absorb / b3_finish).  The
+// streaming drain (engine_drain.ipp) absorbs the values on threads of its own; everyone else — the streaming evaluators
+// (engine_evaluate.ipp), gsv_session_ciphertext_blake3 (engine_readback.ipp: it feeds ranges of the resident program-order stream),
+// gsv_engine_blake3_streams and gsv_engine_blake3_files — goes through one B3Receiver, which also compares what the streams hash to
+// with their outboards (outboard.hpp: the values the host absorbs, kept by the drain; B3Check) and with the commitments.
 //
 // Split (DESIGN.md §3 "Commitment stage"): a stream of L records has N = max(1, ceil(L / 64)) chunks.  The device hashes chunks
 // 0 .. N-2 and reduces aligned groups of G = 2^k of them to one value each; the host absorbs floor((N-1) / G) group values, then the
@@ -21,10 +22,11 @@ struct B3Stream {
   uint64_t chunks_done = 0, records_done = 0;
   std::vector<Blake3Host> hashers;
 };
+static int check_b3_k(uint32_t k) { return k > 20 ? fail(GSV_ERR_INVALID, "GSV_B3_SUBTREE_LOG2 must be an integer in [0, 20]") : GSV_OK; }
 // a new stream set: buffers are kept when the shape is the one they were allocated for
 static int b3_begin(std::unique_ptr<B3Stream>& p, size_t n_inst, uint64_t total, uint64_t seg_cap, uint32_t k) {
   if (n_inst == 0 || n_inst > 65535) return fail(GSV_ERR_INVALID, "BLAKE3 commitments take 1 .. 65535 streams at a time");
-  if (k > 20) return fail(GSV_ERR_INVALID, "GSV_B3_SUBTREE_LOG2 must be an integer in [0, 20]");
+  if (int rc = check_b3_k(k)) return rc;
   const uint64_t cv_stride = ((1ull << k) - 1) + (seg_cap + 64) / 64 + 1, red_cap = (cv_stride >> k) + 1;
   if (cv_stride >= (1ull << 32)) return fail(GSV_ERR_INVALID, "segment too long for the BLAKE3 value buffers");
   if (!p || p->n_inst != n_inst || p->k != k || p->cv_stride != cv_stride) {
@@ -76,71 +78,6 @@ static bool b3_absorb(B3Stream& b, const uint8_t* vals, uint32_t groups, unsigne
     for (uint32_t g = 0; g < groups; ++g) ok = b.hashers[i].absorb_subtree(vals + (i * groups + g) * 32, k) && ok;
   return ok;
 }
-// The outboards a set of streams is verified against (outboard.hpp), by whoever receives the values the host absorbs: a streaming
-// evaluation in verified mode (engine_evaluate.ipp) and gsv_engine_blake3_files.  Every value is compared, in the order it arrives,
-// with the outboard of its instance; the first difference — the lowest group, then the lowest instance — is kept.
-struct B3Check {
-  std::vector<std::vector<uint8_t>> bytes;  // per instance: a well-formed outboard for `k` and `n_records`
-  uint32_t k = 0;
-  uint64_t n_records = 0, n_groups = 0, n_pending = 0;
-  uint64_t next = 0;                        // group values compared so far, per instance
-  size_t bad_instance = 0;
-  uint64_t bad_group = 0, bad_record = 0;   // the group (the open tail behind the last complete group: n_groups) and the first record the value covers
-  const uint8_t* value(size_t i, uint64_t v) const { return bytes[i].data() + Outboard::HEADER_BYTES + 32 * v; }
-  // `groups` group values per instance, [instance][group] dense
-  bool groups_match(const uint8_t* vals, uint32_t groups) {
-    if (next + groups > n_groups) { bad_instance = 0; bad_group = n_groups; bad_record = (n_groups << k) * 64; return false; }
-    for (uint32_t g = 0; g < groups; ++g)
-      for (size_t i = 0; i < bytes.size(); ++i)
-        if (std::memcmp(vals + (i * groups + g) * 32, value(i, next + g), 32) != 0) { bad_instance = i; bad_group = next + g; bad_record = ((next + g) << k) * 64; return false; }
-    next += groups;
-    return true;
-  }
-  // the chunk values behind the last complete group, [instance][value] dense
-  bool pending_match(const uint8_t* vals, uint32_t pend) {
-    if (next != n_groups || pend != n_pending) { bad_instance = 0; bad_group = std::min(next, n_groups); bad_record = (bad_group << k) * 64; return false; }
-    for (uint32_t c = 0; c < pend; ++c)
-      for (size_t i = 0; i < bytes.size(); ++i)
-        if (std::memcmp(vals + (i * pend + c) * 32, value(i, n_groups + c), 32) != 0) { bad_instance = i; bad_group = n_groups; bad_record = ((n_groups << k) + c) * 64; return false; }
-    return true;
-  }
-  std::string where(const char* what) const {
-    return std::string(what) + " " + std::to_string(bad_instance) + " does not match its outboard in group " + std::to_string(bad_group) + " (from record " + std::to_string(bad_record) + ")";
-  }
-};
-// The whole of `path` (at most `most` bytes are accepted) -> *out.  False: *why.
-static bool read_small_file(const std::string& path, uint64_t most, std::vector<uint8_t>* out, std::string* why) {
-  FILE* f = std::fopen(path.c_str(), "rb");
-  if (!f) { *why = "cannot open " + path; return false; }
-  out->resize(size_t(most) + 1);
-  const size_t n = std::fread(out->data(), 1, out->size(), f);
-  const bool bad = std::ferror(f) != 0;
-  std::fclose(f);
-  if (bad) { *why = "read error on " + path; return false; }
-  out->resize(n);
-  return true;
-}
-// The outboard at `path` for a stream of n_records records in groups of 2^k chunks -> *out, parsed and bounds-checked.  A header that
-// says otherwise, and a length that does not follow from it, are refused (*why names both sides).
-// ... `name` being the file's path, or what else the message should call an outboard that came in memory
-static bool check_outboard(const std::string& name, const uint8_t* p, uint64_t n_bytes, uint32_t k, uint64_t n_records, std::string* why) {
-  Outboard o;
-  if (!Outboard::parse_header(p, n_bytes, &o, why)) { *why = name + ": " + *why; return false; }
-  if (o.n_records != n_records) { *why = name + " is the outboard of a stream of " + std::to_string(o.n_records) + " records, the stream here holds " + std::to_string(n_records); return false; }
-  if (o.k != k) { *why = name + " was written for groups of 2^" + std::to_string(o.k) + " chunks, this pass reduces groups of 2^" + std::to_string(k) + " (GSV_B3_SUBTREE_LOG2)"; return false; }
-  if (!Outboard::parse(p, n_bytes, &o, why)) { *why = name + ": " + *why; return false; }
-  return true;
-}
-static bool load_outboard(const std::string& path, uint32_t k, uint64_t n_records, std::vector<uint8_t>* out, std::string* why) {
-  if (!read_small_file(path, Outboard::file_bytes(n_records, k), out, why)) return false;
-  return check_outboard(path, out->data(), out->size(), k, n_records, why);
-}
-// a B3Check for n_inst streams of n_records records in groups of 2^k chunks, its outboards still to be filled in
-static void b3_check_shape(B3Check& c, size_t n_inst, uint32_t k, uint64_t n_records) {
-  const uint64_t dev_chunks = Outboard::chunks(n_records) - 1;
-  c.k = k; c.n_records = n_records; c.n_groups = dev_chunks >> k; c.n_pending = dev_chunks & ((1ull << k) - 1);
-  c.bytes.resize(n_inst);
-}
 
 // every record has been fed and every group value absorbed: the pending chunk values and the last chunks come to the host.
 // `pending` (optional) sees the pending chunk values ([instance][value], dense) before they are absorbed and before anything is
@@ -177,6 +114,61 @@ static int b3_finish(B3Stream& b, hipStream_t st, uint8_t* digests, const std::f
   }
   return GSV_OK;
 }
+// The single-threaded consumer of a B3Stream, for whoever receives streams and hashes them on one thread: the streaming evaluators, the
+// two commitments to streams that lie in device memory and gsv_engine_blake3_files (the drain absorbs on threads of its own:
+// B3Absorbers).  The group values of a segment sit in the page-locked buffer once `ev` — recorded behind the segment's hash kernels —
+// has passed; they are looked at when the next segment is fed, or at flush().  With a `check` (verified mode) every value is compared
+// with the outboard of its instance before it is absorbed, and a difference ends the pass with GSV_ERR_MISMATCH: `check` holds the place.
+struct B3Receiver {
+  std::unique_ptr<B3Stream>& slot;  // the caller's: a session keeps its buffers from pass to pass
+  const char* noun;                 // what a mismatch calls a stream: "file", "the ciphertext stream of instance"
+  B3Check* check;                   // the streams' outboards, or null
+  Event ev;
+  uint32_t groups = 0;              // group values per instance in flight
+  bool on = false;                  // begin() has succeeded: feed() hashes (else it does nothing)
+  explicit B3Receiver(std::unique_ptr<B3Stream>& slot_, const char* noun_ = "stream", B3Check* check_ = nullptr) : slot(slot_), noun(noun_), check(check_) {}
+  int begin(size_t n_inst, uint64_t total, uint64_t seg_cap, uint32_t k) {
+    if (int rc = b3_begin(slot, n_inst, total, seg_cap, k)) return rc;
+    HIPCHK(ev.create(hipEventDisableTiming));
+    if (check) check->reset();
+    groups = 0; on = true;
+    return GSV_OK;
+  }
+  int mismatch() const { return fail(GSV_ERR_MISMATCH, check->where(noun)); }
+  // the values in flight: waited for, compared, absorbed
+  int flush() {
+    if (!groups) return GSV_OK;
+    if (hipEventSynchronize(ev.get()) != hipSuccess) return fail(GSV_ERR_DEVICE, "event wait failed");
+    const uint32_t g = groups;
+    groups = 0;
+    if (check && !check->groups_match(slot->pinned.get(), g)) return mismatch();
+    return b3_absorb(*slot, slot->pinned.get(), g, slot->k, 0, 1) ? GSV_OK : fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
+  }
+  // the next n records of every stream (b3_segment), enqueued on st behind a flush(): the page-locked buffer is free for their values
+  int feed(const void* buf, uint64_t stride, uint64_t n, hipStream_t st, const B3Indexed* ix = nullptr) {
+    if (!on) return GSV_OK;
+    int rc = flush();
+    if (rc == GSV_OK) rc = b3_segment(*slot, buf, stride, n, st, &groups, ix);
+    if (rc == GSV_OK && groups && hipEventRecord(ev.get(), st) != hipSuccess) rc = fail(GSV_ERR_DEVICE, "event record failed");
+    return rc;
+  }
+  // The end of the streams: the chunk values behind the last complete group against the outboards, then — with `expected`, n_inst x
+  // expected_len bytes, which needs a `check` — the computed digests against the commitments: a difference there has no group of its
+  // own and is blamed on the last chunk.  `digests` (n_inst x 32) is written only when everything succeeded.
+  int finish(hipStream_t st, uint8_t* digests, const uint8_t* expected = nullptr, uint64_t expected_len = 0) {
+    int rc = flush();
+    if (rc) return rc;
+    std::vector<uint8_t> got(slot->n_inst * 32);
+    rc = b3_finish(*slot, st, got.data(), check ? std::function<int(const uint8_t*, uint32_t)>([this](const uint8_t* vals, uint32_t pend) { return check->pending_match(vals, pend) ? GSV_OK : mismatch(); }) : nullptr);
+    for (size_t i = 0; expected && i < slot->n_inst && rc == GSV_OK; ++i)
+      if (std::memcmp(got.data() + 32 * i, expected + expected_len * i, size_t(expected_len)) != 0) {
+        check->bad_instance = i; check->bad_group = check->n_groups; check->bad_record = (Outboard::chunks(check->n_records) - 1) * 64;
+        rc = mismatch();
+      }
+    if (rc == GSV_OK) std::memcpy(digests, got.data(), got.size());
+    return rc;
+  }
+};
 
 struct gsv_blake3 { Blake3Host h; };
 int gsv_blake3_create(gsv_blake3** out) {
@@ -253,28 +245,26 @@ int gsv_engine_blake3_files(gsv_engine* e, const char* const* paths, uint64_t n_
   if (!e || !paths || !digests) return fail(GSV_ERR_INVALID, "null argument");
   const uint32_t k = knobs::b3_subtree_log2();
   const uint64_t seg_knob = knobs::at_least_1("GSV_DRAIN_SEGMENT_RECORDS");
-  if (k > 20) return fail(GSV_ERR_INVALID, "GSV_B3_SUBTREE_LOG2 must be an integer in [0, 20]");
+  if (int krc = check_b3_k(k)) return krc;
   if (n_files == 0 || n_files > 65535) return fail(GSV_ERR_INVALID, "BLAKE3 commitments take 1 .. 65535 streams at a time");
   const size_t n = size_t(n_files);
-  std::vector<FILE*> files(n, nullptr);
-  struct Closer { std::vector<FILE*>& f; ~Closer() { for (FILE* q : f) if (q) std::fclose(q); } } closer{files};
+  GcFileSource files;
   uint64_t total = 0;
+  std::string why;
   for (size_t i = 0; i < n; ++i) {
     if (!paths[i] || (outboard_paths && !outboard_paths[i])) return fail(GSV_ERR_INVALID, "null path");
-    files[i] = std::fopen(paths[i], "rb");
+    if (!files.add(paths[i], &why)) return fail(GSV_ERR_INVALID, why);
     struct stat sb;
-    if (!files[i] || fstat(fileno(files[i]), &sb) != 0) return fail(GSV_ERR_INVALID, std::string("cannot open ") + paths[i]);
+    if (fstat(fileno(files.file(i)), &sb) != 0) return fail(GSV_ERR_INVALID, std::string("cannot open ") + paths[i]);
     if (sb.st_size < 0 || (uint64_t(sb.st_size) & 15) || uint64_t(sb.st_size) / 16 > Outboard::MAX_RECORDS) return fail(GSV_ERR_INVALID, std::string(paths[i]) + " does not hold whole 16-byte records");
     if (i == 0) total = uint64_t(sb.st_size) / 16;
     else if (uint64_t(sb.st_size) / 16 != total)
       return fail(GSV_ERR_INVALID, "the files must be equally long: " + std::string(paths[0]) + " holds " + std::to_string(total) + " records, " + paths[i] + " " + std::to_string(uint64_t(sb.st_size) / 16));
   }
-  std::unique_ptr<B3Check> check;
+  B3Check check;
   if (outboard_paths) {
-    check.reset(new B3Check());
-    b3_check_shape(*check, n, k, total);
-    std::string why;
-    for (size_t i = 0; i < n; ++i) if (!load_outboard(outboard_paths[i], k, total, &check->bytes[i], &why)) return fail(GSV_ERR_INVALID, why);
+    check.shape(n, k, total);
+    for (size_t i = 0; i < n; ++i) if (!load_outboard(outboard_paths[i], k, total, &check.bytes[i], &why)) return fail(GSV_ERR_INVALID, why);
   }
   // records per file and segment: the knob, or 16 MiB per file within 256 MiB for all of them
   const uint64_t seg = std::max<uint64_t>(1, std::min<uint64_t>(total, seg_knob ? seg_knob : std::max<uint64_t>(4096, std::min<uint64_t>(1ull << 20, (1ull << 24) / n))));
@@ -282,33 +272,12 @@ int gsv_engine_blake3_files(gsv_engine* e, const char* const* paths, uint64_t n_
   const hipStream_t st = e->stream.get();
   DevBuf gate;
   DEVALLOC(gate, n * size_t(seg) * 16, "the segment of the files to hash");
-  std::vector<uint64_t> pos(n, 0);
-  CtUploader up(n, seg, std::min<uint64_t>(seg, CT_STAGE_RECORDS), 0, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t m) -> int {
-    if (pos[i] != first) { if (fseeko(files[i], off_t(first * 16), SEEK_SET) != 0) return 1; pos[i] = first; }
-    if (m && std::fread(dst, 16, m, files[i]) != m) return 1;
-    pos[i] += m;
-    return 0;
-  });
+  CtUploader up(n, seg, std::min<uint64_t>(seg, CT_STAGE_RECORDS), 0, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t m) { return files.read(i, first, dst, m); });
   if (up.alloc() != hipSuccess) return fail(GSV_ERR_DEVICE, "cannot allocate the staging buffers");
   std::unique_ptr<B3Stream> b;
-  int rc = b3_begin(b, n, total, seg, k);
+  B3Receiver rx(b, "file", outboard_paths ? &check : nullptr);
+  int rc = rx.begin(n, total, seg, k);
   if (rc) return rc;
-  Event ev;
-  HIPCHK(ev.create(hipEventDisableTiming));
-  uint32_t groups = 0;  // group values of the segment in flight
-  auto mismatch = [&]() {
-    if (bad_file_out) *bad_file_out = check->bad_instance;
-    if (bad_group_out) *bad_group_out = check->bad_group;
-    return fail(GSV_ERR_MISMATCH, check->where("file"));
-  };
-  auto flush = [&]() -> int {
-    if (!groups) return GSV_OK;
-    if (hipEventSynchronize(ev.get()) != hipSuccess) return fail(GSV_ERR_DEVICE, "event wait failed");
-    const uint32_t g = groups;
-    groups = 0;
-    if (check && !check->groups_match(b->pinned.get(), g)) return mismatch();
-    return b3_absorb(*b, b->pinned.get(), g, k, 0, 1) ? GSV_OK : fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
-  };
   for (uint64_t off = 0; off < total && rc == GSV_OK; off += seg) {
     const uint64_t m = std::min(seg, total - off);
     switch (up.upload(off, m, gate.get(), st)) {
@@ -316,16 +285,14 @@ int gsv_engine_blake3_files(gsv_engine* e, const char* const* paths, uint64_t n_
       case UploadError::Dry: rc = fail(GSV_ERR_INVALID, std::string("read error on ") + paths[up.dry_instance()]); break;
       default: rc = fail(GSV_ERR_DEVICE, "upload of a file segment failed");
     }
-    if (rc == GSV_OK) rc = flush();  // (the page-locked value buffer is free for this segment's values)
-    if (rc == GSV_OK) rc = b3_segment(*b, gate.get(), seg, m, st, &groups);
-    if (rc == GSV_OK && groups && hipEventRecord(ev.get(), st) != hipSuccess) rc = fail(GSV_ERR_DEVICE, "event record failed");
+    if (rc == GSV_OK) rc = rx.feed(gate.get(), seg, m, st);  // (the values of the segment before are looked at first)
   }
-  if (rc == GSV_OK) rc = flush();
-  std::vector<uint8_t> out(n * 32);
-  if (rc == GSV_OK)
-    rc = b3_finish(*b, st, out.data(), check ? std::function<int(const uint8_t*, uint32_t)>([&](const uint8_t* vals, uint32_t pend) { return check->pending_match(vals, pend) ? GSV_OK : mismatch(); }) : nullptr);
+  if (rc == GSV_OK) rc = rx.finish(st, digests);
   (void)hipStreamSynchronize(st);  // (nothing of `gate` or the staging buffers is in flight when they are released)
-  if (rc == GSV_OK) std::memcpy(digests, out.data(), out.size());
+  if (rc == GSV_ERR_MISMATCH) {
+    if (bad_file_out) *bad_file_out = check.bad_instance;
+    if (bad_group_out) *bad_group_out = check.bad_group;
+  }
   return rc;
 }
 // The kernels alone: n_streams streams of records_per_stream records each (data: [stream][record]) are uploaded and fed to the chunk,
@@ -336,7 +303,7 @@ int gsv_engine_blake3_streams(gsv_engine* e, const uint8_t* data, uint64_t n_str
   uint64_t sum = 0, seg_cap = 0;
   for (uint64_t i = 0; i < n_segments; ++i) { sum += segment_records[i]; seg_cap = std::max(seg_cap, segment_records[i]); }
   if (sum != records_per_stream) return fail(GSV_ERR_INVALID, "the segments do not add up to records_per_stream");
-  if (k > 20) return fail(GSV_ERR_INVALID, "GSV_B3_SUBTREE_LOG2 must be an integer in [0, 20]");
+  if (int krc = check_b3_k(k)) return krc;
   if (n_streams == 0 || n_streams > 65535) return fail(GSV_ERR_INVALID, "BLAKE3 commitments take 1 .. 65535 streams at a time");
   if (records_per_stream > (~0ull >> 4) / n_streams) return fail(GSV_ERR_INVALID, "n_streams x records_per_stream x 16 bytes does not fit 64 bits");
   HIPCHK(hipSetDevice(e->device));
@@ -344,27 +311,24 @@ int gsv_engine_blake3_streams(gsv_engine* e, const uint8_t* data, uint64_t n_str
   DEVALLOC(d, size_t(n_streams) * size_t(records_per_stream) * 16, "the streams to hash");
   if (records_per_stream) HIPCHK(hipMemcpyAsync(d.get(), data, size_t(n_streams) * size_t(records_per_stream) * 16, hipMemcpyHostToDevice, e->stream.get()));
   std::unique_ptr<B3Stream> b;
-  int rc = b3_begin(b, size_t(n_streams), records_per_stream, seg_cap, k);
+  B3Receiver rx(b);
+  int rc = rx.begin(size_t(n_streams), records_per_stream, seg_cap, k);
   Event t0, t1;
   HIPCHK(t0.create()); HIPCHK(t1.create());
   HIPCHK(hipEventRecord(t0.get(), e->stream.get()));
   uint64_t off = 0;
-  for (uint64_t i = 0; i < n_segments && rc == GSV_OK; ++i) {
-    uint32_t groups = 0;
-    rc = b3_segment(*b, d.as<uint8_t>() + off * 16, records_per_stream, segment_records[i], e->stream.get(), &groups);
+  for (uint64_t i = 0; i < n_segments && rc == GSV_OK; ++i) {  // (a segment's group values are absorbed before the next one is enqueued)
+    rc = rx.feed(d.as<uint8_t>() + off * 16, records_per_stream, segment_records[i], e->stream.get());
     off += segment_records[i];
-    if (rc == GSV_OK && groups) {
-      HIPCHK(hipStreamSynchronize(e->stream.get()));
-      if (!b3_absorb(*b, b->pinned.get(), groups, k, 0, 1)) rc = fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
-    }
   }
+  if (rc == GSV_OK) rc = rx.flush();  // (in front of t1: the time covers the host's folding between the segments)
   if (rc == GSV_OK) {
     float ms = 0;
     HIPCHK(hipEventRecord(t1.get(), e->stream.get()));
     HIPCHK(hipEventSynchronize(t1.get()));
     HIPCHK(hipEventElapsedTime(&ms, t0.get(), t1.get()));
     e->b3_streams_seconds = double(ms) * 1e-3;
-    rc = b3_finish(*b, e->stream.get(), digests);
+    rc = rx.finish(e->stream.get(), digests);
   }
   (void)hipStreamSynchronize(e->stream.get());  // (nothing of d is in flight when it is released)
   return rc;

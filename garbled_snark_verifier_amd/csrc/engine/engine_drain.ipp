@@ -370,7 +370,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   }
   // BLAKE3: the state lives in the session like the MAC states — a new pass starts it afresh, later slices chain
   if (want_b3) {
-    if (new_pass) { int rc = b3_begin(s->b3, n_inst, s->plan ? s->plan->n_ct : s->replays * g.n_ct, seg_records, s->pass.b3_subtree_log2); if (rc) return rc; }
+    if (new_pass) { int rc = b3_begin(s->b3, n_inst, stream_records(s), seg_records, s->pass.b3_subtree_log2); if (rc) return rc; }
     else if (!s->b3 || s->b3->n_inst != n_inst || s->b3->seg_cap < seg_records) return fail(GSV_ERR_INVALID, "this slice continues a pass whose earlier slices computed no BLAKE3 commitment for these instances");
   }
   if (ev && (s->ct_ring || ev->ct_ring)) return fail(GSV_ERR_INVALID, "garble || evaluate pairs need sessions with explicit launch windows (window_ct_records, e.g. 1 << 28): the default is one whole-pass window over a ciphertext ring");

@@ -16,44 +16,13 @@ int gsv_session_evaluate(gsv_session* s, uint64_t gate_id_base) {
   return launch(s, gate_id_base, true);
 }
 
-// The streaming evaluator (evaluate_streaming_pass below).  BLAKE3 of the uploaded segments.  The group values of a segment sit in the page-locked buffer once `ev` — recorded behind the
-// segment's hash kernels, in front of its scatter — has passed, and are absorbed before the next segment's kernels are enqueued.
-struct EvalB3 {
-  gsv_session* s;
-  uint64_t seg_records;
-  bool on;  // digests were asked for
-  B3Check* check;  // verified mode: the instances' outboards, every group value is compared before it is absorbed (else null)
-  Event ev;
-  uint32_t groups = 0;
-  // the pass ends here: the stream differs from its outboard at the place `check` holds
-  int mismatch() {
-    s->mismatch = true; s->mismatch_instance = check->bad_instance; s->mismatch_group = check->bad_group; s->mismatch_record = check->bad_record;
-    return fail(GSV_ERR_MISMATCH, check->where("the ciphertext stream of instance"));
-  }
-  int flush() {
-    if (!groups) return GSV_OK;
-    if (hipEventSynchronize(ev.get()) != hipSuccess) return fail(GSV_ERR_DEVICE, "event wait failed");
-    if (check && !check->groups_match(s->b3_eval->pinned.get(), groups)) { groups = 0; return mismatch(); }
-    const bool ok = b3_absorb(*s->b3_eval, s->b3_eval->pinned.get(), groups, s->b3_eval->k, 0, 1);
-    groups = 0;
-    return ok ? GSV_OK : fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
-  }
-  // the `n` records per instance just uploaded to the gate-order buffer through `st`
-  int feed(uint64_t n, hipStream_t st) {
-    if (!on) return GSV_OK;
-    int frc = flush();
-    if (frc == GSV_OK) frc = b3_segment(*s->b3_eval, s->ct_gate.get(), seg_records, n, st, &groups);
-    if (frc == GSV_OK && groups && hipEventRecord(ev.get(), st) != hipSuccess) frc = fail(GSV_ERR_DEVICE, "event record failed");
-    return frc;
-  }
-};
 // What the three drivers of one evaluate_streaming_pass share
 struct EvalPass {
   gsv_session* s;
   uint64_t gate_id_base;
   CtUploader& up;
   uint64_t seg_records;  // per instance: stride of the gate-order buffer
-  EvalB3 b3;
+  B3Receiver& b3;        // BLAKE3 of the uploaded segments, when digests were asked for; verified mode: with the instances' outboards
   // `n` records per instance starting at stream index `base` -> the gate-order buffer through `st` (bounded page-locked chunks, hashed as read)
   int upload(uint64_t base, uint64_t n, hipStream_t st) {
     switch (up.upload(base, n, s->ct_gate.get(), st)) {
@@ -63,6 +32,8 @@ struct EvalPass {
       default: return fail(GSV_ERR_DEVICE, "ciphertext upload failed");
     }
   }
+  // the `n` records per instance just uploaded to the gate-order buffer through `st`: hashed in front of their scatter
+  int hash(uint64_t n, hipStream_t st) { return b3.feed(s->ct_gate.get(), seg_records, n, st); }
 };
 // Plan session over a ciphertext ring: the window (the whole pass) is launched FIRST; its calls wait on the device until the host's
 // position counter says their segment has been uploaded.  Segment after segment: wait until the calls whose blocks this segment's
@@ -87,7 +58,7 @@ static int evaluate_plan_ring(EvalPass& p) {
       if (window_done) { rc = fail(GSV_ERR_DEVICE, "internal: the window finished before its ciphertexts were uploaded"); break; }
       // uploads and the scatter go through the side stream (the main stream holds the running window)
       rc = p.upload(sg.ct0, sg.n_ct, s->aux_stream.get());
-      if (rc == GSV_OK) rc = p.b3.feed(sg.n_ct, s->aux_stream.get());
+      if (rc == GSV_OK) rc = p.hash(sg.n_ct, s->aux_stream.get());
       if (rc == GSV_OK) rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, p.seg_records, 1, nullptr, nullptr, s->aux_stream.get());
       if (rc == GSV_OK && hipStreamSynchronize(s->aux_stream.get()) != hipSuccess) rc = fail(GSV_ERR_DEVICE, "ciphertext scatter failed");
       if (rc == GSV_OK) __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);
@@ -112,7 +83,7 @@ static int evaluate_plan_windows(EvalPass& p) {
       const Schedule::Segment& sg = s->sched.segments[q];
       // (the stream orders this segment's uploads behind the scatter of the previous one, which read the same buffer)
       rc = p.upload(sg.ct0, sg.n_ct, s->e->stream.get());
-      if (rc == GSV_OK) rc = p.b3.feed(sg.n_ct, s->e->stream.get());
+      if (rc == GSV_OK) rc = p.hash(sg.n_ct, s->e->stream.get());
       if (rc == GSV_OK) rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, p.seg_records, 1, nullptr, nullptr, nullptr);
     }
     // verified mode: every group value the segments uploaded so far have produced is compared before the window that reads them is launched
@@ -129,7 +100,7 @@ static int evaluate_program_rings(EvalPass& p) {
   for (uint64_t r0 = 0; r0 < total && rc == GSV_OK; r0 += seg) {
     const uint64_t r1 = std::min(total, r0 + seg);
     rc = p.upload(r0 * n_ct, (r1 - r0) * n_ct, s->e->stream.get());
-    if (rc == GSV_OK) rc = p.b3.feed((r1 - r0) * n_ct, s->e->stream.get());
+    if (rc == GSV_OK) rc = p.hash((r1 - r0) * n_ct, s->e->stream.get());
     if (rc == GSV_OK && p.b3.check) rc = p.b3.flush();  // verified mode: compared before the ring is scattered and launched
     if (rc != GSV_OK) break;
     if (gsvk_gather_segment(s->CT.get(), s->ct_stride(), s->dp->ct_pos.as<const uint32_t>(), n_ct, uint32_t(r1 - r0), uint32_t(s->n_inst), s->ct_gate.get(), p.seg_records, 1, s->e->stream.get()) != 0) { rc = fail(GSV_ERR_DEVICE, "ciphertext scatter launch failed"); break; }
@@ -147,13 +118,6 @@ static int evaluate_program_rings(EvalPass& p) {
 // Verified mode (gsv_session_evaluate_streaming_verified): the instances' outboards, already checked against `expected`, and the
 // commitments themselves (n_inst x expected_len bytes) for the last look at the computed digests.
 struct EvalVerify { B3Check check; const uint8_t* expected; uint64_t expected_len; };
-static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests, EvalVerify* vf);
-static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests, EvalVerify* vf = nullptr) {
-  if (vf) { vf->check.next = 0; s->mismatch = false; }  // (the pass the safe-schedule fallback repeats verifies from group 0 again)
-  const int rc = evaluate_streaming_pass_inner(s, gate_id_base, read, hashes, digests, vf);
-  if (rc == GSV_ERR_MISMATCH) s->ran = false;  // no outputs for a stream that did not verify: gsv_session_read_outputs fails as after a pass that never ran
-  return rc;
-}
 static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests, EvalVerify* vf) {
   const Program& g = s->prog();
   if (s->plan) s->windows_launched = 0;
@@ -168,12 +132,10 @@ static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, 
   const size_t T = hashes ? std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n_inst, 16), gsv_drain::usable_cores() > 1 ? gsv_drain::usable_cores() - 1 : 1)) : 0;
   CtUploader up(n_inst, seg_records, std::min<uint64_t>(std::max<uint64_t>(seg_records, 1), CT_STAGE_RECORDS), T, read);
   if (up.alloc() != hipSuccess) return fail(GSV_ERR_DEVICE, "cannot allocate the ciphertext staging buffers");
-  EvalPass p{s, gate_id_base, up, seg_records, {s, seg_records, digests != nullptr, vf ? &vf->check : nullptr}};
-  if (digests) {  // every pass starts the hash afresh (the pass the safe-schedule fallback repeats too)
-    int brc = b3_begin(s->b3_eval, n_inst, s->plan ? s->plan->n_ct : s->replays * g.n_ct, seg_records, s->pass.b3_subtree_log2);
-    if (brc) return brc;
-    HIPCHK(p.b3.ev.create(hipEventDisableTiming));
-  }
+  B3Receiver b3(s->b3_eval, "the ciphertext stream of instance", vf ? &vf->check : nullptr);
+  EvalPass p{s, gate_id_base, up, seg_records, b3};
+  // every pass starts the hash afresh, and verifies from group 0 (the pass the safe-schedule fallback repeats too)
+  if (digests) { int brc = b3.begin(n_inst, stream_records(s), seg_records, s->pass.b3_subtree_log2); if (brc) return brc; }
   if (s->plan) HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));
   HIPCHK(hipEventRecord(s->ev0.get(), s->e->stream.get()));
   int rc = s->plan ? (s->ct_ring ? evaluate_plan_ring(p) : evaluate_plan_windows(p)) : evaluate_program_rings(p);
@@ -181,26 +143,20 @@ static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, 
   if (rc != GSV_OK) return rc;
   if (s->plan) { HIPCHK(hipEventRecord(s->ev1.get(), s->e->stream.get())); rc = gather_plan_outputs(s, true); if (rc) return rc; HIPCHK(hipStreamSynchronize(s->e->stream.get())); rc = check_plan_error(s); if (rc) return rc; }
   up.finish();
-  if (digests) {  // (before the MACs are written: a failure leaves both arrays untouched)
-    rc = p.b3.flush();
-    if (rc == GSV_OK && !vf) rc = b3_finish(*s->b3_eval, s->e->stream.get(), digests);
-    if (rc == GSV_OK && vf) {
-      // the end of a verified pass: the chunk values behind the last complete group against the outboards, then the computed digests
-      // against the commitments (the last chunk was read before the pass; what was uploaded is what counts)
-      std::vector<uint8_t> got(n_inst * 32);
-      B3Check& c = vf->check;
-      rc = b3_finish(*s->b3_eval, s->e->stream.get(), got.data(), [&](const uint8_t* vals, uint32_t pend) { return c.pending_match(vals, pend) ? GSV_OK : p.b3.mismatch(); });
-      for (size_t i = 0; i < n_inst && rc == GSV_OK; ++i)
-        if (std::memcmp(got.data() + 32 * i, vf->expected + vf->expected_len * i, size_t(vf->expected_len)) != 0) {
-          c.bad_instance = i; c.bad_group = c.n_groups; c.bad_record = (Outboard::chunks(c.n_records) - 1) * 64;
-          rc = p.b3.mismatch();
-        }
-      if (rc == GSV_OK) std::memcpy(digests, got.data(), got.size());
-    }
-    if (rc) return rc;
-  }
+  // (before the MACs are written: a failure leaves both arrays untouched.)  The end of a verified pass compares the computed digests with
+  // the commitments: the last chunk was read before the pass, what was uploaded is what counts
+  if (digests) { rc = b3.finish(s->e->stream.get(), digests, vf ? vf->expected : nullptr, vf ? vf->expected_len : 0); if (rc) return rc; }
   if (hashes) up.digests(hashes);
   return GSV_OK;
+}
+static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests, EvalVerify* vf = nullptr) {
+  if (vf) s->mismatch = false;
+  const int rc = evaluate_streaming_pass_inner(s, gate_id_base, read, hashes, digests, vf);
+  if (rc == GSV_ERR_MISMATCH) {  // the stream differs from its outboard at the place the check holds
+    s->mismatch = true; s->mismatch_instance = vf->check.bad_instance; s->mismatch_group = vf->check.bad_group; s->mismatch_record = vf->check.bad_record;
+    s->ran = false;  // no outputs for a stream that did not verify: gsv_session_read_outputs fails as after a pass that never ran
+  }
+  return rc;
 }
 // The evaluator's side of the safe-schedule fallback (engine_drain.ipp, fall_back_to_safe_schedule): a pass that ended with a dependency wait
 // giving up switches the session to one call per launch; a source that can be read again from the start (gc files) is then evaluated
@@ -214,61 +170,56 @@ static int evaluate_streaming_impl(gsv_session* s, uint64_t gate_id_base, const 
   if (s->pass.drain_debug || s->pass.plan_debug) std::fprintf(stderr, "plan session: %s -- repeating the evaluation on the safe schedule (one call per launch)\n", first_error.c_str());
   return evaluate_streaming_pass(s, gate_id_base, read, hashes, digests, vf);
 }
-// In front of a verified pass: the (well-formed) outboard of instance i, folded with the last chunk, must be the commitment.  A
-// difference has no place in the stream: the mismatch names the instance alone.
-static int check_outboard_root(gsv_session* s, const B3Check& c, size_t i, const uint8_t* last, uint64_t last_bytes, const uint8_t* expected, uint64_t expected_len) {
-  Outboard o;
-  uint8_t root[32];
+// In front of a verified pass, before anything is uploaded: every instance's outboard is loaded and bounds-checked against the SESSION's
+// stream length and this pass's k — all of them before any is folded — and then, with `last_chunk`, its root — folded with the
+// instance's last chunk — must be the commitment.  A difference there has no place in the stream: the mismatch names the instance
+// alone.  No kernel has run when this fails.
+//   load(i, k, n_records, out, why) -> the outboard of instance i, well-formed (load_outboard, check_outboard), or false
+//   last_chunk(i, dst, n_records) -> 0 with the last n_records records of instance i's stream in dst; null: the roots are left to the end of the pass
+using LoadOutboard = std::function<bool(size_t, uint32_t, uint64_t, std::vector<uint8_t>*, std::string*)>;
+using LastChunk = std::function<int(size_t, uint8_t*, uint64_t)>;
+static int prepare_verified_pass(gsv_session* s, EvalVerify& vf, const LoadOutboard& load, const LastChunk& last_chunk) {
+  const uint32_t k = s->pass.b3_subtree_log2;
+  if (int krc = check_b3_k(k)) return krc;
+  const uint64_t total = stream_records(s), first_of_last = (Outboard::chunks(total) - 1) * 64;
+  B3Check& c = vf.check;
+  c.shape(s->n_inst, k, total);
+  s->mismatch = false;
   std::string why;
-  if (!Outboard::parse(c.bytes[i].data(), c.bytes[i].size(), &o, &why) || !o.root(last, last_bytes, root, &why)) return fail(GSV_ERR_INVALID, why);
-  if (std::memcmp(root, expected + expected_len * i, size_t(expected_len)) != 0) {
-    s->mismatch = true; s->mismatch_instance = i; s->mismatch_group = s->mismatch_record = ~0ull;
-    s->ran = false;
-    return fail(GSV_ERR_MISMATCH, "outboard or last chunk of instance " + std::to_string(i) + " does not match the commitment");
+  for (size_t i = 0; i < s->n_inst; ++i) if (!load(i, k, total, &c.bytes[i], &why)) return fail(GSV_ERR_INVALID, why);
+  std::vector<uint8_t> last(size_t(total - first_of_last) * 16);
+  for (size_t i = 0; last_chunk && i < s->n_inst; ++i) {
+    if (last_chunk(i, last.data(), total - first_of_last) != 0)
+      return fail(GSV_ERR_EXHAUSTED, "Ciphertext source exhausted: instance " + std::to_string(i) + " holds fewer than " + std::to_string(total) + " ciphertexts");
+    Outboard o;
+    uint8_t root[32];
+    if (!Outboard::parse(c.bytes[i].data(), c.bytes[i].size(), &o, &why) || !o.root(last.data(), last.size(), root, &why)) return fail(GSV_ERR_INVALID, why);
+    if (std::memcmp(root, vf.expected + vf.expected_len * i, size_t(vf.expected_len)) != 0) {
+      s->mismatch = true; s->mismatch_instance = i; s->mismatch_group = s->mismatch_record = ~0ull;
+      s->ran = false;
+      return fail(GSV_ERR_MISMATCH, "outboard or last chunk of instance " + std::to_string(i) + " does not match the commitment");
+    }
   }
   return GSV_OK;
 }
-// FileSource: instance i reads <dir>/gc_<indexes[i]>.bin (indexes == NULL: first_index + i)
+// FileSource: instance i reads <dir>/gc_<indexes[i]>.bin (indexes == NULL: first_index + i).  Verified mode (outboard_dir): the
+// outboards lie in files too, and a file's last chunk lies where the session's stream length puts it.
 static int evaluate_from_files(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint64_t first_index, uint8_t* hashes, uint8_t* digests,
                                const char* outboard_dir = nullptr, const uint8_t* expected = nullptr, uint64_t expected_len = 0) {
   if (!s || !dir) return fail(GSV_ERR_INVALID, "null argument");
-  std::vector<FILE*> files(s->n_inst, nullptr);
-  struct Closer { std::vector<FILE*>& f; ~Closer() { for (FILE*& q : f) if (q) { std::fclose(q); q = nullptr; } } } closer{files};
-  for (size_t i = 0; i < s->n_inst; ++i) {
-    const std::string path = std::string(dir) + "/gc_" + std::to_string(indexes ? indexes[i] : first_index + i) + ".bin";
-    files[i] = std::fopen(path.c_str(), "rb");
-    if (!files[i]) return fail(GSV_ERR_INVALID, "cannot open " + path);
-  }
-  // the reads of one instance are sequential in the stream, but the instances alternate: seek when the position is not the expected one
-  std::vector<uint64_t> pos(s->n_inst, 0);
-  // Verified mode, before anything is uploaded: every instance's outboard is read and bounds-checked against the SESSION's stream length
-  // and this pass's k, and its root — folded with the file's last chunk, which lies where the session's stream length puts it — must be
-  // the commitment.  No kernel has run when this fails.
-  std::unique_ptr<EvalVerify> vf;
+  auto index = [&](size_t i) { return indexes ? indexes[i] : first_index + i; };
+  GcFileSource files;
+  std::string why;
+  for (size_t i = 0; i < s->n_inst; ++i)
+    if (!files.add(std::string(dir) + "/gc_" + std::to_string(index(i)) + ".bin", &why)) return fail(GSV_ERR_INVALID, why);
+  EvalVerify vf{B3Check(), expected, expected_len};
   if (outboard_dir) {
-    const uint32_t k = s->pass.b3_subtree_log2;
-    if (k > 20) return fail(GSV_ERR_INVALID, "GSV_B3_SUBTREE_LOG2 must be an integer in [0, 20]");
-    const uint64_t total = s->plan ? s->plan->n_ct : s->replays * s->prog().n_ct, dev_chunks = Outboard::chunks(total) - 1;
-    vf.reset(new EvalVerify{B3Check(), expected, expected_len});
-    B3Check& c = vf->check;
-    b3_check_shape(c, s->n_inst, k, total);
-    s->mismatch = false;
-    std::vector<uint8_t> last(size_t(Outboard::last_chunk_bytes(total)));
-    for (size_t i = 0; i < s->n_inst; ++i) {
-      std::string why;
-      if (!load_outboard(OutboardWriter::path(outboard_dir, indexes ? indexes[i] : first_index + i), k, total, &c.bytes[i], &why)) return fail(GSV_ERR_INVALID, why);
-      if (!last.empty() && (fseeko(files[i], off_t(dev_chunks * 1024), SEEK_SET) != 0 || std::fread(last.data(), 1, last.size(), files[i]) != last.size()))
-        return fail(GSV_ERR_EXHAUSTED, "Ciphertext source exhausted: instance " + std::to_string(i) + " holds fewer than " + std::to_string(total) + " ciphertexts");
-      pos[i] = total;  // (where the file's position stands now: the pass seeks back)
-      if (int rrc = check_outboard_root(s, c, i, last.data(), last.size(), expected, expected_len)) return rrc;
-    }
+    const int vrc = prepare_verified_pass(s, vf,
+        [&](size_t i, uint32_t k, uint64_t n_records, std::vector<uint8_t>* out, std::string* w) { return load_outboard(OutboardWriter::path(outboard_dir, index(i)), k, n_records, out, w); },
+        [&](size_t i, uint8_t* dst, uint64_t n) { return files.read(i, stream_records(s) - n, dst, n); });
+    if (vrc) return vrc;
   }
-  return evaluate_streaming_impl(s, gate_id_base, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t n) -> int {
-    if (pos[i] != first) { if (fseeko(files[i], off_t(first * 16), SEEK_SET) != 0) return 1; pos[i] = first; }
-    if (n && std::fread(dst, 16, n, files[i]) != n) return 1;
-    pos[i] += n;
-    return 0;
-  }, hashes, digests, /*rereadable=*/true, vf.get());
+  return evaluate_streaming_impl(s, gate_id_base, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t n) { return files.read(i, first, dst, n); }, hashes, digests, /*rereadable=*/true, outboard_dir ? &vf : nullptr);
 }
 int gsv_session_evaluate_streaming(gsv_session* s, uint64_t gate_id_base, const char* dir, uint64_t first_index, uint8_t* hashes) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
@@ -323,21 +274,15 @@ int gsv_session_evaluate_streaming_source_verified(gsv_session* s, uint64_t gate
   if (!s || !source || !outboards || !outboard_bytes || !expected || !blake3_digests) return fail(GSV_ERR_INVALID, "null argument");
   if (expected_len != 16 && expected_len != 32) return fail(GSV_ERR_INVALID, "expected_len must be 16 (a truncated digest) or 32");
   if (s->plan && s->ct_ring) return fail(GSV_ERR_INVALID, VERIFIED_OVER_A_RING);
-  const uint32_t k = s->pass.b3_subtree_log2;
-  if (k > 20) return fail(GSV_ERR_INVALID, "GSV_B3_SUBTREE_LOG2 must be an integer in [0, 20]");
-  const uint64_t total = s->plan ? s->plan->n_ct : s->replays * s->prog().n_ct, last_bytes = Outboard::last_chunk_bytes(total);
   EvalVerify vf{B3Check(), expected, expected_len};
-  B3Check& c = vf.check;
-  b3_check_shape(c, s->n_inst, k, total);
-  s->mismatch = false;
-  // every outboard is parsed and bounds-checked before any of them is folded, and all of that before the source is called
-  for (size_t i = 0; i < s->n_inst; ++i) {
-    std::string why;
-    if (!outboards[i]) return fail(GSV_ERR_INVALID, "null outboard");
-    if (!check_outboard("outboards[" + std::to_string(i) + "]", outboards[i], outboard_bytes[i], k, total, &why)) return fail(GSV_ERR_INVALID, why);
-    c.bytes[i].assign(outboards[i], outboards[i] + outboard_bytes[i]);
-  }
-  for (size_t i = 0; last_chunks && i < s->n_inst; ++i)
-    if (int rrc = check_outboard_root(s, c, i, last_chunks + 1024 * i, last_bytes, expected, expected_len)) return rrc;
+  const int vrc = prepare_verified_pass(s, vf,
+      [&](size_t i, uint32_t k, uint64_t n_records, std::vector<uint8_t>* out, std::string* why) {
+        if (!outboards[i]) { *why = "null outboard"; return false; }
+        if (!check_outboard("outboards[" + std::to_string(i) + "]", outboards[i], outboard_bytes[i], k, n_records, why)) return false;
+        out->assign(outboards[i], outboards[i] + outboard_bytes[i]);
+        return true;
+      },
+      last_chunks ? LastChunk([&](size_t i, uint8_t* dst, uint64_t n) { if (n) std::memcpy(dst, last_chunks + 1024 * i, size_t(n) * 16); return 0; }) : LastChunk());
+  if (vrc) return vrc;
   return evaluate_streaming_impl(s, gate_id_base, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t n) -> int { return source(user, i, first, dst, n); }, cbcmac_hashes, blake3_digests, /*rereadable=*/false, &vf);
 }

@@ -271,6 +271,8 @@ struct gsv_session {
   ~gsv_session();  // selects the device and synchronises the engine's stream; the members then release what they hold
   uint64_t ct_stride() const { return plan ? (plan_retain ? plan->n_ct : plan_max_block) : ct_cap * p->prog.n_ct; }  // n_ct does not depend on the variant
 };
+// records of one instance's whole ciphertext stream: what a streaming pass drains or reads, and what a commitment covers
+static inline uint64_t stream_records(const gsv_session* s) { return s->plan ? s->plan->n_ct : s->replays * s->prog().n_ct; }
 PassGuard::PassGuard(gsv_session* s) { if (s) s->pass = knobs::Pass(); ReleaseGate& g = release_gate(); std::lock_guard<std::recursive_mutex> lk(g.mu); ++g.active; }
 
 // Failure paths release whatever was allocated so far through the public destroy functions (a failed hipMalloc on a

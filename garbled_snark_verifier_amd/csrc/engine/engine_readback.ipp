@@ -134,23 +134,19 @@ int gsv_session_ciphertext_blake3(gsv_session* s, uint8_t* digests) {
   cap = std::min(cap, std::max<uint64_t>(total, 1));
   const hipStream_t st = s->e->stream.get();
   std::unique_ptr<B3Stream> b;
+  B3Receiver rx(b);
   struct Quiesce { hipStream_t st; ~Quiesce() { (void)hipStreamSynchronize(st); } } quiesce{st};  // declared after `b`: nothing of its buffers is in flight when they go
-  int rc = b3_begin(b, s->n_inst, total, cap, kn.b3_subtree_log2);
+  int rc = rx.begin(s->n_inst, total, cap, kn.b3_subtree_log2);
   if (rc) return rc;
   Event t0, t1;
   HIPCHK(t0.create()); HIPCHK(t1.create());
   HIPCHK(hipEventRecord(t0.get(), st));
-  // records [first, first + n) of the gate-order stream of one block (block_off records into every instance's stream, n_ct records per replay)
+  // records [first, first + n) of the gate-order stream of one block (block_off records into every instance's stream, n_ct records per replay);
+  // the group values of a range are out of the page-locked buffer before the next range is enqueued
   auto feed = [&](uint64_t block_off, const DevBuf& ct_pos, uint64_t n_ct, uint64_t block_records) -> int {
     for (uint64_t first = 0; first < block_records; first += cap) {
       const B3Indexed ix{ct_pos.get(), n_ct, first};
-      uint32_t groups = 0;
-      int frc = b3_segment(*b, static_cast<const uint8_t*>(s->CT.get()) + block_off * 16, s->ct_stride(), std::min(cap, block_records - first), st, &groups, &ix);
-      if (frc) return frc;
-      if (groups) {  // the group values sit in the page-locked buffer once the stream is idle, and must be out of it before the next range
-        HIPCHK(hipStreamSynchronize(st));
-        if (!b3_absorb(*b, b->pinned.get(), groups, b->k, 0, 1)) return fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
-      }
+      if (int frc = rx.feed(static_cast<const uint8_t*>(s->CT.get()) + block_off * 16, s->ct_stride(), std::min(cap, block_records - first), st, &ix)) return frc;
     }
     return GSV_OK;
   };
@@ -160,13 +156,14 @@ int gsv_session_ciphertext_blake3(gsv_session* s, uint8_t* digests) {
       const uint64_t n_ct = s->call_prog(k).n_ct;
       if (n_ct) rc = feed(s->plan->calls[k].ct_off, s->call_dev[k]->ct_pos, n_ct, n_ct);
     }
+  if (rc == GSV_OK) rc = rx.flush();  // (in front of t1: the time covers the host's folding between the ranges)
   if (rc) return rc;
   float ms = 0;
   HIPCHK(hipEventRecord(t1.get(), st));
   HIPCHK(hipEventSynchronize(t1.get()));
   HIPCHK(hipEventElapsedTime(&ms, t0.get(), t1.get()));
   s->e->b3_streams_seconds = double(ms) * 1e-3;
-  rc = b3_finish(*b, st, digests);
+  rc = rx.finish(st, digests);
   if (rc) return rc;
   return s->plan ? check_plan_error(s) : GSV_OK;  // (behind an asynchronous garble: a pass whose dependency wait gave up left no stream to commit to)
 }

@@ -1,8 +1,9 @@
 // The BLAKE3 outboard of a ciphertext stream (include/gsv_engine.h, "BLAKE3 outboards"): the values the host absorbs when a stream is
 // hashed on the device — one 32-byte value per aligned group of 2^k chunks, then the chunk values behind the last complete group —
 // kept in a file beside gc_<i>.bin, or handed to a host callback, instead of thrown away.  One level of the tree, a format of this project's own: NOT Bao.  This
-// header parses and folds an outboard and computes one on the host for a file that already exists; it needs host_crypto.hpp and the
-// standard library only (the drain-side writer is OutboardWriter, drain_pipeline.hpp).
+// header parses and folds an outboard, computes one on the host for a file that already exists, and loads the outboards of a set of
+// streams and compares them with the values a receiver's streams hash to (B3Check); it needs host_crypto.hpp and the standard library
+// only (the drain-side writer is OutboardWriter, drain_pipeline.hpp).
 #pragma once
 #include <sys/types.h>
 
@@ -134,5 +135,72 @@ inline bool outboard_of_file(const char* path, uint32_t k, std::vector<uint8_t>*
   last_chunk->resize(size_t(Outboard::last_chunk_bytes(n_records)));
   if (!last_chunk->empty() && std::fread(last_chunk->data(), 1, last_chunk->size(), f) != last_chunk->size()) { *why = std::string("read error on ") + path; return false; }
   return true;
+}
+
+// The outboards a set of streams is verified against, by whoever receives the values the host absorbs (B3Receiver, engine_blake3.ipp):
+// a streaming evaluation in verified mode and gsv_engine_blake3_files.  Every value is compared, in the order it arrives, with the
+// outboard of its instance; the first difference — the lowest group, then the lowest instance — is kept.
+struct B3Check {
+  std::vector<std::vector<uint8_t>> bytes;  // per instance: a well-formed outboard for `k` and `n_records`
+  uint32_t k = 0;
+  uint64_t n_records = 0, n_groups = 0, n_pending = 0;
+  uint64_t next = 0;                        // group values compared so far, per instance
+  size_t bad_instance = 0;
+  uint64_t bad_group = 0, bad_record = 0;   // the group (the open tail behind the last complete group: n_groups) and the first record the value covers
+  // for n_inst streams of n_records records in groups of 2^k chunks, the outboards still to be filled in
+  void shape(size_t n_inst, uint32_t k_, uint64_t n_records_) {
+    const uint64_t dev_chunks = Outboard::chunks(n_records_) - 1;
+    k = k_; n_records = n_records_; n_groups = dev_chunks >> k; n_pending = dev_chunks & ((1ull << k) - 1);
+    bytes.resize(n_inst);
+  }
+  void reset() { next = 0; }  // the streams start again from group 0
+  const uint8_t* value(size_t i, uint64_t v) const { return bytes[i].data() + Outboard::HEADER_BYTES + 32 * v; }
+  // `groups` group values per instance, [instance][group] dense
+  bool groups_match(const uint8_t* vals, uint32_t groups) {
+    if (next + groups > n_groups) { bad_instance = 0; bad_group = n_groups; bad_record = (n_groups << k) * 64; return false; }
+    for (uint32_t g = 0; g < groups; ++g)
+      for (size_t i = 0; i < bytes.size(); ++i)
+        if (std::memcmp(vals + (i * groups + g) * 32, value(i, next + g), 32) != 0) { bad_instance = i; bad_group = next + g; bad_record = ((next + g) << k) * 64; return false; }
+    next += groups;
+    return true;
+  }
+  // the chunk values behind the last complete group, [instance][value] dense
+  bool pending_match(const uint8_t* vals, uint32_t pend) {
+    if (next != n_groups || pend != n_pending) { bad_instance = 0; bad_group = std::min(next, n_groups); bad_record = (bad_group << k) * 64; return false; }
+    for (uint32_t c = 0; c < pend; ++c)
+      for (size_t i = 0; i < bytes.size(); ++i)
+        if (std::memcmp(vals + (i * pend + c) * 32, value(i, n_groups + c), 32) != 0) { bad_instance = i; bad_group = n_groups; bad_record = ((n_groups << k) + c) * 64; return false; }
+    return true;
+  }
+  std::string where(const char* what) const {
+    return std::string(what) + " " + std::to_string(bad_instance) + " does not match its outboard in group " + std::to_string(bad_group) + " (from record " + std::to_string(bad_record) + ")";
+  }
+};
+// The whole of `path` (at most `most` bytes are accepted) -> *out.  False: *why.
+inline bool read_small_file(const std::string& path, uint64_t most, std::vector<uint8_t>* out, std::string* why) {
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) { *why = "cannot open " + path; return false; }
+  out->resize(size_t(most) + 1);
+  const size_t n = std::fread(out->data(), 1, out->size(), f);
+  const bool bad = std::ferror(f) != 0;
+  std::fclose(f);
+  if (bad) { *why = "read error on " + path; return false; }
+  out->resize(n);
+  return true;
+}
+// The outboard at `path` for a stream of n_records records in groups of 2^k chunks -> *out, parsed and bounds-checked.  A header that
+// says otherwise, and a length that does not follow from it, are refused (*why names both sides).
+// ... `name` being the file's path, or what else the message should call an outboard that came in memory
+inline bool check_outboard(const std::string& name, const uint8_t* p, uint64_t n_bytes, uint32_t k, uint64_t n_records, std::string* why) {
+  Outboard o;
+  if (!Outboard::parse_header(p, n_bytes, &o, why)) { *why = name + ": " + *why; return false; }
+  if (o.n_records != n_records) { *why = name + " is the outboard of a stream of " + std::to_string(o.n_records) + " records, the stream here holds " + std::to_string(n_records); return false; }
+  if (o.k != k) { *why = name + " was written for groups of 2^" + std::to_string(o.k) + " chunks, this pass reduces groups of 2^" + std::to_string(k) + " (GSV_B3_SUBTREE_LOG2)"; return false; }
+  if (!Outboard::parse(p, n_bytes, &o, why)) { *why = name + ": " + *why; return false; }
+  return true;
+}
+inline bool load_outboard(const std::string& path, uint32_t k, uint64_t n_records, std::vector<uint8_t>* out, std::string* why) {
+  if (!read_small_file(path, Outboard::file_bytes(n_records, k), out, why)) return false;
+  return check_outboard(path, out->data(), out->size(), k, n_records, why);
 }
 }  // namespace gsv

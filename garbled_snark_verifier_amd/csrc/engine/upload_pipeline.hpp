@@ -1,17 +1,20 @@
-// The host side of the streaming evaluator (engine_evaluate.ipp): the page-locked staging buffers a ciphertext source is read into, the
-// H2D copies out of them, and the pool of workers that folds each instance's chunks into its CBC-MAC beside the copies.  As in
+// The host side of the streaming evaluator (engine_evaluate.ipp): the page-locked staging buffers a ciphertext source is read into, the H2D
+// copies out of them, the pool of workers that folds each instance's chunks into its CBC-MAC beside the copies, and the file source.  As in
 // drain_pipeline.hpp nothing here knows sessions, schedules, plans or knobs — plain values in — and nothing but the HIP runtime API,
 // hip_owned.hpp, host_crypto.hpp and the standard library is needed: this header compiles alone (tests/upload_pipeline runs it against
 // stand-ins for the HIP calls, also under the thread and address sanitizers).
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <sys/types.h>
 
 #include <algorithm>
 #include <condition_variable>
 #include <cstdint>
+#include <cstdio>
 #include <deque>
 #include <functional>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -117,5 +120,34 @@ class CtUploader {
   uint64_t dry_record_ = 0;
   std::vector<CbcMacHost> macs_;
   MacPool pool_;  // last: its threads read `stage_` and write `macs_`
+};
+
+// A CiphertextSource over files of 16-byte records, one per instance (FileSource, ciphertext_source.rs:14-107), closed when this goes.
+// The reads of one instance are sequential in the stream, but the instances alternate: read() seeks only when the file's position is
+// not the expected one.
+class GcFileSource {
+ public:
+  GcFileSource() = default;
+  GcFileSource(const GcFileSource&) = delete; GcFileSource& operator=(const GcFileSource&) = delete;
+  ~GcFileSource() { for (FILE* f : files_) std::fclose(f); }
+  // the file of the next instance.  False: *why names the path.
+  bool add(const std::string& path, std::string* why) {
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) { *why = "cannot open " + path; return false; }
+    files_.push_back(f); pos_.push_back(0);
+    return true;
+  }
+  size_t size() const { return files_.size(); }
+  FILE* file(size_t i) const { return files_[i]; }  // (for fstat; the position is read()'s)
+  // records [first, first + n) of instance i -> dst; 0, or non-zero when the file ends before them (CtUploader::Read)
+  int read(size_t i, uint64_t first, uint8_t* dst, uint64_t n) {
+    if (pos_[i] != first) { pos_[i] = ~0ull; if (fseeko(files_[i], off_t(first * 16), SEEK_SET) != 0) return 1; pos_[i] = first; }
+    if (n && std::fread(dst, 16, n, files_[i]) != n) { pos_[i] = ~0ull; return 1; }
+    pos_[i] += n;
+    return 0;
+  }
+ private:
+  std::vector<FILE*> files_;
+  std::vector<uint64_t> pos_;  // per file: the record its position stands at (~0 after a failed seek or a short read: the next read seeks)
 };
 }  // namespace gsv

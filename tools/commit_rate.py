@@ -4,7 +4,7 @@ device with BLAKE3 (DESIGN.md §3 "Commitment stage", §6), and the stand-alone 
 
     python tools/commit_rate.py [--instances 64,1024] [--rounds 2] [--kernel-gib 1] [--out profiles/commit_blake3]
     python tools/commit_rate.py --evaluator [--resident-instances 4] [--evaluate-instances 16] [--out profiles/commit_blake3]
-    python tools/commit_rate.py --receive [--rounds 3] [--evaluate-instances 16] [--parent-so <the parent commit's libgsv_engine.so>] [--out profiles/verified_receive]
+    python tools/commit_rate.py --receive [--rounds 3] [--evaluate-instances 16] [--parent-so <the parent commit's libgsv_engine.so> [--parent-all-legs]] [--out profiles/verified_receive]
 
 The driver touches no GPU.  Every GPU step is a child process of this file under its own `timeout`:
   kernel   gsv.blake3_streams on 16 streams of --kernel-gib GiB each, one segment: device seconds from the first hash kernel to the last
@@ -312,11 +312,12 @@ def _host_outboard(gsv, d, i):
 def child_receive_legs(a):
     """--receive: one round of the legs over the files in --dir, each after a warm run of its own: the host loop (blake3_file over all
     files), blake3_files on the device with and without outboards, evaluate_streaming(commitment="blake3") unverified and verified.
-    With the parent commit's library (--parent-so) the unverified evaluation alone runs (the yardstick of the verified mode)."""
+    With the parent commit's library (--parent-so) the unverified evaluation alone runs (the yardstick of the verified mode), or, with
+    --parent-all-legs (a parent that has every entry point: a refactor's yardstick), all of them."""
     import ctypes
     import resource
-    parent = os.environ.get("GSV_RECEIVE_PARENT") == "1"  # (set by the driver, with GSV_ENGINE_SO naming that library)
-    if parent:
+    parent = os.environ.get("GSV_RECEIVE_PARENT")  # "1": the yardstick leg alone, "all": every leg (set by the driver, with GSV_ENGINE_SO naming that library)
+    if parent == "1":
         # the parent's library lacks the entry points this change adds: they get a stand-in that is never called
         import garbled_snark_verifier_amd as g0
 
@@ -349,7 +350,7 @@ def child_receive_legs(a):
         return ev.evaluate_streaming(a.dir, commitment="blake3", **kw)
 
     legs = {"evaluate_unverified": lambda: evaluate()}
-    if not parent:
+    if parent != "1":
         legs = {"host_blake3_file": lambda: [gsv.blake3_file(f) for f in files],
                 "device_blake3_files_outboards": lambda: gsv.blake3_files(eng, files, obs),
                 "device_blake3_files": lambda: gsv.blake3_files(eng, files),
@@ -400,7 +401,7 @@ def driver_receive(a):
         step("receive_files", 600)
         for _ in range(a.rounds):
             if a.parent_so:
-                step("receive_legs", 300, {"GSV_ENGINE_SO": os.path.abspath(a.parent_so), "GSV_RECEIVE_PARENT": "1"})
+                step("receive_legs", 600 if a.parent_all_legs else 300, {"GSV_ENGINE_SO": os.path.abspath(a.parent_so), "GSV_RECEIVE_PARENT": "all" if a.parent_all_legs else "1"})
             step("receive_legs", 600)
     finally:
         shutil.rmtree(d, ignore_errors=True)
@@ -498,6 +499,7 @@ if __name__ == "__main__":
     ap.add_argument("--evaluate-instances", type=int, default=16)
     ap.add_argument("--receive", action="store_true")
     ap.add_argument("--parent-so", default=None)
+    ap.add_argument("--parent-all-legs", action="store_true")
     ap.add_argument("--dir", default=None)
     ap.add_argument("--child", choices=["kernel", "check", "round", "file", "resident", "evaluate", "receive_files", "receive_legs"])
     ap.add_argument("--batch", type=int, default=64)
