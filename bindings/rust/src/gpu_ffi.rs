@@ -164,6 +164,27 @@ extern "C" {
     pub fn gsv_session_windows_launched(s: *const GsvSession, n: *mut u64) -> c_int;
     // Commitments on the callback paths (include/gsv_engine.h): sizes here, the two session calls below
     pub fn gsv_blake3_outboard_size(n_records: u64, k: u32, outboard_bytes: *mut u64, last_chunk_bytes: *mut u64) -> c_int;
+    // Sliced evaluation (include/gsv_engine.h): calls [first_call, first_call + n_calls) of a plan session, whole windows; `restartable`
+    // keeps a restart point in front of the slice, and after GSV_ERR_MISMATCH / GSV_ERR_EXHAUSTED gsv_session_evaluate_resume_info names
+    // the call to repeat from and the first record to supply again (GSV_ERR_INVALID: nothing to resume).  outboard_dir null: unverified.
+    // The source form is declared with the other callback calls below.
+    pub fn gsv_session_evaluate_streaming_calls(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, restartable: c_int, dir: *const c_char, indexes: *const u64, first_index: u64, outboard_dir: *const c_char, expected: *const u8, expected_len: u64, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int;
+    pub fn gsv_session_evaluate_resume_info(s: *const GsvSession, next_call: *mut u64, next_record: *mut u64) -> c_int;
+}
+
+/// The source form of a sliced evaluation: its outboards come as an array of pointers (`const uint8_t* const*`, null: unverified),
+/// so it is declared apart like the two calls below; the wrapper is what a mode calls.
+mod sliced_source {
+    use super::*;
+    extern "C" {
+        pub(super) fn gsv_session_evaluate_streaming_source_calls(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, restartable: c_int, source: GsvCtSourceFn, user: *mut std::ffi::c_void, outboards: *const *const u8, outboard_bytes: *const u64, last_chunks: *const u8, expected: *const u8, expected_len: u64, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int;
+    }
+}
+/// gsv_session_evaluate_streaming_source_calls: one slice of a plan session's evaluation from the generic source; with `outboards` as
+/// evaluate_streaming_source_verified (the same outboards in every slice).  `restartable`: see gsv_session_evaluate_resume_info.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn evaluate_streaming_source_calls(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, restartable: c_int, source: GsvCtSourceFn, user: *mut std::ffi::c_void, outboards: *const *const u8, outboard_bytes: *const u64, last_chunks: *const u8, expected: *const u8, expected_len: u64, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int {
+    sliced_source::gsv_session_evaluate_streaming_source_calls(s, gate_id_base, first_call, n_calls, restartable, source, user, outboards, outboard_bytes, last_chunks, expected, expected_len, cbcmac_hashes, blake3_digests)
 }
 
 /// The two session calls of "Commitments on the callback paths".  Their callbacks may be NULL, which a Rust `fn` pointer cannot be —

@@ -39,11 +39,13 @@ class CiphertextMismatch(GsvError):
     """GSV_ERR_MISMATCH: a received ciphertext stream differs from its BLAKE3 outboard or commitment.  `instance` is the instance of
     the session (blake3_files: the index into `paths`), `group` the group of 2^k chunks (the tail behind the last complete group
     counts as the group after it) and `first_record` the first record the differing value covers; `group` and `first_record` are
-    None when the outboard or the last chunk did not match the commitment before the pass."""
+    None when the outboard or the last chunk did not match the commitment before the pass.  `resume_call` (Session.evaluate_calls with
+    restartable=True): the call the session was rolled back to and the repeat starts at — Session.resume_info() adds the record —
+    or None when nothing can be resumed."""
 
-    def __init__(self, message, instance=None, group=None, first_record=None):
+    def __init__(self, message, instance=None, group=None, first_record=None, resume_call=None):
         super().__init__(message)
-        self.instance, self.group, self.first_record = instance, group, first_record
+        self.instance, self.group, self.first_record, self.resume_call = instance, group, first_record, resume_call
 
 
 # Device objects are released in dependency order BEFORE the interpreter tears down: a session collected during interpreter
@@ -142,6 +144,7 @@ EXPORTS = [
     "gsv_blake3_outboard_root", "gsv_blake3_file_outboard", "gsv_session_garble_streaming_commit_outboard", "gsv_engine_blake3_files",
     "gsv_session_evaluate_streaming_verified", "gsv_session_mismatch_info", "gsv_session_windows_launched",
     "gsv_blake3_outboard_size", "gsv_session_garble_streaming_sink_commit", "gsv_session_evaluate_streaming_source_verified",
+    "gsv_session_evaluate_streaming_calls", "gsv_session_evaluate_streaming_source_calls", "gsv_session_evaluate_resume_info",
 ]
 
 # CiphertextHandler / CiphertextSource as host callbacks (include/gsv_engine.h: gsv_ct_sink_fn, gsv_ct_source_fn)
@@ -267,6 +270,9 @@ def lib():
         L.gsv_blake3_outboard_size.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.gsv_session_garble_streaming_sink_commit.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, CT_SINK_FN, vp, C.c_int, u8p, u8p, OUTBOARD_SINK_FN, vp, u8p]
         L.gsv_session_evaluate_streaming_source_verified.argtypes = [vp, C.c_uint64, CT_SOURCE_FN, vp, C.POINTER(u8p), C.POINTER(C.c_uint64), u8p, u8p, C.c_uint64, u8p, u8p]
+        L.gsv_session_evaluate_streaming_calls.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_char_p, u8p, C.c_uint64, u8p, u8p]
+        L.gsv_session_evaluate_streaming_source_calls.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, CT_SOURCE_FN, vp, C.POINTER(u8p), C.POINTER(C.c_uint64), u8p, u8p, C.c_uint64, u8p, u8p]
+        L.gsv_session_evaluate_resume_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -276,10 +282,11 @@ def _chk(rc):
         raise GsvError("gsv status %d: %s" % (rc, lib().gsv_last_error().decode(errors="replace")))
 
 
-def _chk_mismatch(rc, place):
-    """_chk, but GSV_ERR_MISMATCH raises CiphertextMismatch at place() = (instance, group[, first_record])."""
+def _chk_mismatch(rc, place, resume=None):
+    """_chk, but GSV_ERR_MISMATCH raises CiphertextMismatch at place() = (instance, group[, first_record]); resume() -> its resume_call."""
     if rc == 5:
-        raise CiphertextMismatch("gsv status 5: %s" % lib().gsv_last_error().decode(errors="replace"), *place())
+        message = "gsv status 5: %s" % lib().gsv_last_error().decode(errors="replace")
+        raise CiphertextMismatch(message, *place(), **({"resume_call": resume()} if resume else {}))
     _chk(rc)
 
 
@@ -1007,27 +1014,53 @@ class Session:
         are unauthenticated.  Either way the pass stops at the first group that differs from its outboard: CiphertextMismatch names
         (instance, group, first_record), and read_outputs then fails."""
         _check_commitment(commitment, False)
-        verified = outboards is not None or expected is not None or last_chunks is not None
-        if verified:
-            if commitment == "cbcmac":
-                raise ValueError("outboards / expected / last_chunks need commitment='blake3' or 'both'")
-            if outboards is None or expected is None:
-                raise ValueError("verified evaluation takes outboards and expected together")
-            obs = [np.frombuffer(bytes(o), np.uint8) for o in outboards]
-            if len(obs) != self.n:
-                raise ValueError("outboards: one per instance")
-            exp_a, exp_len = _pack_expected(expected, self.n)
-            last_a = None
-            if last_chunks is not None:
-                lc = [bytes(x) for x in last_chunks]
-                if len(lc) != self.n or any(len(x) > 1024 for x in lc):
-                    raise ValueError("last_chunks: one per instance, at most 1024 bytes each")
-                last_a = np.zeros((self.n, 1024), np.uint8)
-                for i, x in enumerate(lc):
-                    last_a[i, :len(x)] = np.frombuffer(x, np.uint8)
-            nothing = np.zeros(1, np.uint8)
-            ob_p = (C.POINTER(C.c_uint8) * self.n)(*[_p(o) if o.size else _p(nothing) for o in obs])
-            ob_n = (C.c_uint64 * self.n)(*[o.size for o in obs])
+        ob_p, ob_n, last_a, exp_a, exp_len = self._pack_outboards(commitment, outboards, expected, last_chunks)
+        cb, failure = self._source_callback(source)
+
+        def call(macs, dig):
+            with _gc_paused():
+                if ob_p is not None:
+                    rc = lib().gsv_session_evaluate_streaming_source_verified(self.h, gate_id_base, cb, None, ob_p, ob_n, _p(last_a), _p(exp_a), exp_len, _p(macs), _p(dig))
+                elif dig is None:
+                    rc = lib().gsv_session_evaluate_streaming_source(self.h, gate_id_base, cb, None, _p(macs))
+                else:
+                    rc = lib().gsv_session_evaluate_streaming_source_commit(self.h, gate_id_base, cb, None, _p(macs), _p(dig))
+            if failure:
+                raise failure[0]
+            _chk_mismatch(rc, self.mismatch_info)
+
+        return self._evaluate_commit(commitment, call)
+
+    def _pack_outboards(self, commitment, outboards, expected, last_chunks):
+        """The arguments of a verified evaluation from a source -> (outboard pointers, their lengths, last chunks [n,1024] or None,
+        commitments, bytes per commitment); five times None when none of them is given (unverified)."""
+        if outboards is None and expected is None and last_chunks is None:
+            return None, None, None, None, 0
+        if commitment == "cbcmac":
+            raise ValueError("outboards / expected / last_chunks need commitment='blake3' or 'both'")
+        if outboards is None or expected is None:
+            raise ValueError("verified evaluation takes outboards and expected together")
+        obs = [np.frombuffer(bytes(o), np.uint8) for o in outboards]
+        if len(obs) != self.n:
+            raise ValueError("outboards: one per instance")
+        exp_a, exp_len = _pack_expected(expected, self.n)
+        last_a = None
+        if last_chunks is not None:
+            lc = [bytes(x) for x in last_chunks]
+            if len(lc) != self.n or any(len(x) > 1024 for x in lc):
+                raise ValueError("last_chunks: one per instance, at most 1024 bytes each")
+            last_a = np.zeros((self.n, 1024), np.uint8)
+            for i, x in enumerate(lc):
+                last_a[i, :len(x)] = np.frombuffer(x, np.uint8)
+        nothing = np.zeros(1, np.uint8)
+        ob_p = (C.POINTER(C.c_uint8) * self.n)(*[_p(o) if o.size else _p(nothing) for o in obs])
+        ob_p._keep = (obs, nothing)  # the arrays the pointers point into
+        ob_n = (C.c_uint64 * self.n)(*[o.size for o in obs])
+        return ob_p, ob_n, last_a, exp_a, exp_len
+
+    @staticmethod
+    def _source_callback(source):
+        """`source(instance, first_record, n) -> [n,16] uint8` as a gsv_ct_source_fn, and the list an exception it raises is kept in."""
         failure = []
 
         def _cb(_user, inst, first, ptr, n):
@@ -1044,21 +1077,74 @@ class Session:
                 failure.append(e)
                 return 2
 
-        cb = CT_SOURCE_FN(_cb)
+        return CT_SOURCE_FN(_cb), failure
 
-        def call(macs, dig):
+    def evaluate_calls(self, first_call, n_calls, directory=None, indexes=None, first_index=0, source=None, gate_id_base=0, commitment="cbcmac", outboard_dir=None, outboards=None,
+                       expected=None, last_chunks=None, restartable=False):
+        """Plan sessions: evaluate calls [first_call, first_call + n_calls) only, whole windows of the schedule (windows()), from gc files
+        (`directory`, with `indexes` or `first_index`) or from `source` — evaluate_streaming / evaluate_streaming_indexed /
+        evaluate_from_source in slices (gsv_session_evaluate_streaming_calls / _source_calls).  The wire file, gate ids, the stream
+        position, the MAC states, the BLAKE3 state and the outboard comparison continue from the previous evaluate slice; first_call == 0
+        starts a new pass, every slice asks for the same commitment and verification as the first, and read_outputs succeeds after the
+        slice that ends the pass.  Returns what the whole-pass method returns, the MACs being the states after the slice and the BLAKE3
+        digests None until the slice that ends the pass.  Verified: outboard_dir + expected (files), or outboards + expected
+        [+ last_chunks] (source), in every slice.
+        restartable=True keeps a restart point in front of the slice: when the slice fails with a CiphertextMismatch that has a place
+        or because a file or the source ran dry, the session is rolled back — resume_info() says to which call and from which record
+        the ciphertexts are needed again (CiphertextMismatch.resume_call is that call) — and the repaired slice is simply repeated."""
+        _check_commitment(commitment, False)
+        if (directory is None) == (source is None):
+            raise ValueError("a directory of gc files or a source")
+        if first_call == 0 and n_calls == 0:
+            raise ValueError("an empty slice")  # (0, 0 means the whole pass to the C entry points)
+        macs = np.zeros((self.n, 16), np.uint8) if commitment != "blake3" else None
+        dig = np.zeros((self.n, 32), np.uint8) if commitment != "cbcmac" else None
+        failure = []
+        if source is not None:
+            if outboard_dir is not None or indexes is not None:
+                raise ValueError("outboard_dir / indexes belong to gc files: a source takes outboards")
+            ob_p, ob_n, last_a, exp_a, exp_len = self._pack_outboards(commitment, outboards, expected, last_chunks)
+            cb, failure = self._source_callback(source)
             with _gc_paused():
-                if verified:
-                    rc = lib().gsv_session_evaluate_streaming_source_verified(self.h, gate_id_base, cb, None, ob_p, ob_n, _p(last_a), _p(exp_a), exp_len, _p(macs), _p(dig))
-                elif dig is None:
-                    rc = lib().gsv_session_evaluate_streaming_source(self.h, gate_id_base, cb, None, _p(macs))
-                else:
-                    rc = lib().gsv_session_evaluate_streaming_source_commit(self.h, gate_id_base, cb, None, _p(macs), _p(dig))
-            if failure:
-                raise failure[0]
-            _chk_mismatch(rc, self.mismatch_info)
+                rc = lib().gsv_session_evaluate_streaming_source_calls(self.h, gate_id_base, first_call, n_calls, int(bool(restartable)), cb, None, ob_p, ob_n, _p(last_a), _p(exp_a), exp_len,
+                                                                       _p(macs), _p(dig))
+        else:
+            if outboards is not None or last_chunks is not None:
+                raise ValueError("outboards / last_chunks belong to a source: gc files take outboard_dir")
+            exp_a, exp_len = None, 0
+            if outboard_dir is not None or expected is not None:
+                if commitment == "cbcmac":
+                    raise ValueError("outboard_dir / expected need commitment='blake3' or 'both'")
+                if outboard_dir is None or expected is None:
+                    raise ValueError("verified streaming takes outboard_dir and expected together")
+                exp_a, exp_len = _pack_expected(expected, self.n)
+            idx_p = None
+            if indexes is not None:
+                idx = np.ascontiguousarray(indexes, np.uint64)
+                assert idx.size == self.n
+                idx_p = idx.ctypes.data_as(C.POINTER(C.c_uint64))
+            with _gc_paused():
+                rc = lib().gsv_session_evaluate_streaming_calls(self.h, gate_id_base, first_call, n_calls, int(bool(restartable)), os.fsencode(directory), idx_p, first_index,
+                                                                os.fsencode(outboard_dir) if outboard_dir is not None else None, _p(exp_a), exp_len, _p(macs), _p(dig))
+        if failure:
+            raise failure[0]
+        _chk_mismatch(rc, self.mismatch_info, self._resume_call)
+        m, d = _rows(macs), _rows(dig) if self._ends_pass(first_call, n_calls) else None  # (else the engine leaves `dig` alone)
+        return (m, d) if commitment == "both" else m if commitment == "cbcmac" else d
 
-        return self._evaluate_commit(commitment, call)
+    def resume_info(self):
+        """(next_call, next_record) after a restartable evaluate_calls slice failed and the session was rolled back: the call to repeat
+        from and the first record of every instance's stream that is needed again.  (0, 0): no restart point reaches back far enough,
+        the pass starts again from set_evaluate_inputs.  Raises GsvError when nothing can be resumed."""
+        a, b = C.c_uint64(), C.c_uint64()
+        _chk(lib().gsv_session_evaluate_resume_info(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def _resume_call(self):
+        try:
+            return self.resume_info()[0]
+        except GsvError:
+            return None
 
     def schedule_info(self):
         """Plan sessions: the call-level schedule this session executes (windows, batches of calls side by side, wire-file layout,

@@ -126,11 +126,26 @@ struct B3Receiver {
   Event ev;
   uint32_t groups = 0;              // group values per instance in flight
   bool on = false;                  // begin() has succeeded: feed() hashes (else it does nothing)
+  bool at_end = false;              // finish() ended with a digest that differs from its commitment: a mismatch without a group of its own
   explicit B3Receiver(std::unique_ptr<B3Stream>& slot_, const char* noun_ = "stream", B3Check* check_ = nullptr) : slot(slot_), noun(noun_), check(check_) {}
   int begin(size_t n_inst, uint64_t total, uint64_t seg_cap, uint32_t k) {
     if (int rc = b3_begin(slot, n_inst, total, seg_cap, k)) return rc;
     HIPCHK(ev.create(hipEventDisableTiming));
     if (check) check->reset();
+    groups = 0; on = true;
+    return GSV_OK;
+  }
+  // ... or goes on with streams an earlier receiver began (a later slice of a sliced evaluation): nothing is reset, no value is in
+  // flight — every slice ends with a flush() — and the comparison stands where it stood
+  int resume(size_t n_inst, uint64_t total, uint64_t seg_cap, uint32_t k) {
+    if (!slot || slot->n_inst != n_inst || slot->total != total || slot->k != k)
+      return fail(GSV_ERR_INVALID, "this slice continues a pass whose earlier slices computed no BLAKE3 commitment of this shape (instances, GSV_B3_SUBTREE_LOG2)");
+    // The value buffers were sized for the largest segment of the schedule the pass began on.  A schedule installed in the middle of a
+    // pass is the safe one (fall_back_to_safe_schedule): its windows, and so its segments, are single calls, and a segment of any
+    // schedule holds at least one whole call — its largest segment cannot be larger.  Should that ever change, say so:
+    if (slot->seg_cap < seg_cap)
+      return fail(GSV_ERR_INVALID, "internal: the schedule's largest segment grew in the middle of a pass (" + std::to_string(slot->seg_cap) + " -> " + std::to_string(seg_cap) + " records): the BLAKE3 value buffers of the pass cannot hold it");
+    HIPCHK(ev.create(hipEventDisableTiming));
     groups = 0; on = true;
     return GSV_OK;
   }
@@ -163,12 +178,67 @@ struct B3Receiver {
     for (size_t i = 0; expected && i < slot->n_inst && rc == GSV_OK; ++i)
       if (std::memcmp(got.data() + 32 * i, expected + expected_len * i, size_t(expected_len)) != 0) {
         check->bad_instance = i; check->bad_group = check->n_groups; check->bad_record = (Outboard::chunks(check->n_records) - 1) * 64;
+        at_end = true;
         rc = mismatch();
       }
     if (rc == GSV_OK) std::memcpy(digests, got.data(), got.size());
     return rc;
   }
 };
+
+// ---- what a sliced streaming evaluation carries from slice to slice (engine_evaluate.ipp; include/gsv_engine.h "Sliced evaluation") ----
+// A restart point: the session as it stood when a restartable slice began, before anything of the slice was uploaded.  The wire files
+// (labels and plaintext bits) and the device half of the evaluator's B3Stream are stream-ordered device-to-device copies into buffers
+// allocated at the first restartable slice; the host half is plain values.
+struct EvalRestart {
+  bool held = false;
+  uint64_t call = 0, record = 0;                  // the slice's first call, and its first record
+  DevBuf W, VB, carry[2], cv[2];
+  uint32_t n_slots = 0, global_base = 0;          // the wire-file layout W / VB were copied in (the safe schedule lays it out anew)
+  bool b3 = false;                                // the B3 half below was taken (the pass computes BLAKE3 commitments)
+  int cpar = 0, vpar = 0;
+  uint32_t carry_n = 0, pend = 0;
+  uint64_t chunks_done = 0, records_done = 0;
+  std::vector<Blake3Host> hashers;
+  std::vector<CbcMacHost> macs;
+  uint64_t check_position = 0, windows_launched = 0;
+};
+struct EvalCarry {
+  uint64_t next_call = 0;            // the call the next slice must start with (garbling has a counter of its own: gsv_session::next_call)
+  uint8_t commit = 0;                // what the pass in progress asked for: 1 CBC-MAC, 2 BLAKE3, 4 verified (outboards from files), 8 verified (in memory, up front), 16 (deferred)
+  std::vector<CbcMacHost> macs;      // the per-instance MAC states after the last slice
+  B3Check check;                     // verified passes: the parsed outboards (the slice at call 0 loaded them) and the comparison's position
+  EvalRestart rp[2];                 // [0]: where the last restartable slice began, [1]: the restartable slice before it
+  bool resumable = false;            // the last slice failed and the session was rolled back: to `resume_call` / `resume_record`
+  uint64_t resume_call = 0, resume_record = 0;
+};
+static int ensure_dev(DevBuf& d, size_t bytes, const char* what) {
+  if (d && d.bytes() >= bytes) return GSV_OK;
+  return dev_alloc(d, bytes, what);
+}
+// the device half of a B3Stream and its counts <-> a restart point, through st
+static int b3_save(const B3Stream& b, EvalRestart& r, hipStream_t st) {
+  for (int i = 0; i < 2; ++i) {
+    if (int rc = ensure_dev(r.carry[i], b.carry[i].bytes(), "a restart point's BLAKE3 carries")) return rc;
+    if (int rc = ensure_dev(r.cv[i], b.cv[i].bytes(), "a restart point's BLAKE3 values")) return rc;
+    HIPCHK(hipMemcpyAsync(r.carry[i].get(), b.carry[i].get(), b.carry[i].bytes(), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(r.cv[i].get(), b.cv[i].get(), b.cv[i].bytes(), hipMemcpyDeviceToDevice, st));
+  }
+  r.cpar = b.cpar; r.vpar = b.vpar; r.carry_n = b.carry_n; r.pend = b.pend; r.chunks_done = b.chunks_done; r.records_done = b.records_done;
+  r.hashers = b.hashers;
+  r.b3 = true;
+  return GSV_OK;
+}
+static int b3_restore(B3Stream& b, const EvalRestart& r, hipStream_t st) {
+  for (int i = 0; i < 2; ++i) {
+    if (r.carry[i].bytes() < b.carry[i].bytes() || r.cv[i].bytes() < b.cv[i].bytes()) return fail(GSV_ERR_INVALID, "internal: a restart point of another BLAKE3 stream shape");
+    HIPCHK(hipMemcpyAsync(b.carry[i].get(), r.carry[i].get(), b.carry[i].bytes(), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(b.cv[i].get(), r.cv[i].get(), b.cv[i].bytes(), hipMemcpyDeviceToDevice, st));
+  }
+  b.cpar = r.cpar; b.vpar = r.vpar; b.carry_n = r.carry_n; b.pend = r.pend; b.chunks_done = r.chunks_done; b.records_done = r.records_done;
+  b.hashers = r.hashers;
+  return GSV_OK;
+}
 
 struct gsv_blake3 { Blake3Host h; };
 int gsv_blake3_create(gsv_blake3** out) {

@@ -199,6 +199,7 @@ struct gsv_engine {
 
 struct PairState;
 struct B3Stream;
+struct EvalCarry;
 struct gsv_session {
   gsv_engine* e = nullptr;
   gsv_program* p = nullptr;
@@ -260,6 +261,7 @@ struct gsv_session {
   uint8_t pass_commit = 0;             // commitments of the pass in progress (1 CBC-MAC, 2 BLAKE3): a pass with BLAKE3 carries the same ones in every slice
   std::unique_ptr<B3Stream> b3;        // BLAKE3 commitments of the drained streams: device buffers and per-instance hashers, beside drain->macs (engine_blake3.ipp)
   std::unique_ptr<B3Stream> b3_eval;   // ... of the streams a streaming evaluation reads (gsv_session_evaluate_streaming*_commit): apart from `b3`, which a garbling pass chains from slice to slice
+  std::unique_ptr<EvalCarry> evs;      // a streaming evaluation in slices: next call, MAC states, outboards, restart points (engine_blake3.ipp; created on first use)
   // verified streaming evaluation (gsv_session_evaluate_streaming_verified): where the last such pass found a stream that differs from its outboard
   bool mismatch = false;
   uint64_t mismatch_instance = 0, mismatch_group = 0, mismatch_record = 0;
@@ -267,7 +269,7 @@ struct gsv_session {
   std::vector<DevBuf> ct_gate_more;    // further gate-order buffers of the drain pipeline (ct_gate is the first)
   DevBuf ct_alt;                       // garble -> evaluate on the device: the second program-order ciphertext block
   std::unique_ptr<PairState> pair;     // ... and its stream / events (created on first use)
-  gsv_session();   // (both in engine_drain.ipp, where PairState and B3Stream are complete)
+  gsv_session();   // (both in engine_drain.ipp, where PairState, B3Stream and EvalCarry are complete)
   ~gsv_session();  // selects the device and synchronises the engine's stream; the members then release what they hold
   uint64_t ct_stride() const { return plan ? (plan_retain ? plan->n_ct : plan_max_block) : ct_cap * p->prog.n_ct; }  // n_ct does not depend on the variant
 };

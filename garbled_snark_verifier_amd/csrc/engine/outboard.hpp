@@ -154,6 +154,15 @@ struct B3Check {
     bytes.resize(n_inst);
   }
   void reset() { next = 0; }  // the streams start again from group 0
+  // A restart point of the comparison (a sliced evaluation rolls back to where a slice began): the position is all that moves
+  uint64_t position() const { return next; }
+  void rewind(uint64_t position) { next = position; }
+  // is every outboard still the well-formed one of this shape?  (a host hands the in-memory outboards in again with every slice)
+  bool holds(size_t n_inst, uint32_t k_, uint64_t n_records_) const {
+    if (bytes.size() != n_inst || k != k_ || n_records != n_records_) return false;
+    for (const std::vector<uint8_t>& b : bytes) if (b.size() != Outboard::file_bytes(n_records, k)) return false;
+    return true;
+  }
   const uint8_t* value(size_t i, uint64_t v) const { return bytes[i].data() + Outboard::HEADER_BYTES + 32 * v; }
   // `groups` group values per instance, [instance][group] dense
   bool groups_match(const uint8_t* vals, uint32_t groups) {

@@ -63,7 +63,7 @@ class MacPool {
   std::vector<std::thread> threads_;  // last, as in DrainWorkers
 };
 
-enum class UploadError { None, EventWait, Copy, Dry };  // Copy: the copy or the record of its event; Dry: the source ran out (dry_instance / dry_record)
+enum class UploadError { None, EventWait, Copy, Dry, Order };  // Copy: the copy or the record of its event; Dry: the source ran out (dry_instance / dry_record); Order: `base` is not where the stream stands
 
 // The records of a CiphertextSource on their way to a gate-order device buffer, in bounded page-locked chunks.  With T > 0 the chunks are
 // read CHUNK-major (every instance's chunk at one offset, then the next offset) and instance i's chunks are folded in order by worker
@@ -88,8 +88,17 @@ class CtUploader {
     }
     return hipSuccess;
   }
-  // `n` records per instance starting at stream index `base` -> the gate-order buffer `gate` (seg_records apart) through `st`, hashed as read
+  // A stream that goes on behind records read earlier (a later slice of a pass): the record the first upload() starts at and, with MAC
+  // workers, the per-instance states to go on from (empty: h = 0).  Before the first upload(); without it the stream starts at record 0.
+  void start_at(uint64_t first_record, const std::vector<CbcMacHost>& macs = std::vector<CbcMacHost>()) {
+    next_ = first_record;
+    if (macs.size() == n_inst_) macs_ = macs;
+  }
+  uint64_t next_record() const { return next_; }  // the stream index behind the last upload() that succeeded
+  // `n` records per instance starting at stream index `base` -> the gate-order buffer `gate` (seg_records apart) through `st`, hashed as read.
+  // The uploads of one uploader follow each other in the stream (the MAC chains are serial): any other `base` is UploadError::Order.
   UploadError upload(uint64_t base, uint64_t n, void* gate, hipStream_t st) {
+    if (base != next_) return UploadError::Order;
     const size_t NB = stage_.size();
     for (uint64_t off = 0; off < n; off += chunk_)
       for (size_t i = 0; i < n_inst_; ++i, b_ = (b_ + 1) % NB) {
@@ -102,12 +111,14 @@ class CtUploader {
         if (hipMemcpyAsync(static_cast<uint8_t*>(gate) + (i * seg_records_ + off) * 16, host, m * 16, hipMemcpyHostToDevice, st) != hipSuccess || hipEventRecord(stage_ev_[b_].get(), st) != hipSuccess)
           return UploadError::Copy;
       }
+    next_ = base + n;
     return UploadError::None;
   }
   size_t dry_instance() const { return dry_instance_; }
   uint64_t dry_record() const { return dry_record_; }
   void finish() { pool_.finish(); }  // every queued chunk folded
   void digests(uint8_t* hashes) const { for (size_t i = 0; i < n_inst_; ++i) macs_[i].digest(hashes + 16 * i); }  // n_inst x 16, after finish()
+  const std::vector<CbcMacHost>& mac_states() const { return macs_; }  // after finish(): what the next slice's start_at() takes
  private:
   const size_t n_inst_;
   const uint64_t seg_records_, chunk_;
@@ -116,6 +127,7 @@ class CtUploader {
   std::vector<MappedHost<uint8_t>> stage_;
   std::vector<Event> stage_ev_;
   size_t b_ = 0;  // round robin over the staging buffers, across calls
+  uint64_t next_ = 0;  // the stream index the next upload() must start at
   size_t dry_instance_ = 0;
   uint64_t dry_record_ = 0;
   std::vector<CbcMacHost> macs_;

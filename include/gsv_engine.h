@@ -649,6 +649,70 @@ int gsv_session_evaluate_streaming_source_verified(gsv_session* s, uint64_t gate
                                                    const uint8_t* expected, uint64_t expected_len /* 16 or 32 */,
                                                    uint8_t* cbcmac_hashes /* or NULL */, uint8_t* blake3_digests);
 
+/* ---- Sliced evaluation ------------------------------------------------------------------------------------------------------------
+ * The streaming evaluators of a PLAN session for calls [first_call, first_call + n_calls) only, as gsv_session_garble_streaming_calls
+ * slices the garbler: a receiver evaluates what has arrived, and one that met a bad group or a source that ran dry replaces that part
+ * and goes on instead of reading every file again from record 0.  Two calls, one over files and one over the generic source; each is
+ * unverified with its verification arguments NULL (outboard_dir; outboards) and verified otherwise, with the arguments, checks and THE
+ * GUARANTEE of gsv_session_evaluate_streaming_verified / gsv_session_evaluate_streaming_source_verified.  The whole-pass entry points
+ * above are these calls over the whole range without a restart point.  Program sessions are refused (GSV_ERR_INVALID).
+ *
+ * SLICES.  A slice is made of whole windows of the session's schedule (gsv_session_plan_window), else GSV_ERR_INVALID.  first_call == 0
+ * starts a new pass; any other slice must start where the previous EVALUATE slice ended, else GSV_ERR_INVALID — the counter is apart
+ * from the garbler's, gsv_session_set_unchecked_slices lifts both checks.  first_call = n_calls = 0 is the whole pass; n_calls == 0 at
+ * any other first_call, an empty slice, is GSV_ERR_INVALID.  From slice to
+ * slice the session carries the wire file, the gate ids (gate_id_base plus the calls' own offsets: pass the same base), the stream
+ * position (a slice's first record is its first window's; the files are opened per slice and read from there, a source is called with
+ * first_record values that go on from there), the per-instance CBC-MAC states, the BLAKE3 state and the position of the outboard
+ * comparison.  cbcmac_hashes receives the MAC states after the slice; blake3_digests must be given in every slice of a pass that
+ * commits with BLAKE3 and is written by the slice that ends the pass, left untouched before.  Every slice of a pass must ask for the
+ * same commitments and the same kind of verification (none, outboards from files, in memory up front, in memory deferred) as the
+ * slice at call 0, else GSV_ERR_INVALID.  gsv_session_read_outputs succeeds only after the slice that ends the pass; before, it fails
+ * as after a pass that never ran.
+ * Verified slices: the up-front checks — the outboards' form, k and n_records, and with the last chunks their roots against
+ * `expected` — run in the slice at call 0 only.  The outboards read from outboard_dir stay parsed in the session; in-memory outboards
+ * are handed in again with every slice (and bounds-checked again: a different one fails at the next comparison anyway).  last_chunks
+ * is looked at by the slice at call 0 alone, but its being NULL or not is part of the kind of verification.  The last look at the
+ * computed digests against `expected` — in deferred mode the whole commitment check — happens in the slice that ends the pass.
+ * Over a ciphertext ring (retain_stream = GSV_STREAM_RING) verified slices stay refused; unverified slices follow the garbler's: the
+ * ring's schedule is ONE window, so the only slice is the whole pass, and a restart point is refused (GSV_ERR_INVALID).
+ *
+ * RESTART POINTS, restartable != 0.  Before anything of the slice is uploaded the engine keeps the session as it stands: every
+ * instance's wire file — labels (16 bytes per slot) and plaintext bits (1 byte per slot), gsv_plan_schedule_info.wire_file_slots slots
+ * each — and the device half of the BLAKE3 state, as stream-ordered device-to-device copies, and the host half (hashers, MAC states,
+ * comparison position, next call, the count of gsv_session_windows_launched).  The session holds the restart points of the current and
+ * of the previous restartable slice: TWO copies of the wire files, n_instances x wire_file_slots x 17 bytes each, allocated at the
+ * first restartable slice and released with the session.
+ * A restartable slice that fails with GSV_ERR_MISMATCH at a place in the stream, or with GSV_ERR_EXHAUSTED (a file too short, a source
+ * that returned non-zero), leaves the session rolled back to a restart point, and
+ *     gsv_session_evaluate_resume_info(s, &next_call, &next_record)
+ * names it: the call the repeat starts at and the first record the host must supply again.  Repeat that slice — the file repaired, or a
+ * source that serves from next_record — and go on: the finished pass is the one that never failed, outputs, MACs and digests.
+ * THE OPEN GROUP.  By THE GUARANTEE a launch evaluates the one group per instance that is still open before it is verified, so a
+ * mismatch found in one slice may lie in a group whose first record belongs to the slice before, whose wire file then cannot be
+ * trusted either: when the differing group's first_record (gsv_session_mismatch_info) lies in front of the failing slice's first
+ * record the session is rolled back to the PREVIOUS slice's restart point; when that slice took none, next_call = next_record = 0
+ * and nothing was rolled back: the pass starts again from gsv_session_set_evaluate_inputs.  So that two restart points always
+ * suffice, a verified restartable slice must hold at least one whole group — 64 x 2^k records per instance — else GSV_ERR_INVALID.
+ * A mismatch without a place — the computed digest against `expected` at the end of the pass, deferred mode's commitment check, the
+ * up-front checks — is not resumable, and gsv_session_evaluate_resume_info returns GSV_ERR_INVALID whenever nothing can be resumed.
+ * A failed slice without `restartable` ends the pass as a failed whole pass does.
+ * Safe-schedule fallback: a restartable slice over files is repeated by the engine, alone, from its restart point on the safe
+ * schedule (whose windows are single calls: the host's later call ranges stay valid); a restartable slice over a source fails with
+ * the remedy in its message and the session rolled back — the host's repeat of the slice succeeds; any other slice fails as a
+ * garbling slice does, and the pass starts again. */
+int gsv_session_evaluate_streaming_calls(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, int restartable,
+                                         const char* dir, const uint64_t* indexes /* NULL: first_index + i */, uint64_t first_index,
+                                         const char* outboard_dir /* NULL: unverified */, const uint8_t* expected, uint64_t expected_len /* 16 or 32 */,
+                                         uint8_t* cbcmac_hashes /* or NULL */, uint8_t* blake3_digests /* or NULL; required when verified */);
+int gsv_session_evaluate_streaming_source_calls(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, int restartable,
+                                                gsv_ct_source_fn source, void* user,
+                                                const uint8_t* const* outboards /* NULL: unverified */, const uint64_t* outboard_bytes,
+                                                const uint8_t* last_chunks /* n x 1024, or NULL: deferred mode */,
+                                                const uint8_t* expected, uint64_t expected_len /* 16 or 32 */,
+                                                uint8_t* cbcmac_hashes /* or NULL */, uint8_t* blake3_digests /* or NULL; required when verified */);
+int gsv_session_evaluate_resume_info(const gsv_session* s, uint64_t* next_call, uint64_t* next_record);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@ device with BLAKE3 (DESIGN.md §3 "Commitment stage", §6), and the stand-alone 
     python tools/commit_rate.py [--instances 64,1024] [--rounds 2] [--kernel-gib 1] [--out profiles/commit_blake3]
     python tools/commit_rate.py --evaluator [--resident-instances 4] [--evaluate-instances 16] [--out profiles/commit_blake3]
     python tools/commit_rate.py --receive [--rounds 3] [--evaluate-instances 16] [--parent-so <the parent commit's libgsv_engine.so> [--parent-all-legs]] [--out profiles/verified_receive]
+    python tools/commit_rate.py --receive --slices [--rounds 3] [--parent-so <the parent commit's libgsv_engine.so>] --out profiles/eval_slices
 
 The driver touches no GPU.  Every GPU step is a child process of this file under its own `timeout`:
   kernel   gsv.blake3_streams on 16 streams of --kernel-gib GiB each, one segment: device seconds from the first hash kernel to the last
@@ -317,7 +318,7 @@ def child_receive_legs(a):
     import ctypes
     import resource
     parent = os.environ.get("GSV_RECEIVE_PARENT")  # "1": the yardstick leg alone, "all": every leg (set by the driver, with GSV_ENGINE_SO naming that library)
-    if parent == "1":
+    if parent in ("1", "slices"):
         # the parent's library lacks the entry points this change adds: they get a stand-in that is never called
         import garbled_snark_verifier_amd as g0
 
@@ -343,14 +344,29 @@ def child_receive_legs(a):
     out0 = np.load(os.path.join(a.dir, "out0.npy"))
     files = [os.path.join(a.dir, gsv.gc_file_name(i)) for i in range(B)]
     obs = [os.path.join(a.dir, "gc_%d.b3o" % i) for i in range(B)]
-    ev = gsv.Session(eng, plan, B, retain_stream=False)
+    # (--slices: explicit launch windows of an eighth of the stream for every leg and both libraries — the default schedule of this shape is one window, and a slice is made of whole windows)
+    ev = gsv.Session(eng, plan, B, retain_stream=False, **({"window_ct_records": plan.info["n_ciphertexts"] // 8} if a.slices else {}))
 
     def evaluate(**kw):
         ev.set_evaluate_inputs(consts_active, active, bits)
         return ev.evaluate_streaming(a.dir, commitment="blake3", **kw)
 
+    def evaluate_sliced(restartable):
+        """one window of the schedule per slice, verified (Session.evaluate_calls)"""
+        ev.set_evaluate_inputs(consts_active, active, bits)
+        got = None
+        for first, n, _ in ev.windows():
+            got = ev.evaluate_calls(first, n, directory=a.dir, commitment="blake3", outboard_dir=a.dir, expected=digests, restartable=restartable)
+        return got
+
     legs = {"evaluate_unverified": lambda: evaluate()}
-    if parent != "1":
+    if a.slices:
+        # --slices: the verified evaluation unsliced (the parent's library: the baseline; this one: the thin caller) and, with this
+        # library, in slices of one window without and with restart points
+        legs = {"evaluate_verified": lambda: evaluate(outboard_dir=a.dir, expected=digests)}
+        if not parent:
+            legs.update({"evaluate_verified_sliced": lambda: evaluate_sliced(False), "evaluate_verified_sliced_restartable": lambda: evaluate_sliced(True)})
+    elif parent != "1":
         legs = {"host_blake3_file": lambda: [gsv.blake3_file(f) for f in files],
                 "device_blake3_files_outboards": lambda: gsv.blake3_files(eng, files, obs),
                 "device_blake3_files": lambda: gsv.blake3_files(eng, files),
@@ -368,8 +384,11 @@ def child_receive_legs(a):
         if name.startswith("evaluate"):
             act, ob = ev.read_outputs(with_bits=True)
             ok = ok and bool((act == np.where(ob[:, :, None] == 1, out0 ^ delta[:, None, :], out0)).all())
+    info = ev.schedule_info()
     ev.close()
     print(json.dumps({"step": "receive_legs", "library": "parent" if parent else "this", "instances": B, "file_bytes": sum(os.path.getsize(f) for f in files), "legs": out,
+                      "n_windows": info["n_windows"], "wire_file_slots": info["wire_file_slots"],
+                      "restart_point_bytes": 2 * B * info["wire_file_slots"] * 17,  # two copies of every wire file: labels and plaintext bits
                       "digests_equal_the_garblers_and_outputs_select": ok}), flush=True)
     return 0 if ok else 1
 
@@ -390,6 +409,8 @@ def driver_receive(a):
         if stopped:
             return None
         cmd = ["timeout", "-k", "10", str(seconds), sys.executable, os.path.relpath(os.path.abspath(__file__), ROOT), "--child", name, "--threads", str(a.threads), "--batch", str(a.evaluate_instances), "--dir", d]
+        if a.slices:
+            cmd.append("--slices")
         log_f.write("$ " + " ".join(["python"] + cmd[5:]) + (" (parent library)" if env else "") + "\n"); log_f.flush()
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=log_f, text=True, cwd=ROOT, env=dict(os.environ, **(env or {})))
         log_f.write(p.stdout); log_f.flush()
@@ -401,7 +422,7 @@ def driver_receive(a):
         step("receive_files", 600)
         for _ in range(a.rounds):
             if a.parent_so:
-                step("receive_legs", 600 if a.parent_all_legs else 300, {"GSV_ENGINE_SO": os.path.abspath(a.parent_so), "GSV_RECEIVE_PARENT": "all" if a.parent_all_legs else "1"})
+                step("receive_legs", 600 if a.parent_all_legs else 300, {"GSV_ENGINE_SO": os.path.abspath(a.parent_so), "GSV_RECEIVE_PARENT": "slices" if a.slices else "all" if a.parent_all_legs else "1"})
             step("receive_legs", 600)
     finally:
         shutil.rmtree(d, ignore_errors=True)
@@ -498,6 +519,7 @@ if __name__ == "__main__":
     ap.add_argument("--resident-instances", type=int, default=4)
     ap.add_argument("--evaluate-instances", type=int, default=16)
     ap.add_argument("--receive", action="store_true")
+    ap.add_argument("--slices", action="store_true")
     ap.add_argument("--parent-so", default=None)
     ap.add_argument("--parent-all-legs", action="store_true")
     ap.add_argument("--dir", default=None)
