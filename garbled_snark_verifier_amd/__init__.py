@@ -24,7 +24,8 @@ from . import build as _build
 
 __all__ = ["GsvError", "lib", "Program", "Engine", "Session", "CircuitBuilder", "StreamingResult", "labels_from_seed", "GATE_NAMES", "cbcmac", "cbcmac_many",
            "write_gc_file", "read_gc_file", "gc_file_name", "blake3", "blake3_file", "blake3_streams", "Blake3",
-           "CiphertextMismatch", "outboard_file_name", "blake3_outboard_root", "blake3_file_outboard", "blake3_files", "blake3_outboard_size", "SinkCommit"]
+           "CiphertextMismatch", "outboard_file_name", "blake3_outboard_root", "blake3_file_outboard", "blake3_files", "blake3_outboard_size", "SinkCommit",
+           "checkpoint_file_name", "cbcmac_checkpoints_size", "cbcmac_file_checkpoints", "cbcmac_file_check", "cbcmac_files", "cbcmac_streams_check"]
 
 GATE_NAMES = ["And", "Nand", "Nimp", "Imp", "Ncimp", "Cimp", "Nor", "Or", "Xor", "Xnor", "Not"]
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -145,6 +146,8 @@ EXPORTS = [
     "gsv_session_evaluate_streaming_verified", "gsv_session_mismatch_info", "gsv_session_windows_launched",
     "gsv_blake3_outboard_size", "gsv_session_garble_streaming_sink_commit", "gsv_session_evaluate_streaming_source_verified",
     "gsv_session_evaluate_streaming_calls", "gsv_session_evaluate_streaming_source_calls", "gsv_session_evaluate_resume_info",
+    "gsv_cbcmac_checkpoints_size", "gsv_cbcmac_file_checkpoints", "gsv_cbcmac_file_check", "gsv_engine_cbcmac_streams_check", "gsv_engine_cbcmac_streams_check_seconds",
+    "gsv_engine_cbcmac_files", "gsv_session_garble_streaming_checkpoints", "gsv_session_garble_streaming_check",
 ]
 
 # CiphertextHandler / CiphertextSource as host callbacks (include/gsv_engine.h: gsv_ct_sink_fn, gsv_ct_source_fn)
@@ -273,6 +276,14 @@ def lib():
         L.gsv_session_evaluate_streaming_calls.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_char_p, u8p, C.c_uint64, u8p, u8p]
         L.gsv_session_evaluate_streaming_source_calls.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, CT_SOURCE_FN, vp, C.POINTER(u8p), C.POINTER(C.c_uint64), u8p, u8p, C.c_uint64, u8p, u8p]
         L.gsv_session_evaluate_resume_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.gsv_cbcmac_checkpoints_size.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.gsv_cbcmac_file_checkpoints.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, u8p]
+        L.gsv_cbcmac_file_check.argtypes = [C.c_char_p, C.c_char_p, C.c_int, u8p, C.POINTER(C.c_uint64)]
+        L.gsv_engine_cbcmac_streams_check.argtypes = [vp, u8p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.gsv_engine_cbcmac_streams_check_seconds.argtypes = [vp, C.POINTER(C.c_double)]
+        L.gsv_engine_cbcmac_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(C.c_char_p), u8p, u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.gsv_session_garble_streaming_checkpoints.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int, u8p, C.c_char_p]
+        L.gsv_session_garble_streaming_check.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, u8p, u8p]
         _lib = L
     return _lib
 
@@ -443,6 +454,95 @@ def blake3_streams(engine, array, segments, with_seconds=False):
     s = C.c_double()
     _chk(lib().gsv_engine_blake3_streams_seconds(engine.h, C.byref(s)))
     return digests, s.value
+
+
+_MAC_GROUP_DEFAULT = 0xFFFFFFFF  # GSV_MAC_GROUP_DEFAULT: the knob GSV_MAC_GROUP_LOG2
+_NO_PLACE = (1 << 64) - 1
+
+
+def checkpoint_file_name(index):
+    """The CBC-MAC checkpoints of gc_<index>.bin, beside it (include/gsv_engine.h, "CBC-MAC checkpoints")."""
+    return "gc_%d.mck" % index
+
+
+def cbcmac_checkpoints_size(n_records, k=None):
+    """Bytes of the checkpoint file of a stream of n_records records with a chain state every 2^k records (k <= 30; None:
+    GSV_MAC_GROUP_LOG2)."""
+    a = C.c_uint64()
+    _chk(lib().gsv_cbcmac_checkpoints_size(int(n_records), _MAC_GROUP_DEFAULT if k is None else int(k), C.byref(a)))
+    return int(a.value)
+
+
+def cbcmac_file_checkpoints(path, k=None, out_path=None):
+    """Writes the checkpoints of the file at `path` — its CBC-MAC chain state after every 2^k records (None: GSV_MAC_GROUP_LOG2) — to
+    `out_path` (None: nowhere), on the host; returns the file's CBC-MAC."""
+    out = np.zeros(16, np.uint8)
+    _chk(lib().gsv_cbcmac_file_checkpoints(os.fsencode(path), _MAC_GROUP_DEFAULT if k is None else int(k), os.fsencode(out_path) if out_path is not None else None, _p(out)))
+    return out.tobytes()
+
+
+def cbcmac_file_check(path, checkpoints, threads=0):
+    """The file at `path` against its checkpoint file, on the host, groups in parallel over `threads` threads: (CBC-MAC, None) when
+    every group holds — the CBC-MAC is then the checkpoint file's last state — else (None, the lowest group that does not).  A
+    malformed checkpoint file, or one for another file length, raises GsvError (GSV_ERR_INVALID)."""
+    out = np.zeros(16, np.uint8)
+    bad = C.c_uint64()
+    rc = lib().gsv_cbcmac_file_check(os.fsencode(path), os.fsencode(checkpoints), int(threads), _p(out), C.byref(bad))
+    if rc == 5:
+        return None, int(bad.value)
+    _chk(rc)
+    return out.tobytes(), None
+
+
+def cbcmac_files(engine, paths, checkpoints, expected=None):
+    """CBC-MAC commitments of equally long files verified on the device against their checkpoint files (one path per file), read in
+    bounded segments (GSV_DRAIN_SEGMENT_RECORDS records per file) without evaluating them: a list of 16-byte CBC-MACs.  expected: one
+    trusted 16-byte commitment per file, compared with the checkpoint file's last state before anything is uploaded.  The first
+    difference — the lowest group, then the lowest file — raises CiphertextMismatch(instance = index into paths, group, first_record);
+    group and first_record are None when a last state did not match `expected`."""
+    n = len(paths)
+    assert len(checkpoints) == n
+    arr = (C.c_char_p * max(1, n))(*[os.fsencode(q) for q in paths])
+    cks = (C.c_char_p * max(1, n))(*[os.fsencode(q) for q in checkpoints])
+    exp = None
+    if expected is not None:
+        exp = np.frombuffer(b"".join(bytes(e) for e in expected), np.uint8)
+        if exp.size != 16 * n:
+            raise ValueError("expected: one 16-byte commitment per file")
+    out = np.zeros((max(1, n), 16), np.uint8)
+    bad_file, bad_group = C.c_uint64(), C.c_uint64()
+    rc = lib().gsv_engine_cbcmac_files(engine.h, arr, n, cks, _p(exp), _p(out), C.byref(bad_file), C.byref(bad_group))
+
+    def place():
+        if bad_group.value == _NO_PLACE:
+            return int(bad_file.value), None, None
+        k = int.from_bytes(open(checkpoints[int(bad_file.value)], "rb").read(16)[12:16], "little")
+        return int(bad_file.value), int(bad_group.value), int(bad_group.value) << k
+    _chk_mismatch(rc, place)
+    return _rows(out, n)
+
+
+def cbcmac_streams_check(engine, array, segments, checkpoints, with_seconds=False):
+    """The device check alone: `array` is [n_streams, records, 16] uint8, `segments` the record counts in which the streams are fed to
+    the check kernel (they add up to `records`), `checkpoints` one checkpoint file's bytes per stream.  Returns None when every group
+    of every stream holds, else (stream, group) of the lowest group that does not (then the lowest stream); with_seconds=True:
+    (that, device seconds)."""
+    a = _u8(array)
+    assert a.ndim == 3 and a.shape[2] == 16, a.shape
+    cks = [bytes(c) for c in checkpoints]
+    assert len(cks) == a.shape[0] and len(set(len(c) for c in cks)) == 1
+    ck = np.frombuffer(b"".join(cks), np.uint8)
+    seg = (C.c_uint64 * max(1, len(segments)))(*[int(x) for x in segments])
+    bad_stream, bad_group = C.c_uint64(), C.c_uint64()
+    rc = lib().gsv_engine_cbcmac_streams_check(engine.h, _p(a) if a.size else None, a.shape[0], a.shape[1], seg, len(segments), _p(ck), len(cks[0]), C.byref(bad_stream), C.byref(bad_group))
+    if rc != 5:
+        _chk(rc)
+    found = (int(bad_stream.value), int(bad_group.value)) if rc == 5 else None
+    if not with_seconds:
+        return found
+    s = C.c_double()
+    _chk(lib().gsv_engine_cbcmac_streams_check_seconds(engine.h, C.byref(s)))
+    return found, s.value
 
 
 def cbcmac_chains_per_step():
@@ -834,13 +934,48 @@ class Session:
         """Does the slice [first_call, first_call + n_calls) of a streaming garble (0, 0: all of it) end its pass?"""
         return (first_call == 0 and n_calls == 0) or not isinstance(self.program, Plan) or first_call + n_calls == self.schedule_info()["n_calls"]
 
-    def garble_streaming(self, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False, commitment="cbcmac", outboard_dir=None):
+    def _garble_checkpoints(self, gate_id_base, first_call, n_calls, directory, first_index, threads, checkpoint_dir):
+        out = np.zeros((self.n, 16), np.uint8)
+        with _gc_paused():
+            _chk(lib().gsv_session_garble_streaming_checkpoints(self.h, gate_id_base, first_call, n_calls, directory.encode() if directory else None, first_index, threads, _p(out),
+                                                                os.fsencode(checkpoint_dir)))
+        return _rows(out)
+
+    def garble_check(self, checkpoint_dir, first_index=0, indexes=None, first_call=0, n_calls=0, expected=None, gate_id_base=0):
+        """Garble and verify the streams against the CBC-MAC checkpoint files <checkpoint_dir>/gc_<index>.mck (index = indexes[i], or
+        first_index + i) on the device: nothing is drained and no host MAC worker runs.  Plan sessions may run it in slices (first_call,
+        n_calls; 0, 0: the whole pass), every slice of a pass with the same check.  expected: one trusted 16-byte commitment per
+        instance, compared with the files' last states before anything is launched.  Returns the verified CBC-MACs from the call that
+        ends the pass (None before); a stream that differs raises CiphertextMismatch(instance, group, first_record)."""
+        n = getattr(self, "n_drain", self.n)
+        idx_p = None
+        if indexes is not None:
+            idx = np.ascontiguousarray(indexes, np.uint64)
+            assert idx.size == n
+            idx_p = idx.ctypes.data_as(C.POINTER(C.c_uint64))
+        exp = None
+        if expected is not None:
+            exp = np.frombuffer(b"".join(bytes(e) for e in expected), np.uint8)
+            if exp.size != 16 * n:
+                raise ValueError("expected: one 16-byte commitment per instance")
+        out = np.zeros((n, 16), np.uint8)
+        with _gc_paused():
+            rc = lib().gsv_session_garble_streaming_check(self.h, gate_id_base, first_call, n_calls, os.fsencode(checkpoint_dir), idx_p, first_index, _p(exp), _p(out))
+        _chk_mismatch(rc, self.mismatch_info)
+        return _rows(out) if self._ends_pass(first_call, n_calls) else None
+
+    def garble_streaming(self, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False, commitment="cbcmac", outboard_dir=None, checkpoint_dir=None):
         """Garble all replays while the host drains the stream segment by segment: returns the per-instance ciphertext
         hashes (CBC-MAC, gate order) and, with `directory`, writes gc_<first_index+i>.bin files.  discard=True: garble
         only, the ciphertexts are dropped.  commitment="blake3": 32-byte BLAKE3 digests of the streams instead, computed on the
         device (nothing of the stream is copied out unless `directory` is given); "both": (CBC-MACs, BLAKE3 digests).
-        outboard_dir (with "blake3" / "both"): the BLAKE3 outboards gc_<first_index+i>.b3o are written there."""
+        outboard_dir (with "blake3" / "both"): the BLAKE3 outboards gc_<first_index+i>.b3o are written there.
+        checkpoint_dir (with "cbcmac"): the CBC-MAC checkpoint files gc_<first_index+i>.mck are written there (k = GSV_MAC_GROUP_LOG2)."""
         _check_commitment(commitment, discard, outboard_dir)
+        if checkpoint_dir is not None:
+            if commitment != "cbcmac" or discard:
+                raise ValueError("checkpoint_dir needs commitment='cbcmac' and discard=False: the files hold the states of the CBC-MAC")
+            return self._garble_checkpoints(gate_id_base, 0, 0, directory, first_index, threads, checkpoint_dir)
         if commitment != "cbcmac":
             return self._garble_commit(commitment, gate_id_base, 0, 0, directory, first_index, threads, outboard_dir)
         if discard:
@@ -850,13 +985,20 @@ class Session:
             _chk(lib().gsv_session_garble_streaming(self.h, gate_id_base, directory.encode() if directory else None, first_index, threads, _p(out)))
         return _rows(out)
 
-    def garble_calls(self, first_call, n_calls, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False, commitment="cbcmac", outboard_dir=None):
+    def garble_calls(self, first_call, n_calls, gate_id_base=0, directory=None, first_index=0, threads=0, discard=False, commitment="cbcmac", outboard_dir=None, checkpoint_dir=None):
         """Plan sessions: garble calls [first_call, first_call + n_calls) only (a slice of the plan).  Wires, gate ids and the
         CBC-MAC states continue from the previous slice; first_call == 0 starts a new pass.  Returns the MAC states after the
         slice (the commitments once the last slice has run), or None with discard=True.  commitment="blake3" / "both" as for
         garble_streaming: the BLAKE3 state chains from slice to slice too, the digests are None until the slice that ends the pass.
-        outboard_dir as for garble_streaming, in every slice of the pass: the first slice truncates the outboards, later ones append."""
+        outboard_dir as for garble_streaming, in every slice of the pass: the first slice truncates the outboards, later ones append;
+        checkpoint_dir likewise."""
         _check_commitment(commitment, discard, outboard_dir)
+        if checkpoint_dir is not None:
+            if commitment != "cbcmac" or discard:
+                raise ValueError("checkpoint_dir needs commitment='cbcmac' and discard=False: the files hold the states of the CBC-MAC")
+            if first_call == 0 and n_calls == 0:
+                raise ValueError("an empty slice")  # (0, 0 means the whole pass to the C entry point)
+            return self._garble_checkpoints(gate_id_base, first_call, n_calls, directory, first_index, threads, checkpoint_dir)
         if commitment != "cbcmac":
             if first_call == 0 and n_calls == 0:
                 raise ValueError("an empty slice")  # (0, 0 means the whole pass to the C entry point)

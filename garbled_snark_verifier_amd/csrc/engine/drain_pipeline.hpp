@@ -1,6 +1,6 @@
 // The host side of the streaming drain (engine_drain.ipp): the session's copy streams, pinned chunk buffers and MAC states; where a
 // drained stream goes; the gc_<i>.bin files of a pass and its outboards (gc_<i>.b3o files, or a host callback); the pool of MAC / copy workers behind a queue of
-// segments; the BLAKE3 absorbers.
+// segments; the BLAKE3 absorbers; the CBC-MAC checkpoint files (gc_<i>.mck: the chain states the MAC workers pass through anyway, kept).
 // Each pool owns its threads and joins them in its destructor.  Nothing here knows sessions, schedules, plans or knobs — plain values
 // in — and nothing but the HIP runtime API, hip_owned.hpp, host_crypto.hpp and the standard library is needed: this header compiles
 // alone (tests/drain_pipeline runs it against stand-ins for the HIP calls, also under the thread and address sanitizers).
@@ -23,6 +23,7 @@
 
 #include "hip_owned.hpp"
 #include "host_crypto.hpp"
+#include "mac_checkpoints.hpp"
 #include "outboard.hpp"
 
 namespace gsv {
@@ -86,9 +87,16 @@ struct DrainSink {
   OutboardSinkFn ob_fn = nullptr;      // ... or handed to the host as they are produced (needs b3)
   void* ob_user = nullptr;
   uint8_t* last_chunks = nullptr;      // n_inst x 1024: the streams' last chunks, zero-padded, written with b3 (needs b3)
+  const char* checkpoint_dir = nullptr;  // gc_<index>.mck: the MAC states after every 2^k records, kept (needs hashes)
+  // the CBC-MAC check on the device (engine_cbcmac.ipp): the streams are verified against the checkpoint files gc_<index>.mck of
+  // mac_check_dir, index = mac_check_indexes ? mac_check_indexes[i] : first_index + i; nothing leaves the device and no MAC worker starts
+  const char* mac_check_dir = nullptr;
+  const uint64_t* mac_check_indexes = nullptr;
+  const uint8_t* mac_check_expected = nullptr;  // n_inst x 16 or null: the commitments the caller trusts
+  uint8_t* mac_check_hashes = nullptr;          // n_inst x 16 or null: the verified commitments, written by the call that ends the pass
   bool outboard() const { return outboard_dir || ob_fn; }
   bool host() const { return hashes || dir || fn; }  // the stream is copied to the host
-  bool any() const { return host() || b3; }
+  bool any() const { return host() || b3 || mac_check_dir; }
 };
 
 // The gc_<first_index + i>.bin files of one call.  Closed when the object goes away and REMOVED unless keep() was called: a failed pass
@@ -194,6 +202,54 @@ class OutboardWriter {
 };
 using OutboardFiles = OutboardWriter;  // (the name from before the callback back end)
 
+// The CBC-MAC checkpoint files of one call (mac_checkpoints.hpp): gc_<first_index + i>.mck — a header, then the chain state after every
+// 2^k records and at the end of the stream, in stream order.  A new pass writes the header, a later slice appends; closed when the
+// object goes away and REMOVED unless keep() was called, like the gc files beside them.  The MAC workers write them: instances may be
+// written from different threads, one instance from one thread at a time.
+class CheckpointWriter {
+ public:
+  CheckpointWriter() = default;
+  CheckpointWriter(const CheckpointWriter&) = delete;
+  CheckpointWriter& operator=(const CheckpointWriter&) = delete;
+  ~CheckpointWriter() {
+    for (FILE* f : files_) std::fclose(f);
+    if (!keep_) for (const std::string& q : paths_) std::remove(q.c_str());
+  }
+  static std::string path(const char* dir, uint64_t index) { return std::string(dir) + "/gc_" + std::to_string(index) + ".mck"; }
+  // new_pass: truncate and write the header for a stream of n_records records in groups of 2^k records; else append.  False: `*failed`.
+  bool open(const char* dir, uint64_t first_index, size_t n_inst, bool new_pass, uint32_t k, uint64_t n_records, std::string* failed) {
+    uint8_t header[MacCheckpoints::HEADER_BYTES];
+    MacCheckpoints::put_header(header, k, n_records);
+    k_ = k; total_ = n_records;
+    for (size_t i = 0; i < n_inst; ++i) {
+      const std::string q = path(dir, first_index + i);
+      FILE* f = std::fopen(q.c_str(), new_pass ? "wb" : "ab");
+      if (!f) { *failed = q; return false; }
+      files_.push_back(f); paths_.push_back(q);
+      if (new_pass && std::fwrite(header, 1, sizeof header, f) != sizeof header) { *failed = q; return false; }
+    }
+    return true;
+  }
+  bool on() const { return !files_.empty(); }
+  // records a chain at stream position `pos` may advance before its state has to be kept: up to the next multiple of 2^k, at least 1
+  uint64_t run(uint64_t pos, uint64_t most) const { return std::min<uint64_t>(most, (1ull << k_) - (pos & ((1ull << k_) - 1))); }
+  // is the state of a chain that has absorbed `pos` records a checkpoint?  (a multiple of 2^k, or the end of the stream)
+  bool due(uint64_t pos) const { return pos && ((pos & ((1ull << k_) - 1)) == 0 || pos == total_); }
+  bool append(size_t i, const CbcMacHost& mac) {
+    uint8_t st[16];
+    mac.digest(st);
+    return std::fwrite(st, 1, 16, files_[i]) == 16;
+  }
+  bool flush() { bool ok = true; for (FILE* f : files_) ok = std::fflush(f) == 0 && ok; return ok; }
+  void keep() { keep_ = true; }
+ private:
+  std::vector<FILE*> files_;
+  std::vector<std::string> paths_;
+  bool keep_ = false;
+  uint32_t k_ = 0;
+  uint64_t total_ = 0;
+};
+
 // What went wrong on the host side of a drain.  The pools of one pass share one slot, the first error stays: a worker that sees one
 // set stops copying and hashing.
 enum class DrainError { None, Copy, FileWrite, Sink, B3Order, OutboardSink };
@@ -232,8 +288,9 @@ struct DrainShape {
 class DrainWorkers {
  public:
   // `d` (n_workers > 0: its workers, chunk buffers and copy streams), `macs` and `files` must outlive this object
-  DrainWorkers(gsv_drain* d, const DrainShape& shape, const DrainSink& sink, std::vector<CbcMacHost>& macs, const GcFiles& files, std::atomic<DrainError>& err)
-      : d_(d), c_(shape), sink_(sink), macs_(macs), files_(files), err_(err), depth_(std::max<size_t>(1, shape.gate_bufs.size())), n_groups_((shape.n_inst + shape.group - 1) / shape.group) {
+  // `checkpoints` (optional; needs sink.hashes): the MAC states after every 2^k records go there as the workers pass through them
+  DrainWorkers(gsv_drain* d, const DrainShape& shape, const DrainSink& sink, std::vector<CbcMacHost>& macs, const GcFiles& files, std::atomic<DrainError>& err, CheckpointWriter* checkpoints = nullptr)
+      : d_(d), c_(shape), sink_(sink), macs_(macs), files_(files), err_(err), ckw_(checkpoints && checkpoints->on() ? checkpoints : nullptr), depth_(std::max<size_t>(1, shape.gate_bufs.size())), n_groups_((shape.n_inst + shape.group - 1) / shape.group) {
     for (size_t t = 0; t < c_.n_workers; ++t) threads_.emplace_back([this, t] { work(t); });
   }
   ~DrainWorkers() { finish(); }
@@ -304,7 +361,20 @@ class DrainWorkers {
             CbcMacHost* mp[gsv_drain::GROUP_MAX];
             const uint8_t* cp[gsv_drain::GROUP_MAX];
             for (size_t g = 0; g < ng; ++g) { mp[g] = &macs_[i0 + g]; cp[g] = w.pinned[b][g].get(); }
-            CbcMacHost::update_many(mp, cp, ng, m);  // sixteen / four chains per step, a ragged last group chain by chain
+            if (!ckw_) CbcMacHost::update_many(mp, cp, ng, m);  // sixteen / four chains per step, a ragged last group chain by chain
+            else {
+              // checkpoints: the call is split at the multiples of 2^k of the stream position base + off — all chains of the group are
+              // at the same position, so the split is common to them — and the states behind each split are kept
+              for (uint64_t q = 0; q < m;) {
+                const uint64_t step = ckw_->run(base + off + q, m - q);
+                const uint8_t* cq[gsv_drain::GROUP_MAX];
+                for (size_t g = 0; g < ng; ++g) cq[g] = cp[g] + q * 16;
+                CbcMacHost::update_many(mp, cq, ng, step);
+                q += step;
+                if (ckw_->due(base + off + q))
+                  for (size_t g = 0; g < ng; ++g) if (!ckw_->append(i0 + g, macs_[i0 + g])) { drain_set_error(err_, DrainError::FileWrite); break; }
+              }
+            }
           }
           if (sink_.dir)
             for (size_t g = 0; g < ng; ++g)
@@ -326,6 +396,7 @@ class DrainWorkers {
   std::vector<CbcMacHost>& macs_;
   const GcFiles& files_;
   std::atomic<DrainError>& err_;
+  CheckpointWriter* const ckw_;
   const size_t depth_, n_groups_;
   size_t n_pushed_ = 0;                   // (the pushing thread's alone)
   std::mutex mu_;

@@ -30,6 +30,7 @@
 #include "host_crypto.hpp"
 #include "kernel_api.h"
 #include "knobs.hpp"
+#include "mac_checkpoints.hpp"
 #include "plan_builder.hpp"
 #include "schedule.hpp"
 #include "program.hpp"
@@ -194,11 +195,13 @@ struct gsv_engine {
   Stream stream;
   DevBuf te;  // device T-tables
   double b3_streams_seconds = 0;  // last gsv_engine_blake3_streams: HIP-event time from the first hash kernel to the last (upload in front and the host's finish behind are outside)
+  double mac_check_seconds = 0;   // last gsv_engine_cbcmac_streams_check: HIP-event time from the first check kernel to the last failing-group word (the upload in front is outside)
   ~gsv_engine() { (void)hipSetDevice(device); }  // ... then te, then the stream
 };
 
 struct PairState;
 struct B3Stream;
+struct MacCheckStream;
 struct EvalCarry;
 struct gsv_session {
   gsv_engine* e = nullptr;
@@ -258,8 +261,10 @@ struct gsv_session {
   bool ran = false, last_eval = false, garbled = false;
   std::vector<uint64_t> ct_uploaded;  // per instance: records supplied by gsv_session_upload_ciphertexts
   std::unique_ptr<gsv_drain> drain;    // streaming drain: copy streams, pinned buffers, per-instance MAC states (created on first use)
-  uint8_t pass_commit = 0;             // commitments of the pass in progress (1 CBC-MAC, 2 BLAKE3): a pass with BLAKE3 carries the same ones in every slice
+  uint8_t pass_commit = 0;             // commitments of the pass in progress (1 CBC-MAC, 2 BLAKE3, 4 outboards, 8 the CBC-MAC check on the device, 16 checkpoint files): a pass with BLAKE3 carries the same ones in every slice
   std::unique_ptr<B3Stream> b3;        // BLAKE3 commitments of the drained streams: device buffers and per-instance hashers, beside drain->macs (engine_blake3.ipp)
+  std::unique_ptr<MacCheckStream> mac_check;  // the CBC-MAC check of a garbling pass against checkpoint files (engine_cbcmac.ipp): device buffers, carries, position — beside `b3`, chained from slice to slice
+  uint32_t mck_k = 0;                  // log2 of the group size of the checkpoint files the pass in progress writes (GSV_MAC_GROUP_LOG2 when its first slice began)
   std::unique_ptr<B3Stream> b3_eval;   // ... of the streams a streaming evaluation reads (gsv_session_evaluate_streaming*_commit): apart from `b3`, which a garbling pass chains from slice to slice
   std::unique_ptr<EvalCarry> evs;      // a streaming evaluation in slices: next call, MAC states, outboards, restart points (engine_blake3.ipp; created on first use)
   // verified streaming evaluation (gsv_session_evaluate_streaming_verified): where the last such pass found a stream that differs from its outboard

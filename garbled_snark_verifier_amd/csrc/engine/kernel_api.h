@@ -118,4 +118,10 @@ int gsvk_b3_chunks_indexed(const void* block, uint64_t block_stride, const void*
                            uint64_t chunk0, uint32_t n_chunks, void* cv, uint64_t cv_stride, uint32_t cv_off, uint32_t n_instances, hipStream_t s);
 // the first (n_have >> k) << k values of cv[inst] become n_have >> k group values in red[inst] (dense), the rest moves to the front of cv_next[inst]
 int gsvk_b3_reduce(void* cv, uint64_t cv_stride, uint32_t n_have, uint32_t k, void* red, void* cv_next, uint32_t n_instances, hipStream_t s);
+// CBC-MAC chains checked against checkpoints (cbcmac_device.hpp).  Records [first, first + n) of every instance's stream of `total` records
+// lie in seg[inst] (stride in records); slice[inst] (stride in 16-byte states, at least chains + 1) holds the claimed states
+// (first >> k) - 1 .. (first + n - 1) >> k; te: the device T-tables; carry_in / carry_out: 16 bytes per instance, never the same buffer;
+// bad[inst]: a 64-bit word the kernel lowers to the lowest group that does not hold
+int gsvk_cbcmac_check(const void* te, const void* seg, uint64_t seg_stride, uint64_t first, uint64_t n, uint32_t k, uint64_t total, const void* slice, uint64_t slice_stride,
+                      const void* carry_in, void* carry_out, void* bad, uint32_t n_instances, hipStream_t s);
 }

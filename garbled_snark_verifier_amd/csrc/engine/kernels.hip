@@ -879,6 +879,7 @@ __global__ void probe_set_kernel(uint32_t* word) { __hip_atomic_store(word, 1u, 
 }  // namespace gsv
 
 #include "blake3_device.hpp"  // BLAKE3 tree hash of the gate-order ciphertext streams: kernels and their launchers
+#include "cbcmac_device.hpp"  // CBC-MAC commitments of the same streams verified against chain checkpoints: kernel and launcher
 
 extern "C" {
 

@@ -52,6 +52,9 @@
 // GSV_PAIR_CU_MASK            flag     1                    pass                                   CU-masked streams for garble || evaluate pairs
 // GSV_B3_SUBTREE_LOG2         0..20    10                   pass, gsv_engine_blake3_streams,       BLAKE3 commitments: log2 of the chunks the device reduces to one value (anything else: the call is refused)
 //                                                             gsv_session_ciphertext_blake3
+// GSV_MAC_GROUP_LOG2          0..30    8                    every entry point that writes          CBC-MAC checkpoints: log2 of the records between two chain states, where the caller passes
+//                                                             checkpoint files                       GSV_MAC_GROUP_DEFAULT (a reader takes k from the file).  Measured (tools/mac_check_rate.py):
+//                                                                                                    the largest k of 8 .. 16 whose check rate over 1 GiB segments of 256 streams is within 10 % of the best
 // -- a knobs::ResidentB3 at gsv_session_ciphertext_blake3 (with GSV_B3_SUBTREE_LOG2)
 // GSV_B3_RESIDENT_RECORDS     int      by free memory       gsv_session_ciphertext_blake3          most records per instance one launch range of the resident hash covers
 //                                                                                                    (default: the two chunk-value buffers take <= 1/10 of the free memory, <= 64 M records)
@@ -93,6 +96,10 @@ inline uint32_t b3_subtree_log2() {
   const char* e = getenv("GSV_B3_SUBTREE_LOG2"); char* end = nullptr; const long long v = e ? std::strtoll(e, &end, 10) : 10;
   return e && (end == e || *end != 0 || v < 0 || v > 20) ? ~0u : uint32_t(v);  // ~0u = set to something else: the entry point that needs it refuses (like window_div)
 }
+inline uint32_t mac_group_log2() {
+  const char* e = getenv("GSV_MAC_GROUP_LOG2"); char* end = nullptr; const long long v = e ? std::strtoll(e, &end, 10) : 8;
+  return e && (end == e || *end != 0 || v < 0 || v > 30) ? ~0u : uint32_t(v);  // ~0u = set to something else: the entry point that needs it refuses
+}
 struct PlanBuild {
   CompileOptions opt = compile_options(Scope::Plan);
   size_t compile_threads = knobs::compile_threads();
@@ -118,6 +125,7 @@ struct Pass {
   uint64_t drain_chunk_mb = uint64_t(std::max(1ll, int_or("GSV_DRAIN_CHUNK_MB", 16)));
   size_t drain_depth = size_t(at_least_1("GSV_DRAIN_DEPTH"));  // 0 = by free memory
   uint32_t b3_subtree_log2 = knobs::b3_subtree_log2();
+  uint32_t mac_group_log2 = knobs::mac_group_log2();
 };
 struct ResidentB3 {
   uint32_t b3_subtree_log2 = knobs::b3_subtree_log2();

@@ -126,17 +126,26 @@ def _check_commitment(commitment):
         raise ValueError("commitment must be 'cbcmac' or 'blake3'")
 
 
-def garble_and_commit(circuit, seeds, indexes, engine=None, program=None, replays=1, gc_dir=None, session_kw=None, threads=0, commitment="cbcmac", outboard_dir=None):
+def garble_and_commit(circuit, seeds, indexes, engine=None, program=None, replays=1, gc_dir=None, session_kw=None, threads=0, commitment="cbcmac", outboard_dir=None, checkpoint_dir=None,
+                      check_dir=None):
     """Garbler::create + commit (garbler.rs:191-257) for the given (index, seed) pairs in ONE session: returns the
     [len(seeds), record_len] commit records; with gc_dir the ciphertext streams go to gc_<index>.bin
     (ciphertext_repository.rs:94-127).  Indexes must be consecutive when gc_dir is used.  `program` may be a Plan (the
     verifier): the stream is then drained window by window of the session's schedule.  commitment="blake3": the record's 16-byte
     ciphertext hash is the truncated BLAKE3 digest of the stream, computed on the device (Blake3Hasher truncates the same way);
-    outboard_dir then receives the streams' BLAKE3 outboards gc_<index>.b3o (consecutive indexes, as for gc_dir)."""
+    outboard_dir then receives the streams' BLAKE3 outboards gc_<index>.b3o (consecutive indexes, as for gc_dir).
+    checkpoint_dir (commitment="cbcmac"): the streams' CBC-MAC checkpoint files gc_<index>.mck are written there (consecutive indexes).
+    check_dir (commitment="cbcmac", no gc_dir): the streams are not drained but verified on the device against the checkpoint files
+    gc_<index>.mck of that directory (Session.garble_check; any indexes); a stream that differs raises CiphertextMismatch with the
+    position in `seeds` as its instance."""
     from . import Engine, Plan, Program, Session, labels_from_seed
     _check_commitment(commitment)
     if outboard_dir is not None and commitment != "blake3":
         raise ValueError("outboard_dir needs commitment='blake3'")
+    if (checkpoint_dir is not None or check_dir is not None) and commitment != "cbcmac":
+        raise ValueError("checkpoint_dir / check_dir need commitment='cbcmac'")
+    if check_dir is not None and (gc_dir is not None or checkpoint_dir is not None):
+        raise ValueError("check_dir verifies the streams where they are garbled: nothing is written")
     engine = engine or Engine(0)
     program = program or Program.from_circuit(circuit, chain_feedback=replays > 1)
     n_in = program.info["n_inputs"]
@@ -149,10 +158,19 @@ def garble_and_commit(circuit, seeds, indexes, engine=None, program=None, replay
     else:
         sess = Session(engine, program, B, replays, min(replays, 2) if replays > 1 else 1)
     sess.set_garble_inputs(delta, consts, inputs)
-    if gc_dir is not None or outboard_dir is not None:
+    if gc_dir is not None or outboard_dir is not None or checkpoint_dir is not None:
         assert list(indexes) == list(range(indexes[0], indexes[0] + B)), "gc files are numbered first_index + i"
     kw = {"outboard_dir": outboard_dir} if outboard_dir is not None else {}
-    hashes = sess.garble_streaming(directory=gc_dir, first_index=int(indexes[0]) if B else 0, threads=threads, commitment=commitment, **kw)  # threads: host MAC workers (0 = the engine's default)
+    if checkpoint_dir is not None:
+        kw["checkpoint_dir"] = checkpoint_dir
+    if check_dir is not None:
+        try:
+            hashes = sess.garble_check(check_dir, indexes=[int(i) for i in indexes])
+        except Exception:
+            sess.close()
+            raise
+    else:
+        hashes = sess.garble_streaming(directory=gc_dir, first_index=int(indexes[0]) if B else 0, threads=threads, commitment=commitment, **kw)  # threads: host MAC workers (0 = the engine's default)
     if commitment == "blake3":
         hashes = [d[:16] for d in hashes]
     outs = sess.read_outputs()
@@ -255,7 +273,35 @@ def _device_file_hashes(engine, paths, outboards):
     return out
 
 
-def run_regarbling(commits, to_finalize, seeds, circuit, gc_dir, engine=None, program=None, replays=1, commitment="cbcmac", outboard_dir=None):
+def _mac_file_hashes(engine, paths, checkpoints):
+    """The finalized instances' files against their CBC-MAC checkpoint files: {position: 16-byte hash | "message"}.  With an engine on
+    the device (cbcmac_files) — a file that differs is named and the rest is checked again without it, and files the device call cannot
+    take together (another length or k than the others, a checkpoint file that is none) go through the host checker one by one."""
+    from . import CiphertextMismatch, GsvError, cbcmac_file_check, cbcmac_files
+
+    def host(j):
+        try:
+            h, group = cbcmac_file_check(paths[j], checkpoints[j])
+            return h if group is None else "ciphertext corrupted (group %d)" % group
+        except Exception as e:  # noqa: BLE001
+            return "failed to get ciphertext source: %s" % e
+    out, todo = {}, list(range(len(paths))) if engine is not None else []
+    while todo:
+        try:
+            got = cbcmac_files(engine, [paths[j] for j in todo], [checkpoints[j] for j in todo])
+            out.update(dict(zip(todo, got)))
+            break
+        except CiphertextMismatch as e:
+            out[todo.pop(e.instance)] = "ciphertext corrupted (group %d)" % e.group
+        except GsvError:
+            break
+    for j in range(len(paths)):
+        if j not in out:
+            out[j] = host(j)
+    return out
+
+
+def run_regarbling(commits, to_finalize, seeds, circuit, gc_dir, engine=None, program=None, replays=1, commitment="cbcmac", outboard_dir=None, checkpoint_dir=None):
     """Evaluator::run_regarbling (cut_and_choose/evaluator.rs:83-181).  `commits`: [total, record_len] table of the
     garbler's commit records; `to_finalize`: indexes kept for evaluation; `seeds`: {index: seed} of the OPENED instances.
       * finalized index: its gc_<index>.bin is streamed through the CBC-MAC and compared with the committed ciphertext
@@ -266,12 +312,23 @@ def run_regarbling(commits, to_finalize, seeds, circuit, gc_dir, engine=None, pr
     commits the same way.  With an `engine` the finalized instances' files are hashed on the device instead (blake3_files: read in
     bounded segments, never evaluated); outboard_dir (the outboards gc_<index>.b3o the garbler sent) makes either path compare every
     group of 2^k chunks with the file's outboard, and a file that differs is reported as "ciphertext corrupted (group g)" — the part
-    to fetch again.  Returns (ok, errors) with errors = {index: message}; the reference returns Err(()) as soon as any instance fails."""
+    to fetch again.
+    checkpoint_dir (commitment="cbcmac"): the garbler's CBC-MAC checkpoint files gc_<index>.mck lie there.  A finalized file that has
+    one is verified group by group against it — on the device with an `engine` (cbcmac_files), else by the host checker
+    (cbcmac_file_check) — its last state is what is compared with the committed hash, and a file that differs is reported as
+    "ciphertext corrupted (group g)".  Opened instances that have one are re-garbled and verified on the device without their
+    ciphertexts leaving it (Session.garble_check); the record compare is unchanged.  Instances without a checkpoint file take the
+    paths above.  Returns (ok, errors) with errors = {index: message}; the reference returns Err(()) as soon as any instance fails."""
     import os
-    from . import blake3_file, gc_file_name, outboard_file_name, read_gc_file
+    from . import CiphertextMismatch, blake3_file, checkpoint_file_name, gc_file_name, outboard_file_name, read_gc_file
     _check_commitment(commitment)
     if outboard_dir is not None and commitment != "blake3":
         raise ValueError("outboard_dir needs commitment='blake3'")
+    if checkpoint_dir is not None and commitment != "cbcmac":
+        raise ValueError("checkpoint_dir needs commitment='cbcmac'")
+
+    def has_checkpoints(i):
+        return checkpoint_dir is not None and os.path.exists(os.path.join(checkpoint_dir, checkpoint_file_name(i)))
     commits = np.asarray(commits, np.uint8)
     errors = {}
     fin = set(int(i) for i in to_finalize)
@@ -280,6 +337,10 @@ def run_regarbling(commits, to_finalize, seeds, circuit, gc_dir, engine=None, pr
         there = [i for i in sorted(fin) if os.path.exists(os.path.join(gc_dir, gc_file_name(i))) and (outboard_dir is None or os.path.exists(os.path.join(outboard_dir, outboard_file_name(i))))]
         got = _device_file_hashes(engine, [os.path.join(gc_dir, gc_file_name(i)) for i in there],
                                   None if outboard_dir is None else [os.path.join(outboard_dir, outboard_file_name(i)) for i in there])
+        device = {i: got[j] for j, i in enumerate(there)}
+    if checkpoint_dir is not None:
+        there = [i for i in sorted(fin) if os.path.exists(os.path.join(gc_dir, gc_file_name(i))) and has_checkpoints(i)]
+        got = _mac_file_hashes(engine, [os.path.join(gc_dir, gc_file_name(i)) for i in there], [os.path.join(checkpoint_dir, checkpoint_file_name(i)) for i in there])
         device = {i: got[j] for j, i in enumerate(there)}
     for index in sorted(fin):
         path = os.path.join(gc_dir, gc_file_name(index))
@@ -302,12 +363,25 @@ def run_regarbling(commits, to_finalize, seeds, circuit, gc_dir, engine=None, pr
     missing = [i for i in opened if i not in seeds]
     for i in missing:
         errors[i] = "failed to find seed"
-    todo = [i for i in opened if i in seeds]
+    todo = [i for i in opened if i in seeds and not has_checkpoints(i)]
     if todo:
         recs = garble_and_commit(circuit, [seeds[i] for i in todo], todo, engine=engine, program=program, replays=replays, commitment=commitment)
         for k, i in enumerate(todo):
             if not (recs[k] == commits[i]).all():
                 errors[i] = "regarbling failed"
+    # ... and the opened instances whose checkpoint files are there: verified where they are garbled.  A stream that differs from its
+    # checkpoints cannot give the committed hash; it is named, and the others are garbled again without it.
+    todo = [i for i in opened if i in seeds and has_checkpoints(i)]
+    while todo:
+        try:
+            recs = garble_and_commit(circuit, [seeds[i] for i in todo], todo, engine=engine, program=program, replays=replays, check_dir=checkpoint_dir)
+        except CiphertextMismatch as e:
+            errors[todo.pop(e.instance)] = "regarbling failed"
+            continue
+        for k, i in enumerate(todo):
+            if not (recs[k] == commits[i]).all():
+                errors[i] = "regarbling failed"
+        break
     return (not errors), errors
 
 

@@ -38,7 +38,7 @@ typedef enum gsv_status {
   GSV_ERR_CIRCUIT = 2,   /* what the reference would panic! on (missing wire, arity mismatch, ...) */
   GSV_ERR_DEVICE = 3,    /* HIP failure or no gfx950 device: the engine has NO CPU fallback */
   GSV_ERR_EXHAUSTED = 4, /* ciphertext source exhausted (evaluate_mode.rs:141) */
-  GSV_ERR_MISMATCH = 5   /* a received ciphertext stream does not match its BLAKE3 outboard / commitment ("BLAKE3 outboards" below) */
+  GSV_ERR_MISMATCH = 5   /* a ciphertext stream does not match its BLAKE3 outboard / commitment ("BLAKE3 outboards" below) or its CBC-MAC checkpoints ("CBC-MAC checkpoints") */
 } gsv_status;
 
 /* Gate record = reference `Gate` (src/core/gate.rs:7-12) with u64 wire ids; `gate_type` is the
@@ -580,6 +580,75 @@ int gsv_session_mismatch_info(const gsv_session* s, uint64_t* instance, uint64_t
 /* Plan sessions: windows of the schedule launched by the session's last pass (a verified pass that ended early launched fewer than
  * gsv_plan_schedule_info.n_windows). */
 int gsv_session_windows_launched(const gsv_session* s, uint64_t* n);
+
+/* ---- CBC-MAC checkpoints ---------------------------------------------------------------------------------------------------------
+ * The reference's ciphertext commitment (AESAccumulatingHash: h <- AES_K(h ^ ct), h = 0 in front of the stream) is one serial chain
+ * and cannot be COMPUTED in parallel.  It can be VERIFIED in parallel when the garbler also publishes the chain state after every
+ * 2^k records: the checkpoint file gc_<i>.mck beside gc_<i>.bin, for a stream of L records
+ *
+ *     bytes  0 ..  7   magic: the eight bytes "GSVMACK\n" (47 53 56 4d 41 43 4b 0a)
+ *     bytes  8 .. 11   format version, 1, little-endian
+ *     bytes 12 .. 15   k (0 .. 30), little-endian
+ *     bytes 16 .. 23   n_records = L, little-endian
+ *     then             ceil(L / 2^k) states, 16 bytes each: state g is the chain state after records [0, min((g + 1) 2^k, L))
+ *
+ * and nothing else: 24 + 16 ceil(L / 2^k) bytes, 2^-k of the stream.  The last state is the commitment; the empty stream has no states
+ * and its commitment is sixteen zero bytes.  Group g is checked on its own: start from the claimed state g - 1 (zero for g = 0), run
+ * the group's records, compare with the claimed state g.  If every group holds, the stream's true CBC-MAC is the last state, by
+ * induction over the groups — the check is deterministic, and a checkpoint file is UNTRUSTED input: a wrong or hostile one can only
+ * make the check fail.  A bad stream is named by (instance, group): that part of the file can be fetched again.
+ * Every reader takes k from the file.  Refused with GSV_ERR_INVALID and a message that names what is wrong, before anything is sized by
+ * a header field: a wrong magic or version, k above 30, a byte length other than the one k and n_records make, a file written for
+ * another n_records than the stream it is checked against, and files of one call that disagree on k or n_records.  The files are
+ * never held whole: header and length are validated up front, the states are read segment by segment.
+ *
+ * A writer takes k as an argument; GSV_MAC_GROUP_DEFAULT stands for the knob GSV_MAC_GROUP_LOG2 (default 8).
+ * gsv_cbcmac_checkpoints_size: the byte length of the checkpoint file of a stream of n_records records.
+ * gsv_cbcmac_file_checkpoints: the host writer for a file that already exists (whole 16-byte records): writes its checkpoints to
+ * out_path (NULL: nowhere) and returns the file's CBC-MAC.
+ * gsv_cbcmac_file_check: the host checker — groups in parallel over n_threads threads (0: up to 16), each advancing up to sixteen
+ * independent groups side by side.  GSV_OK: the file's CBC-MAC is `hash`, the file's last state.  GSV_ERR_MISMATCH: *bad_group is the
+ * lowest group that does not hold.  The fallback where there is no engine, and the reference the device paths are tested against. */
+#define GSV_MAC_GROUP_DEFAULT 0xffffffffu
+int gsv_cbcmac_checkpoints_size(uint64_t n_records, uint32_t k, uint64_t* bytes);
+int gsv_cbcmac_file_checkpoints(const char* path, uint32_t k, const char* out_path /* or NULL */, uint8_t* hash /* 16 */);
+int gsv_cbcmac_file_check(const char* path, const char* checkpoints_path, int n_threads, uint8_t* hash /* 16 */, uint64_t* bad_group /* or NULL */);
+/* The check kernel alone: n_streams streams of records_per_stream records each (data: [stream][record]) are uploaded and checked, in
+ * the given segmentation (segment_records adds up to records_per_stream), against n_streams checkpoint files given in memory
+ * (checkpoints: [stream][checkpoint_bytes]).  One chain per lane; a group that a segment boundary cuts is carried to the next segment.
+ * GSV_ERR_MISMATCH: *bad_stream / *bad_group name the lowest group that does not hold and, in that group, the lowest stream. */
+int gsv_engine_cbcmac_streams_check(gsv_engine* e, const uint8_t* data, uint64_t n_streams, uint64_t records_per_stream, const uint64_t* segment_records, uint64_t n_segments,
+                                    const uint8_t* checkpoints, uint64_t checkpoint_bytes, uint64_t* bad_stream /* or NULL */, uint64_t* bad_group /* or NULL */);
+/* Device time of the engine's last gsv_engine_cbcmac_streams_check, from the first check kernel to the last failing-group word on the
+ * host (HIP events on the engine's stream: the upload of the streams in front is outside, the uploads of the states are inside). */
+int gsv_engine_cbcmac_streams_check_seconds(const gsv_engine* e, double* seconds);
+/* Received files verified on the device, without evaluating them: gsv_engine_blake3_files with the CBC-MAC check in the place of the
+ * hash.  n_files files of the same length are read in bounded segments (GSV_DRAIN_SEGMENT_RECORDS records per file) and checked
+ * against checkpoint_paths[i].  With `expected` (n_files x 16) every file's last state is compared with the commitment the caller
+ * trusts before anything is uploaded: a difference is GSV_ERR_MISMATCH with *bad_group_out = UINT64_MAX.  A group that does not hold is
+ * GSV_ERR_MISMATCH, *bad_file_out = the index into `paths`, *bad_group_out = the group — the lowest group first, then the lowest file.
+ * hashes (n_files x 16: the files' CBC-MACs) is written only when everything held. */
+int gsv_engine_cbcmac_files(gsv_engine* e, const char* const* paths, uint64_t n_files, const char* const* checkpoint_paths, const uint8_t* expected /* n_files x 16 or NULL */,
+                            uint8_t* hashes /* n_files x 16 */, uint64_t* bad_file_out /* or NULL */, uint64_t* bad_group_out /* or NULL */);
+/* gsv_session_garble_streaming_calls that also writes <checkpoint_dir>/gc_<first_index + i>.mck for the drained instances, k =
+ * GSV_MAC_GROUP_LOG2 when the pass began: the chain states the MAC workers pass through anyway, so the files cost the garbler nothing.
+ * `hashes` is required; checkpoint_dir == NULL is gsv_session_garble_streaming_calls.  Program sessions: first_call = n_calls = 0.  A
+ * slice that starts at call 0 truncates the files and writes their headers, later slices append; a failed call removes them as it
+ * removes its gc files.  Every slice of the pass must ask for checkpoints (GSV_ERR_INVALID otherwise).  Sessions over a ciphertext
+ * ring (retain_stream = GSV_STREAM_RING) are refused with GSV_ERR_INVALID. */
+int gsv_session_garble_streaming_checkpoints(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* dir /* or NULL */, uint64_t first_index, int n_threads,
+                                             uint8_t* hashes, const char* checkpoint_dir);
+/* Garbles and verifies the streams against <checkpoint_dir>/gc_<index>.mck (index = indexes ? indexes[i] : first_index + i) where they
+ * are produced: every finished segment is checked in its gate-order buffer, nothing is drained and no MAC worker starts — the
+ * re-garbling check of an opened instance without its ciphertexts crossing the link.  With `expected` (n_instances x 16) every file's
+ * last state is compared before anything is launched (GSV_ERR_MISMATCH, no place: gsv_session_mismatch_info gives UINT64_MAX).  A group
+ * that does not hold ends the pass with GSV_ERR_MISMATCH; gsv_session_mismatch_info names the instance, the group and its first
+ * record.  `hashes` (n_instances x 16 or NULL) receives the verified commitments from the call that ends the pass.  Program and plan
+ * sessions (program sessions: first_call = n_calls = 0); plan sessions in slices, whose check chains from slice to slice and restarts
+ * with a slice that starts at call 0 — every slice of a pass must ask for the same check (GSV_ERR_INVALID otherwise).  Sessions over
+ * a ciphertext ring are refused with GSV_ERR_INVALID. */
+int gsv_session_garble_streaming_check(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* checkpoint_dir, const uint64_t* indexes /* or NULL */,
+                                       uint64_t first_index, const uint8_t* expected /* or NULL */, uint8_t* hashes /* or NULL */);
 
 /* ---- Commitments on the callback paths -------------------------------------------------------------------------------------------
  * The commitments, outboards and verified evaluation above for hosts that plug in through gsv_ct_sink_fn / gsv_ct_source_fn instead
