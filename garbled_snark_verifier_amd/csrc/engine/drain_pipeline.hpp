@@ -1,6 +1,7 @@
-// The host side of the streaming drain (engine_drain.ipp): the session's copy streams, pinned chunk buffers and MAC states; where a
-// drained stream goes; the gc_<i>.bin files of a pass and its outboards (gc_<i>.b3o files, or a host callback); the pool of MAC / copy workers behind a queue of
-// segments; the BLAKE3 absorbers; the CBC-MAC checkpoint files (gc_<i>.mck: the chain states the MAC workers pass through anyway, kept).
+// The host side of the streaming drain (engine_drain.ipp): the session's copy streams, pinned chunk buffers and MAC states; where a drained stream goes, what that
+// makes a pass carry (PassCommit) and which combinations are refused (DrainSink::refusal, commit_slice_conflict: the policy, as plain values); the gc_<i>.bin files of
+// a pass and its outboards (gc_<i>.b3o files, or a host callback); the pool of MAC / copy workers behind a queue of segments; the BLAKE3 absorbers; the CBC-MAC
+// checkpoint files (gc_<i>.mck: the chain states the MAC workers pass through anyway, kept).
 // Each pool owns its threads and joins them in its destructor.  Nothing here knows sessions, schedules, plans or knobs — plain values
 // in — and nothing but the HIP runtime API, hip_owned.hpp, host_crypto.hpp and the standard library is needed: this header compiles
 // alone (tests/drain_pipeline runs it against stand-ins for the HIP calls, also under the thread and address sanitizers).
@@ -72,6 +73,19 @@ struct gsv_drain {
   std::vector<CbcMacHost> macs;
 };
 
+// What a garbling pass carries from slice to slice, as a set: gsv_session::pass_commit holds the first slice's.  (An outboard, to files
+// or to a callback, is part of what a BLAKE3 pass carries.)
+enum class PassCommit : uint8_t { None = 0, Mac = 1, B3 = 2, Outboard = 4, MacCheck = 8, Checkpoints = 16 };
+constexpr PassCommit operator|(PassCommit a, PassCommit b) { return PassCommit(uint8_t(a) | uint8_t(b)); }
+constexpr bool has(PassCommit set, PassCommit any_of) { return (uint8_t(set) & uint8_t(any_of)) != 0; }
+// A pass that commits with BLAKE3 carries the same commitments in every slice: a slice without MAC workers leaves the MAC states
+// behind, one without the hash kernels the BLAKE3 state (likewise the checkpoint files and the check).  Null: `now` may follow `first`.
+inline const char* commit_slice_conflict(PassCommit first, PassCommit now) {
+  if (first == now) return nullptr;
+  if (has(first | now, PassCommit::B3)) return "every slice of a pass with a BLAKE3 commitment must ask for the same commitments as its first slice";
+  if (has(first | now, PassCommit::MacCheck | PassCommit::Checkpoints)) return "every slice of a pass that writes or checks CBC-MAC checkpoints must ask for the same as its first slice";
+  return nullptr;
+}
 // Where a drained stream goes (any combination): the per-instance CBC-MAC (AESAccumulatingHash), gc_<index>.bin files, a host callback,
 // the per-instance BLAKE3 tree hash on the device (engine_blake3.ipp) — the one destination for which no ciphertext leaves the device.
 using DrainSinkFn = int (*)(void* user, size_t instance, uint64_t first_record, const uint8_t* records, uint64_t n_records);  // (gsv_ct_sink_fn of include/gsv_engine.h)
@@ -97,35 +111,60 @@ struct DrainSink {
   bool outboard() const { return outboard_dir || ob_fn; }
   bool host() const { return hashes || dir || fn; }  // the stream is copied to the host
   bool any() const { return host() || b3 || mac_check_dir; }
+  PassCommit commit() const {
+    const auto on = [](bool q, PassCommit c) { return q ? c : PassCommit::None; };
+    return on(hashes, PassCommit::Mac) | on(b3, PassCommit::B3) | on(outboard(), PassCommit::Outboard) | on(mac_check_dir, PassCommit::MacCheck) | on(checkpoint_dir, PassCommit::Checkpoints);
+  }
+  // The first rule this combination breaks, or null.  b3_refusal: the two an entry point can tell from its own arguments.
+  const char* b3_refusal() const {
+    if (outboard() && !b3) return "an outboard holds the values of the BLAKE3 commitment: blake3_digests must be given";
+    if (last_chunks && !b3) return "the last chunks come with the BLAKE3 commitment: blake3_digests must be given";
+    return nullptr;
+  }
+  // ring: the session's device block is a ciphertext ring; paired: an evaluator session consumes the windows (garble || evaluate)
+  const char* refusal(bool ring, bool paired) const {
+    if (const char* why = b3_refusal()) return why;
+    if (checkpoint_dir && !hashes) return "checkpoint files hold the states of the CBC-MAC: hashes must be given";  // (no entry point of the C ABI gets here: the one that takes a checkpoint directory answers "null hash buffer" first)
+    if ((mac_check_dir || checkpoint_dir) && ring) return "CBC-MAC checkpoints are not written or checked over a ciphertext ring (retain_stream = GSV_STREAM_RING): create the session with launch windows";
+    if (mac_check_dir && (host() || b3 || paired)) return "internal: the CBC-MAC check runs alone";
+    return nullptr;
+  }
 };
 
-// The gc_<first_index + i>.bin files of one call.  Closed when the object goes away and REMOVED unless keep() was called: a failed pass
-// must not leave a plausible-looking prefix of a ciphertext file behind, whichever way it returns.
-class GcFiles {
+// The files one call writes, one per instance.  Closed when the object goes away and REMOVED unless keep() was called: a failed pass
+// must not leave a plausible-looking prefix of a ciphertext file (or of its outboard, or of its checkpoints) behind, whichever way it returns.
+class KeptFiles {
  public:
-  GcFiles() = default;
-  GcFiles(const GcFiles&) = delete;
-  GcFiles& operator=(const GcFiles&) = delete;
-  ~GcFiles() {
+  KeptFiles() = default;
+  KeptFiles(const KeptFiles&) = delete;
+  KeptFiles& operator=(const KeptFiles&) = delete;
+  ~KeptFiles() {
     for (FILE* f : files_) std::fclose(f);
     if (!keep_) for (const std::string& q : paths_) std::remove(q.c_str());
   }
+  bool flush() { bool ok = true; for (FILE* f : files_) ok = std::fflush(f) == 0 && ok; return ok; }
+  void keep() { keep_ = true; }
+ protected:
+  bool add(const std::string& path, const char* mode, const uint8_t* header, size_t header_bytes, std::string* failed) {
+    FILE* f = std::fopen(path.c_str(), mode);
+    if (f) { files_.push_back(f); paths_.push_back(path); }
+    if (f && (!header || std::fwrite(header, 1, header_bytes, f) == header_bytes)) return true;
+    *failed = path;  // the path that could not be created, or its header not written
+    return false;
+  }
+  std::vector<FILE*> files_;
+ private:
+  std::vector<std::string> paths_;
+  bool keep_ = false;
+};
+class GcFiles : public KeptFiles {  // the gc_<first_index + i>.bin files of one call
+ public:
   // mode "wb" (a new pass) or "ab" (a later slice).  False: `*failed` is the path that could not be created.
   bool open(const char* dir, uint64_t first_index, size_t n_inst, const char* mode, std::string* failed) {
-    for (size_t i = 0; i < n_inst; ++i) {
-      const std::string path = std::string(dir) + "/gc_" + std::to_string(first_index + i) + ".bin";
-      FILE* f = std::fopen(path.c_str(), mode);
-      if (!f) { *failed = path; return false; }
-      files_.push_back(f); paths_.push_back(path);
-    }
+    for (size_t i = 0; i < n_inst; ++i) if (!add(std::string(dir) + "/gc_" + std::to_string(first_index + i) + ".bin", mode, nullptr, 0, failed)) return false;
     return true;
   }
   FILE* operator[](size_t i) const { return files_[i]; }
-  void keep() { keep_ = true; }
- private:
-  std::vector<FILE*> files_;
-  std::vector<std::string> paths_;
-  bool keep_ = false;
 };
 
 // The outboards of one call (outboard.hpp): a header, then the 32-byte values in the order the host absorbs them.  One writer, two
@@ -134,28 +173,15 @@ class GcFiles {
 // same bytes handed to the host as they are produced, per instance at increasing byte offsets — the header at offset 0 by the slice
 // that starts a pass, a later slice goes on behind the values the earlier ones delivered; once a call has returned non-zero no
 // further call is started.  Instances may be written from different threads, one instance from one thread at a time.
-class OutboardWriter {
+class OutboardWriter : public KeptFiles {
  public:
-  OutboardWriter() = default;
-  OutboardWriter(const OutboardWriter&) = delete;
-  OutboardWriter& operator=(const OutboardWriter&) = delete;
-  ~OutboardWriter() {
-    for (FILE* f : files_) std::fclose(f);
-    if (!keep_) for (const std::string& q : paths_) std::remove(q.c_str());
-  }
   static std::string path(const char* dir, uint64_t index) { return std::string(dir) + "/gc_" + std::to_string(index) + ".b3o"; }
   // new_pass: truncate and write the header for a stream of n_records records in groups of 2^k chunks; else append.  False: `*failed`.
   bool open(const char* dir, uint64_t first_index, size_t n_inst, bool new_pass, uint32_t k, uint64_t n_records, std::string* failed) {
     uint8_t header[Outboard::HEADER_BYTES];
     Outboard::put_header(header, k, n_records);
     n_ = n_inst;
-    for (size_t i = 0; i < n_inst; ++i) {
-      const std::string q = path(dir, first_index + i);
-      FILE* f = std::fopen(q.c_str(), new_pass ? "wb" : "ab");
-      if (!f) { *failed = q; return false; }
-      files_.push_back(f); paths_.push_back(q);
-      if (new_pass && std::fwrite(header, 1, sizeof header, f) != sizeof header) { *failed = q; return false; }
-    }
+    for (size_t i = 0; i < n_inst; ++i) if (!add(path(dir, first_index + i), new_pass ? "wb" : "ab", new_pass ? header : nullptr, sizeof header, failed)) return false;
     return true;
   }
   // The callback back end.  new_pass: every instance receives the header at offset 0, here, on the calling thread; else the slice goes
@@ -182,8 +208,6 @@ class OutboardWriter {
     }
     return ok;
   }
-  bool flush() { bool ok = true; for (FILE* f : files_) ok = std::fflush(f) == 0 && ok; return ok; }
-  void keep() { keep_ = true; }
  private:
   bool deliver(size_t i, const uint8_t* bytes, uint64_t n) {
     if (refused_.load()) return false;
@@ -191,9 +215,6 @@ class OutboardWriter {
     offset_[i] += n;
     return true;
   }
-  std::vector<FILE*> files_;
-  std::vector<std::string> paths_;
-  bool keep_ = false;
   OutboardSinkFn fn_ = nullptr;
   void* user_ = nullptr;
   std::vector<uint64_t> offset_;     // callback: the next byte of every instance's outboard
@@ -206,28 +227,15 @@ using OutboardFiles = OutboardWriter;  // (the name from before the callback bac
 // 2^k records and at the end of the stream, in stream order.  A new pass writes the header, a later slice appends; closed when the
 // object goes away and REMOVED unless keep() was called, like the gc files beside them.  The MAC workers write them: instances may be
 // written from different threads, one instance from one thread at a time.
-class CheckpointWriter {
+class CheckpointWriter : public KeptFiles {
  public:
-  CheckpointWriter() = default;
-  CheckpointWriter(const CheckpointWriter&) = delete;
-  CheckpointWriter& operator=(const CheckpointWriter&) = delete;
-  ~CheckpointWriter() {
-    for (FILE* f : files_) std::fclose(f);
-    if (!keep_) for (const std::string& q : paths_) std::remove(q.c_str());
-  }
   static std::string path(const char* dir, uint64_t index) { return std::string(dir) + "/gc_" + std::to_string(index) + ".mck"; }
   // new_pass: truncate and write the header for a stream of n_records records in groups of 2^k records; else append.  False: `*failed`.
   bool open(const char* dir, uint64_t first_index, size_t n_inst, bool new_pass, uint32_t k, uint64_t n_records, std::string* failed) {
     uint8_t header[MacCheckpoints::HEADER_BYTES];
     MacCheckpoints::put_header(header, k, n_records);
     k_ = k; total_ = n_records;
-    for (size_t i = 0; i < n_inst; ++i) {
-      const std::string q = path(dir, first_index + i);
-      FILE* f = std::fopen(q.c_str(), new_pass ? "wb" : "ab");
-      if (!f) { *failed = q; return false; }
-      files_.push_back(f); paths_.push_back(q);
-      if (new_pass && std::fwrite(header, 1, sizeof header, f) != sizeof header) { *failed = q; return false; }
-    }
+    for (size_t i = 0; i < n_inst; ++i) if (!add(path(dir, first_index + i), new_pass ? "wb" : "ab", new_pass ? header : nullptr, sizeof header, failed)) return false;
     return true;
   }
   bool on() const { return !files_.empty(); }
@@ -240,12 +248,7 @@ class CheckpointWriter {
     mac.digest(st);
     return std::fwrite(st, 1, 16, files_[i]) == 16;
   }
-  bool flush() { bool ok = true; for (FILE* f : files_) ok = std::fflush(f) == 0 && ok; return ok; }
-  void keep() { keep_ = true; }
  private:
-  std::vector<FILE*> files_;
-  std::vector<std::string> paths_;
-  bool keep_ = false;
   uint32_t k_ = 0;
   uint64_t total_ = 0;
 };

@@ -203,9 +203,13 @@ struct EvalRestart {
   std::vector<CbcMacHost> macs;
   uint64_t check_position = 0, windows_launched = 0;
 };
+// What a streaming evaluation asks for, as a set: every slice of a pass asks for the same.  At most one of the three kinds of
+// verification: outboards from files; outboards in memory, authenticated up front with the last chunks; or at the end of the pass.
+enum class EvalCommit : uint8_t { None = 0, Mac = 1, B3 = 2, VerifiedFiles = 4, VerifiedUpFront = 8, VerifiedDeferred = 16 };
+constexpr EvalCommit operator|(EvalCommit a, EvalCommit b) { return EvalCommit(uint8_t(a) | uint8_t(b)); }
 struct EvalCarry {
   uint64_t next_call = 0;            // the call the next slice must start with (garbling has a counter of its own: gsv_session::next_call)
-  uint8_t commit = 0;                // what the pass in progress asked for: 1 CBC-MAC, 2 BLAKE3, 4 verified (outboards from files), 8 verified (in memory, up front), 16 (deferred)
+  EvalCommit commit = EvalCommit::None;  // what the pass in progress asked for
   std::vector<CbcMacHost> macs;      // the per-instance MAC states after the last slice
   B3Check check;                     // verified passes: the parsed outboards (the slice at call 0 loaded them) and the comparison's position
   EvalRestart rp[2];                 // [0]: where the last restartable slice began, [1]: the restartable slice before it
@@ -307,100 +311,128 @@ int gsv_blake3_file_outboard(const char* path, uint32_t k, const char* outboard_
   }
   return GSV_OK;
 }
-// Received files hashed where the kernels are: n equally long files are read in segments through two page-locked staging buffers
-// (CtUploader without MAC workers: the read of a piece overlaps the upload of the one before), uploaded to a gate-order buffer of one
-// segment and fed to b3_begin / b3_segment / b3_finish as n streams — the whole input is never resident.  With outboards every value
-// the host receives is compared before it is absorbed; the values of a segment are looked at when the next segment has been enqueued.
+// ---- n equally long streams brought to the device: received files, and streams in memory (here and in engine_cbcmac.ipp) ----
+// Received files where the kernels are: n equally long files are read in segments through two page-locked staging buffers (CtUploader
+// without MAC workers: the read of a piece overlaps the upload of the one before) and uploaded to a gate-order buffer of one segment,
+// which is handed to `feed` as n streams — the whole input is never resident.
+static void report_bad(uint64_t* stream_out, uint64_t* group_out, uint64_t stream, uint64_t group) { if (stream_out) *stream_out = stream; if (group_out) *group_out = group; }  // where a mismatch sits
+using SegmentFeed = std::function<int(const void* buf, uint64_t stride, uint64_t n_records, hipStream_t st)>;  // buf[stream * stride + r], r < n_records
+struct FilesOnDevice {
+  GcFileSource files; const char* const* paths = nullptr; size_t n = 0;
+  uint64_t total = 0, seg = 0;  // records per file; per file and segment
+  // records(i, file, why) -> the record count of paths[i], or false with the caller's own message; `also` (optional): a second list
+  // of paths that must not hold a null either.  seg_knob: GSV_DRAIN_SEGMENT_RECORDS, else 16 MiB per file within 256 MiB for all of them.
+  int open(const char* const* paths_, const char* const* also, size_t n_files, uint64_t seg_knob, const std::function<bool(size_t, FILE*, uint64_t*, std::string*)>& records) {
+    paths = paths_; n = n_files;
+    std::string why;
+    for (size_t i = 0; i < n; ++i) {
+      if (!paths[i] || (also && !also[i])) return fail(GSV_ERR_INVALID, "null path");
+      if (!files.add(paths[i], &why)) return fail(GSV_ERR_INVALID, why);
+      uint64_t r = 0;
+      if (!records(i, files.file(i), &r, &why)) return fail(GSV_ERR_INVALID, why);
+      if (i == 0) total = r;
+      else if (r != total) return fail(GSV_ERR_INVALID, "the files must be equally long: " + std::string(paths[0]) + " holds " + std::to_string(total) + " records, " + paths[i] + " " + std::to_string(r));
+    }
+    seg = std::max<uint64_t>(1, std::min<uint64_t>(total, seg_knob ? seg_knob : std::max<uint64_t>(4096, std::min<uint64_t>(1ull << 20, (1ull << 24) / n))));
+    return GSV_OK;
+  }
+  // begin() -> status, once the device is selected and the buffers stand; then feed -> status per segment.  Whatever the outcome, the
+  // stream is synchronised before the buffers are released: the caller finishes behind it.
+  int run(gsv_engine* e, const char* what, const std::function<int()>& begin, const SegmentFeed& feed) {
+    HIPCHK(hipSetDevice(e->device));
+    const hipStream_t st = e->stream.get();
+    DevBuf gate;
+    DEVALLOC(gate, n * size_t(seg) * 16, what);
+    CtUploader up(n, seg, std::min<uint64_t>(seg, CT_STAGE_RECORDS), 0, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t m) { return files.read(i, first, dst, m); });
+    if (up.alloc() != hipSuccess) return fail(GSV_ERR_DEVICE, "cannot allocate the staging buffers");
+    int rc = begin();
+    for (uint64_t off = 0; off < total && rc == GSV_OK; off += seg) {
+      const uint64_t m = std::min(seg, total - off);
+      switch (up.upload(off, m, gate.get(), st)) {
+        case UploadError::None: break;
+        case UploadError::Dry: rc = fail(GSV_ERR_INVALID, std::string("read error on ") + paths[up.dry_instance()]); break;
+        default: rc = fail(GSV_ERR_DEVICE, "upload of a file segment failed");
+      }
+      if (rc == GSV_OK) rc = feed(gate.get(), seg, m, st);  // (a receiver looks at what the segment before left behind)
+    }
+    (void)hipStreamSynchronize(st);  // (nothing of `gate` or the staging buffers is in flight when they are released)
+    return rc;
+  }
+};
+// The kernels alone: n_streams streams of records_per_stream records each (data: [stream][record]) are uploaded and fed in the given
+// segmentation, between two timing events on the engine's stream; what the time covers is the caller's business (stop()).
+struct StreamsOnDevice {
+  DevBuf d; Event t0, t1; hipStream_t st = nullptr;
+  static int segments(const uint64_t* segment_records, uint64_t n_segments, uint64_t records_per_stream, uint64_t* seg_cap) {  // the largest one; they must add up
+    uint64_t sum = 0;
+    for (uint64_t i = 0; i < n_segments; ++i) { sum += segment_records[i]; *seg_cap = std::max(*seg_cap, segment_records[i]); }
+    return sum == records_per_stream ? GSV_OK : fail(GSV_ERR_INVALID, "the segments do not add up to records_per_stream");
+  }
+  static int count(uint64_t n_streams, uint64_t records_per_stream, const char* who) {
+    if (n_streams == 0 || n_streams > 65535) return fail(GSV_ERR_INVALID, std::string(who) + " take 1 .. 65535 streams at a time");
+    return records_per_stream > (~0ull >> 4) / n_streams ? fail(GSV_ERR_INVALID, "n_streams x records_per_stream x 16 bytes does not fit 64 bits") : GSV_OK;
+  }
+  // upload, begin(stream) -> status, t0, then feed -> status per segment (a receiver that could not begin is fed nothing)
+  int run(gsv_engine* e, const uint8_t* data, uint64_t n_streams, uint64_t records_per_stream, const uint64_t* segment_records, uint64_t n_segments, const char* what, const std::function<int(hipStream_t)>& begin, const SegmentFeed& feed) {
+    HIPCHK(hipSetDevice(e->device));
+    DEVALLOC(d, size_t(n_streams) * size_t(records_per_stream) * 16, what);
+    st = e->stream.get();
+    if (records_per_stream) HIPCHK(hipMemcpyAsync(d.get(), data, size_t(n_streams) * size_t(records_per_stream) * 16, hipMemcpyHostToDevice, st));
+    int rc = begin(st);
+    HIPCHK(t0.create()); HIPCHK(t1.create());
+    HIPCHK(hipEventRecord(t0.get(), st));
+    for (uint64_t i = 0, off = 0; i < n_segments && rc == GSV_OK; off += segment_records[i++]) rc = feed(d.as<uint8_t>() + off * 16, records_per_stream, segment_records[i], st);
+    return rc;
+  }
+  hipError_t stop(double* seconds) {  // t1 behind whatever the stream holds: the seconds since t0
+    float ms = 0;
+    hipError_t q = hipEventRecord(t1.get(), st);
+    if (q == hipSuccess && (q = hipEventSynchronize(t1.get())) == hipSuccess && (q = hipEventElapsedTime(&ms, t0.get(), t1.get())) == hipSuccess) *seconds = double(ms) * 1e-3;
+    return q;
+  }
+  ~StreamsOnDevice() { if (st) (void)hipStreamSynchronize(st); }  // (nothing of d is in flight when it is released: declare the receiver first)
+};
+// Received files hashed: fed to b3_begin / b3_segment / b3_finish as n streams.  With outboards every value the host receives is
+// compared before it is absorbed; the values of a segment are looked at when the next segment has been enqueued.
 int gsv_engine_blake3_files(gsv_engine* e, const char* const* paths, uint64_t n_files, const char* const* outboard_paths, uint8_t* digests, uint64_t* bad_file_out, uint64_t* bad_group_out) {
   if (!e || !paths || !digests) return fail(GSV_ERR_INVALID, "null argument");
   const uint32_t k = knobs::b3_subtree_log2();
   const uint64_t seg_knob = knobs::at_least_1("GSV_DRAIN_SEGMENT_RECORDS");
   if (int krc = check_b3_k(k)) return krc;
   if (n_files == 0 || n_files > 65535) return fail(GSV_ERR_INVALID, "BLAKE3 commitments take 1 .. 65535 streams at a time");
-  const size_t n = size_t(n_files);
-  GcFileSource files;
-  uint64_t total = 0;
-  std::string why;
-  for (size_t i = 0; i < n; ++i) {
-    if (!paths[i] || (outboard_paths && !outboard_paths[i])) return fail(GSV_ERR_INVALID, "null path");
-    if (!files.add(paths[i], &why)) return fail(GSV_ERR_INVALID, why);
-    struct stat sb;
-    if (fstat(fileno(files.file(i)), &sb) != 0) return fail(GSV_ERR_INVALID, std::string("cannot open ") + paths[i]);
-    if (sb.st_size < 0 || (uint64_t(sb.st_size) & 15) || uint64_t(sb.st_size) / 16 > Outboard::MAX_RECORDS) return fail(GSV_ERR_INVALID, std::string(paths[i]) + " does not hold whole 16-byte records");
-    if (i == 0) total = uint64_t(sb.st_size) / 16;
-    else if (uint64_t(sb.st_size) / 16 != total)
-      return fail(GSV_ERR_INVALID, "the files must be equally long: " + std::string(paths[0]) + " holds " + std::to_string(total) + " records, " + paths[i] + " " + std::to_string(uint64_t(sb.st_size) / 16));
-  }
+  FilesOnDevice f;
+  if (int rc = f.open(paths, outboard_paths, size_t(n_files), seg_knob, [&](size_t i, FILE* file, uint64_t* records, std::string* why) { return mac_file_records(fileno(file), paths[i], records, why, Outboard::MAX_RECORDS); })) return rc;
   B3Check check;
+  std::string why;
   if (outboard_paths) {
-    check.shape(n, k, total);
-    for (size_t i = 0; i < n; ++i) if (!load_outboard(outboard_paths[i], k, total, &check.bytes[i], &why)) return fail(GSV_ERR_INVALID, why);
+    check.shape(f.n, k, f.total);
+    for (size_t i = 0; i < f.n; ++i) if (!load_outboard(outboard_paths[i], k, f.total, &check.bytes[i], &why)) return fail(GSV_ERR_INVALID, why);
   }
-  // records per file and segment: the knob, or 16 MiB per file within 256 MiB for all of them
-  const uint64_t seg = std::max<uint64_t>(1, std::min<uint64_t>(total, seg_knob ? seg_knob : std::max<uint64_t>(4096, std::min<uint64_t>(1ull << 20, (1ull << 24) / n))));
-  HIPCHK(hipSetDevice(e->device));
-  const hipStream_t st = e->stream.get();
-  DevBuf gate;
-  DEVALLOC(gate, n * size_t(seg) * 16, "the segment of the files to hash");
-  CtUploader up(n, seg, std::min<uint64_t>(seg, CT_STAGE_RECORDS), 0, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t m) { return files.read(i, first, dst, m); });
-  if (up.alloc() != hipSuccess) return fail(GSV_ERR_DEVICE, "cannot allocate the staging buffers");
   std::unique_ptr<B3Stream> b;
   B3Receiver rx(b, "file", outboard_paths ? &check : nullptr);
-  int rc = rx.begin(n, total, seg, k);
-  if (rc) return rc;
-  for (uint64_t off = 0; off < total && rc == GSV_OK; off += seg) {
-    const uint64_t m = std::min(seg, total - off);
-    switch (up.upload(off, m, gate.get(), st)) {
-      case UploadError::None: break;
-      case UploadError::Dry: rc = fail(GSV_ERR_INVALID, std::string("read error on ") + paths[up.dry_instance()]); break;
-      default: rc = fail(GSV_ERR_DEVICE, "upload of a file segment failed");
-    }
-    if (rc == GSV_OK) rc = rx.feed(gate.get(), seg, m, st);  // (the values of the segment before are looked at first)
-  }
-  if (rc == GSV_OK) rc = rx.finish(st, digests);
-  (void)hipStreamSynchronize(st);  // (nothing of `gate` or the staging buffers is in flight when they are released)
-  if (rc == GSV_ERR_MISMATCH) {
-    if (bad_file_out) *bad_file_out = check.bad_instance;
-    if (bad_group_out) *bad_group_out = check.bad_group;
-  }
+  int rc = f.run(e, "the segment of the files to hash", [&] { return rx.begin(f.n, f.total, f.seg, k); }, [&](const void* gate, uint64_t stride, uint64_t m, hipStream_t st) { return rx.feed(gate, stride, m, st); });
+  if (rc == GSV_OK) rc = rx.finish(e->stream.get(), digests);
+  if (rc == GSV_ERR_MISMATCH) report_bad(bad_file_out, bad_group_out, check.bad_instance, check.bad_group);
   return rc;
 }
-// The kernels alone: n_streams streams of records_per_stream records each (data: [stream][record]) are uploaded and fed to the chunk,
-// reduce and carry code of the drain in the given segmentation; the host finishes them.
+// The kernels alone: the streams are fed to the chunk, reduce and carry code of the drain; the host finishes them.
 int gsv_engine_blake3_streams(gsv_engine* e, const uint8_t* data, uint64_t n_streams, uint64_t records_per_stream, const uint64_t* segment_records, uint64_t n_segments, uint8_t* digests) {
   if (!e || !digests || (!data && records_per_stream) || (!segment_records && n_segments)) return fail(GSV_ERR_INVALID, "null argument");
   const uint32_t k = knobs::b3_subtree_log2();
-  uint64_t sum = 0, seg_cap = 0;
-  for (uint64_t i = 0; i < n_segments; ++i) { sum += segment_records[i]; seg_cap = std::max(seg_cap, segment_records[i]); }
-  if (sum != records_per_stream) return fail(GSV_ERR_INVALID, "the segments do not add up to records_per_stream");
+  uint64_t seg_cap = 0;
+  if (int rc = StreamsOnDevice::segments(segment_records, n_segments, records_per_stream, &seg_cap)) return rc;
   if (int krc = check_b3_k(k)) return krc;
-  if (n_streams == 0 || n_streams > 65535) return fail(GSV_ERR_INVALID, "BLAKE3 commitments take 1 .. 65535 streams at a time");
-  if (records_per_stream > (~0ull >> 4) / n_streams) return fail(GSV_ERR_INVALID, "n_streams x records_per_stream x 16 bytes does not fit 64 bits");
-  HIPCHK(hipSetDevice(e->device));
-  DevBuf d;
-  DEVALLOC(d, size_t(n_streams) * size_t(records_per_stream) * 16, "the streams to hash");
-  if (records_per_stream) HIPCHK(hipMemcpyAsync(d.get(), data, size_t(n_streams) * size_t(records_per_stream) * 16, hipMemcpyHostToDevice, e->stream.get()));
+  if (int rc = StreamsOnDevice::count(n_streams, records_per_stream, "BLAKE3 commitments")) return rc;
   std::unique_ptr<B3Stream> b;
   B3Receiver rx(b);
-  int rc = rx.begin(size_t(n_streams), records_per_stream, seg_cap, k);
-  Event t0, t1;
-  HIPCHK(t0.create()); HIPCHK(t1.create());
-  HIPCHK(hipEventRecord(t0.get(), e->stream.get()));
-  uint64_t off = 0;
-  for (uint64_t i = 0; i < n_segments && rc == GSV_OK; ++i) {  // (a segment's group values are absorbed before the next one is enqueued)
-    rc = rx.feed(d.as<uint8_t>() + off * 16, records_per_stream, segment_records[i], e->stream.get());
-    off += segment_records[i];
-  }
+  StreamsOnDevice up;  // (a segment's group values are absorbed before the next one is enqueued)
+  int rc = up.run(e, data, n_streams, records_per_stream, segment_records, n_segments, "the streams to hash", [&](hipStream_t) { return rx.begin(size_t(n_streams), records_per_stream, seg_cap, k); },
+                  [&](const void* buf, uint64_t stride, uint64_t m, hipStream_t st) { return rx.feed(buf, stride, m, st); });
   if (rc == GSV_OK) rc = rx.flush();  // (in front of t1: the time covers the host's folding between the segments)
   if (rc == GSV_OK) {
-    float ms = 0;
-    HIPCHK(hipEventRecord(t1.get(), e->stream.get()));
-    HIPCHK(hipEventSynchronize(t1.get()));
-    HIPCHK(hipEventElapsedTime(&ms, t0.get(), t1.get()));
-    e->b3_streams_seconds = double(ms) * 1e-3;
+    HIPCHK(up.stop(&e->b3_streams_seconds));
     rc = rx.finish(e->stream.get(), digests);
   }
-  (void)hipStreamSynchronize(e->stream.get());  // (nothing of d is in flight when it is released)
   return rc;
 }
 int gsv_engine_blake3_streams_seconds(const gsv_engine* e, double* seconds) {

@@ -153,11 +153,9 @@ int gsv_cbcmac_file_check(const char* path, const char* checkpoints_path, int n_
 int gsv_engine_cbcmac_streams_check(gsv_engine* e, const uint8_t* data, uint64_t n_streams, uint64_t records_per_stream, const uint64_t* segment_records, uint64_t n_segments,
                                     const uint8_t* checkpoints, uint64_t checkpoint_bytes, uint64_t* bad_stream, uint64_t* bad_group) {
   if (!e || !checkpoints || (!data && records_per_stream) || (!segment_records && n_segments)) return fail(GSV_ERR_INVALID, "null argument");
-  uint64_t sum = 0, seg_cap = 0;
-  for (uint64_t i = 0; i < n_segments; ++i) { sum += segment_records[i]; seg_cap = std::max(seg_cap, segment_records[i]); }
-  if (sum != records_per_stream) return fail(GSV_ERR_INVALID, "the segments do not add up to records_per_stream");
-  if (n_streams == 0 || n_streams > 65535) return fail(GSV_ERR_INVALID, "CBC-MAC checks take 1 .. 65535 streams at a time");
-  if (records_per_stream > (~0ull >> 4) / n_streams) return fail(GSV_ERR_INVALID, "n_streams x records_per_stream x 16 bytes does not fit 64 bits");
+  uint64_t seg_cap = 0;
+  if (int rc = StreamsOnDevice::segments(segment_records, n_segments, records_per_stream, &seg_cap)) return rc;
+  if (int rc = StreamsOnDevice::count(n_streams, records_per_stream, "CBC-MAC checks")) return rc;
   MacCheckpoints head;
   std::string why;
   for (uint64_t i = 0; i < n_streams; ++i) {
@@ -168,11 +166,6 @@ int gsv_engine_cbcmac_streams_check(gsv_engine* e, const uint8_t* data, uint64_t
     if (!h.length_ok(checkpoint_bytes, &why)) return fail(GSV_ERR_INVALID, "checkpoints of stream " + std::to_string(i) + ": " + why);
     head = h;
   }
-  HIPCHK(hipSetDevice(e->device));
-  const hipStream_t st = e->stream.get();
-  DevBuf d;
-  DEVALLOC(d, size_t(n_streams) * size_t(records_per_stream) * 16, "the streams to check");
-  if (records_per_stream) HIPCHK(hipMemcpyAsync(d.get(), data, size_t(n_streams) * size_t(records_per_stream) * 16, hipMemcpyHostToDevice, st));
   const uint64_t n_states = head.states();
   std::unique_ptr<MacCheckStream> slot;
   MacCheckReceiver rx(slot, "stream", e->te.get(), [&](size_t i, int64_t s0, uint64_t count, uint8_t* dst) {
@@ -181,28 +174,12 @@ int gsv_engine_cbcmac_streams_check(gsv_engine* e, const uint8_t* data, uint64_t
     std::memcpy(dst, checkpoints + i * checkpoint_bytes + MacCheckpoints::HEADER_BYTES + uint64_t(s0) * 16, size_t(count) * 16);
     return true;
   });
-  int rc = rx.begin(size_t(n_streams), records_per_stream, seg_cap, head.k, st);
-  if (rc) return rc;
-  Event t0, t1;
-  HIPCHK(t0.create()); HIPCHK(t1.create());
-  HIPCHK(hipEventRecord(t0.get(), st));
-  uint64_t off = 0;
-  for (uint64_t i = 0; i < n_segments && rc == GSV_OK; ++i) {
-    rc = rx.feed(d.as<uint8_t>() + off * 16, records_per_stream, segment_records[i], st);
-    off += segment_records[i];
-  }
+  StreamsOnDevice up;
+  int rc = up.run(e, data, n_streams, records_per_stream, segment_records, n_segments, "the streams to check", [&](hipStream_t st) { return rx.begin(size_t(n_streams), records_per_stream, seg_cap, head.k, st); },
+                  [&](const void* buf, uint64_t stride, uint64_t m, hipStream_t st) { return rx.feed(buf, stride, m, st); });
   if (rc == GSV_OK) rc = rx.finish();
-  if (rc == GSV_OK || rc == GSV_ERR_MISMATCH) {
-    const std::string msg = g_err;
-    float ms = 0;
-    if (hipEventRecord(t1.get(), st) == hipSuccess && hipEventSynchronize(t1.get()) == hipSuccess && hipEventElapsedTime(&ms, t0.get(), t1.get()) == hipSuccess) e->mac_check_seconds = double(ms) * 1e-3;
-    g_err = msg;
-  }
-  (void)hipStreamSynchronize(st);  // (nothing of d or the receiver's buffers is in flight when they are released)
-  if (rc == GSV_ERR_MISMATCH) {
-    if (bad_stream) *bad_stream = rx.bad_instance;
-    if (bad_group) *bad_group = rx.bad_group;
-  }
+  if (rc == GSV_OK || rc == GSV_ERR_MISMATCH) (void)up.stop(&e->mac_check_seconds);  // (behind finish(), and on a mismatch too: the time runs to the last failing-group word)
+  if (rc == GSV_ERR_MISMATCH) report_bad(bad_stream, bad_group, rx.bad_instance, rx.bad_group);
   return rc;
 }
 int gsv_engine_cbcmac_streams_check_seconds(const gsv_engine* e, double* seconds) {
@@ -211,64 +188,33 @@ int gsv_engine_cbcmac_streams_check_seconds(const gsv_engine* e, double* seconds
   return GSV_OK;
 }
 // Received files verified where the kernels are, without evaluating them: gsv_engine_blake3_files with the CBC-MAC check in the place of
-// the hash (GcFileSource + CtUploader without MAC workers + the receiver).  The checkpoint files are never held whole.
+// the hash (FilesOnDevice + the receiver).  The checkpoint files are never held whole.
 int gsv_engine_cbcmac_files(gsv_engine* e, const char* const* paths, uint64_t n_files, const char* const* checkpoint_paths, const uint8_t* expected, uint8_t* hashes,
                             uint64_t* bad_file_out, uint64_t* bad_group_out) {
   if (!e || !paths || !checkpoint_paths || !hashes) return fail(GSV_ERR_INVALID, "null argument");
   const uint64_t seg_knob = knobs::at_least_1("GSV_DRAIN_SEGMENT_RECORDS");
   if (n_files == 0 || n_files > 65535) return fail(GSV_ERR_INVALID, "CBC-MAC checks take 1 .. 65535 streams at a time");
-  const size_t n = size_t(n_files);
-  GcFileSource files;
-  uint64_t total = 0;
+  FilesOnDevice f;
+  if (int rc = f.open(paths, checkpoint_paths, size_t(n_files), seg_knob, [&](size_t i, FILE* file, uint64_t* records, std::string* why) { return mac_file_records(fileno(file), paths[i], records, why); })) return rc;
+  const size_t n = f.n;
   std::string why;
-  for (size_t i = 0; i < n; ++i) {
-    if (!paths[i] || !checkpoint_paths[i]) return fail(GSV_ERR_INVALID, "null path");
-    if (!files.add(paths[i], &why)) return fail(GSV_ERR_INVALID, why);
-    uint64_t records = 0;
-    if (!mac_file_records(fileno(files.file(i)), paths[i], &records, &why)) return fail(GSV_ERR_INVALID, why);
-    if (i == 0) total = records;
-    else if (records != total)
-      return fail(GSV_ERR_INVALID, "the files must be equally long: " + std::string(paths[0]) + " holds " + std::to_string(total) + " records, " + paths[i] + " " + std::to_string(records));
-  }
   std::vector<MacCheckpointFile> cks;
-  if (!open_mac_checkpoints(checkpoint_paths, n, &total, &cks, &why)) return fail(GSV_ERR_INVALID, why);
-  const uint32_t k = cks[0].head.k;
+  if (!open_mac_checkpoints(checkpoint_paths, n, &f.total, &cks, &why)) return fail(GSV_ERR_INVALID, why);
   // the commitments the files claim: compared with the ones the caller trusts before anything is uploaded
   std::vector<uint8_t> claimed(n * 16);
   for (size_t i = 0; i < n; ++i) {
     if (!cks[i].commitment(claimed.data() + 16 * i)) return fail(GSV_ERR_INVALID, "read error on " + cks[i].path());
     if (expected && std::memcmp(claimed.data() + 16 * i, expected + 16 * i, 16) != 0) {
-      if (bad_file_out) *bad_file_out = i;
-      if (bad_group_out) *bad_group_out = ~0ull;
+      report_bad(bad_file_out, bad_group_out, i, ~0ull);
       return fail(GSV_ERR_MISMATCH, "the last checkpoint of file " + std::to_string(i) + " does not match the commitment");
     }
   }
-  if (total == 0) { std::memcpy(hashes, claimed.data(), claimed.size()); return GSV_OK; }
-  const uint64_t seg = std::max<uint64_t>(1, std::min<uint64_t>(total, seg_knob ? seg_knob : std::max<uint64_t>(4096, std::min<uint64_t>(1ull << 20, (1ull << 24) / n))));
-  HIPCHK(hipSetDevice(e->device));
-  const hipStream_t st = e->stream.get();
-  DevBuf gate;
-  DEVALLOC(gate, n * size_t(seg) * 16, "the segment of the files to check");
-  CtUploader up(n, seg, std::min<uint64_t>(seg, CT_STAGE_RECORDS), 0, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t m) { return files.read(i, first, dst, m); });
-  if (up.alloc() != hipSuccess) return fail(GSV_ERR_DEVICE, "cannot allocate the staging buffers");
+  if (f.total == 0) { std::memcpy(hashes, claimed.data(), claimed.size()); return GSV_OK; }
   std::unique_ptr<MacCheckStream> slot;
   MacCheckReceiver rx(slot, "file", e->te.get(), [&](size_t i, int64_t s0, uint64_t count, uint8_t* dst) { return cks[i].read_states(s0, count, dst); });
-  int rc = rx.begin(n, total, seg, k, st);
-  for (uint64_t off = 0; off < total && rc == GSV_OK; off += seg) {
-    const uint64_t m = std::min(seg, total - off);
-    switch (up.upload(off, m, gate.get(), st)) {
-      case UploadError::None: break;
-      case UploadError::Dry: rc = fail(GSV_ERR_INVALID, std::string("read error on ") + paths[up.dry_instance()]); break;
-      default: rc = fail(GSV_ERR_DEVICE, "upload of a file segment failed");
-    }
-    if (rc == GSV_OK) rc = rx.feed(gate.get(), seg, m, st);  // (the words of the segment before are looked at behind it)
-  }
+  int rc = f.run(e, "the segment of the files to check", [&] { return rx.begin(n, f.total, f.seg, cks[0].head.k, e->stream.get()); }, [&](const void* gate, uint64_t stride, uint64_t m, hipStream_t st) { return rx.feed(gate, stride, m, st); });
   if (rc == GSV_OK) rc = rx.finish();
-  (void)hipStreamSynchronize(st);  // (nothing of `gate` or the staging buffers is in flight when they are released)
-  if (rc == GSV_ERR_MISMATCH) {
-    if (bad_file_out) *bad_file_out = rx.bad_instance;
-    if (bad_group_out) *bad_group_out = rx.bad_group;
-  }
+  if (rc == GSV_ERR_MISMATCH) report_bad(bad_file_out, bad_group_out, rx.bad_instance, rx.bad_group);
   if (rc == GSV_OK) std::memcpy(hashes, claimed.data(), claimed.size());
   return rc;
 }

@@ -213,32 +213,21 @@ static std::vector<void*> drain_gate_buffers(gsv_session* s, size_t n_units, siz
   for (const DevBuf& q : s->ct_gate_more) if (gate_bufs.size() < want) gate_bufs.push_back(q.get());
   return gate_bufs;
 }
-static int fail_drain(DrainError e) {
-  switch (e) {
-    case DrainError::FileWrite: return fail(GSV_ERR_INVALID, "short write to a gc or outboard file");
-    case DrainError::Sink: return fail(GSV_ERR_INVALID, "the ciphertext sink reported an error");
-    case DrainError::OutboardSink: return fail(GSV_ERR_INVALID, "the outboard sink reported an error");
-    case DrainError::B3Order: return fail(GSV_ERR_INVALID, "internal: BLAKE3 group values out of order");
-    default: return fail(GSV_ERR_DEVICE, "device copy failed while draining ciphertexts");
-  }
-}
 // What the device loops of one garble_streaming_pass share
 struct DrainPass {
   gsv_session *s, *ev;             // ev: the evaluator of a garble || evaluate pair, or null
   uint64_t gate_id_base;
   size_t pw0, n_inst;              // plans: the first window of this call; instances whose streams leave the device
   uint64_t seg_records;            // records between two instances in a gate-order buffer
-  bool want_drain, want_b3;        // finished segments are brought into gate order; ... and hashed there
+  bool want_drain;                 // finished segments are brought into gate order
   std::vector<void*> gate_bufs;
-  DrainWorkers& workers; B3Absorbers* b3; DrainStats& stats;
-  MacCheckReceiver* mac;           // not null: finished segments are checked against their CBC-MAC checkpoints where they lie
+  DrainWorkers& workers; GarbleCommit& commit; DrainStats& stats;  // commit: what is hashed or checked in the gate-order buffers
   hipStream_t gs;                  // the stream the garbler's windows are launched on
   hipEvent_t device_done;          // not null: the host thread sleeps on this blocking-sync event instead of spinning in hipStreamSynchronize
   std::chrono::steady_clock::time_point t_last_pub;  // ring diagnostics: the last publication of the host's position ...
   double worst_gap;                                  // ... and the longest interval between two
   void* gate() const { return gate_bufs[workers.next_buffer()]; }  // the gate-order buffer the next segment goes to
   bool wait_device(hipStream_t st) const { return device_done ? hipEventRecord(device_done, st) == hipSuccess && hipEventSynchronize(device_done) == hipSuccess : hipStreamSynchronize(st) == hipSuccess; }
-  void b3_submit(uint32_t groups) { if (b3) b3->submit(s->b3->pinned.get(), n_inst * size_t(groups) * 32, groups); }
 };
 // One window of a plan: launched (in a pair: handed to the evaluator as well), then drained segment by segment while it runs.
 static int drain_plan_window(DrainPass& p, size_t w) {
@@ -282,11 +271,9 @@ static int drain_plan_window(DrainPass& p, size_t w) {
     const auto tg = std::chrono::steady_clock::now();
     rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, p.seg_records, 0, block, p.gate(), s->aux_stream.get());
     if (rc != GSV_OK) return rc;
-    uint32_t b3_groups = 0;  // the hash kernels follow the gather on the side stream; the buffer is free again when they have finished
-    if (p.want_b3 && (rc = b3_segment(*s->b3, p.gate(), p.seg_records, sg.n_ct, s->aux_stream.get(), &b3_groups)) != GSV_OK) return rc;
-    if (p.mac && (rc = p.mac->feed(p.gate(), p.seg_records, sg.n_ct, s->aux_stream.get())) != GSV_OK) return rc;  // (the words of the segment before are looked at here)
+    if ((rc = p.commit.feed(p.gate(), p.seg_records, sg.n_ct, s->aux_stream.get())) != GSV_OK) return rc;  // (behind the gather, on the side stream)
     if (hipStreamSynchronize(s->aux_stream.get()) != hipSuccess) return fail(GSV_ERR_DEVICE, "ciphertext gather failed");
-    p.b3_submit(b3_groups);
+    p.commit.submit();
     st.t_gather += drain_secs(tg);
     if (s->ct_ring) {
       __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);  // the calls whose blocks overlap this segment's may write now
@@ -316,16 +303,14 @@ static int drain_program_ring(DrainPass& p, uint64_t r0, uint64_t r1) {
   p.stats.t_wait_drain += p.workers.wait_buffer();
   if (gsvk_gather_segment(s->CT.get(), s->ct_stride(), s->dp->ct_pos.as<const uint32_t>(), n_ct, uint32_t(r1 - r0), uint32_t(p.n_inst), p.gate(), p.seg_records, 0, s->e->stream.get()) != 0)
     return fail(GSV_ERR_DEVICE, "ciphertext gather launch failed");
-  uint32_t b3_groups = 0;
-  if (p.want_b3 && (rc = b3_segment(*s->b3, p.gate(), p.seg_records, n_records, s->e->stream.get(), &b3_groups)) != GSV_OK) return rc;
-  if (p.mac && (rc = p.mac->feed(p.gate(), p.seg_records, n_records, s->e->stream.get())) != GSV_OK) return rc;
+  if ((rc = p.commit.feed(p.gate(), p.seg_records, n_records, s->e->stream.get())) != GSV_OK) return rc;
   // the workers own the cores when there is one chain per core: this thread then sleeps on a blocking-sync event instead of
   // spinning in hipStreamSynchronize
   const auto t0 = std::chrono::steady_clock::now();
   if (!p.wait_device(s->e->stream.get())) return fail(GSV_ERR_DEVICE, "kernel failed");
   p.stats.t_wait_device += drain_secs(t0);
   p.stats.drained_records += n_records;
-  p.b3_submit(b3_groups);
+  p.commit.submit();
   p.workers.push(n_records, base);
   return GSV_OK;
 }
@@ -346,15 +331,8 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   const size_t n_inst = s->drain_instances ? std::min(s->drain_instances, s->n_inst) : s->n_inst;
   const bool want_drain = sink.any();    // finished segments are brought into gate order ...
   const bool want_host = sink.host();    // ... and copied out by the workers
-  const bool want_b3 = sink.b3 != nullptr;
-  const bool want_mac = sink.hashes != nullptr;
-  if (sink.outboard() && !want_b3) return fail(GSV_ERR_INVALID, "an outboard holds the values of the BLAKE3 commitment: blake3_digests must be given");
-  if (sink.last_chunks && !want_b3) return fail(GSV_ERR_INVALID, "the last chunks come with the BLAKE3 commitment: blake3_digests must be given");
-  const bool want_check = sink.mac_check_dir != nullptr, want_ckpt = sink.checkpoint_dir != nullptr;
-  if (want_ckpt && !want_mac) return fail(GSV_ERR_INVALID, "checkpoint files hold the states of the CBC-MAC: hashes must be given");
-  if ((want_check || want_ckpt) && s->ct_ring) return fail(GSV_ERR_INVALID, "CBC-MAC checkpoints are not written or checked over a ciphertext ring (retain_stream = GSV_STREAM_RING): create the session with launch windows");
-  if (want_check && (want_host || want_b3 || ev)) return fail(GSV_ERR_INVALID, "internal: the CBC-MAC check runs alone");
-  if (want_check) s->mismatch = false;
+  if (const char* why = sink.refusal(s->ct_ring, ev != nullptr)) return fail(GSV_ERR_INVALID, why);
+  if (sink.mac_check_dir) clear_mismatch(s);
   if (s->plan && new_pass) s->windows_launched = 0;
   const size_t GROUP = size_t(gsv_drain::group_for(n_inst, s->pass.drain_group));
   const size_t n_groups = (n_inst + GROUP - 1) / GROUP;
@@ -369,23 +347,9 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
     int rc = want_host ? ensure_drain(s, T, seg_records, int(GROUP)) : GSV_OK;
     if (rc) return rc;
   }
-  // A pass that commits with BLAKE3 carries the same commitments in every slice: a slice without MAC workers leaves the MAC states
-  // behind, one without the hash kernels the BLAKE3 state, and the commitment returned at the end would cover part of the stream
-  {
-    const uint8_t commit = uint8_t((want_mac ? 1 : 0) | (want_b3 ? 2 : 0) | (sink.outboard() ? 4 : 0) | (want_check ? 8 : 0) | (want_ckpt ? 16 : 0));  // (an outboard, to files or to a callback, is part of what a BLAKE3 pass carries)
-    if (new_pass || !s->plan) s->pass_commit = commit;
-    else if (commit != s->pass_commit && ((commit | s->pass_commit) & 2)) return fail(GSV_ERR_INVALID, "every slice of a pass with a BLAKE3 commitment must ask for the same commitments as its first slice");
-    else if (commit != s->pass_commit && ((commit | s->pass_commit) & (8 | 16))) return fail(GSV_ERR_INVALID, "every slice of a pass that writes or checks CBC-MAC checkpoints must ask for the same as its first slice");
-  }
-  // CBC-MAC checkpoints: the group size is the one the pass began with
-  if (want_ckpt) {
-    if (new_pass) { if (int rc = check_mac_k(s->pass.mac_group_log2)) return rc; s->mck_k = s->pass.mac_group_log2; }
-  }
-  // BLAKE3: the state lives in the session like the MAC states — a new pass starts it afresh, later slices chain
-  if (want_b3) {
-    if (new_pass) { int rc = b3_begin(s->b3, n_inst, stream_records(s), seg_records, s->pass.b3_subtree_log2); if (rc) return rc; }
-    else if (!s->b3 || s->b3->n_inst != n_inst || s->b3->seg_cap < seg_records) return fail(GSV_ERR_INVALID, "this slice continues a pass whose earlier slices computed no BLAKE3 commitment for these instances");
-  }
+  // Declared before the pools and the gc files: its own threads are joined, and its files removed, after theirs (engine_garble_commit.ipp)
+  GarbleCommit commit(s, sink);
+  if (int rc = commit.begin(new_pass, n_inst, seg_records)) return rc;
   if (ev && (s->ct_ring || ev->ct_ring)) return fail(GSV_ERR_INVALID, "garble || evaluate pairs need sessions with explicit launch windows (window_ct_records, e.g. 1 << 28): the default is one whole-pass window over a ciphertext ring");
   if (ev) { int rc = ensure_pair(s); if (rc) return rc; }
   if (s->ct_ring) __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(s->plan && pw0 < s->sched.windows.size() ? s->sched.windows[pw0].ct0 : 0), __ATOMIC_RELEASE);
@@ -397,37 +361,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   std::vector<CbcMacHost>& macs = want_host ? s->drain->macs : no_macs;
   GcFiles files;  // (removed again on every return but the last)
   if (std::string failed; sink.dir && !files.open(sink.dir, sink.first_index, n_inst, new_pass ? "wb" : "ab", &failed)) return fail(GSV_ERR_INVALID, "cannot create " + failed);
-  CheckpointWriter checkpoints;  // (likewise; written by the MAC workers)
-  if (std::string failed; want_ckpt && !checkpoints.open(sink.checkpoint_dir, sink.first_index, n_inst, new_pass, s->mck_k, stream_records(s), &failed)) return fail(GSV_ERR_INVALID, "cannot create " + failed);
-  // The CBC-MAC check: the checkpoint files are opened and validated by every slice (headers and lengths; they are never held whole);
-  // the receiver's device state lives in the session and restarts with a pass that starts at call 0
-  std::vector<MacCheckpointFile> mcks;
-  std::vector<uint8_t> mac_claimed;
-  const hipStream_t mac_stream = s->plan ? s->aux_stream.get() : s->e->stream.get();  // where the segments are gathered
-  MacCheckReceiver mac_rx(s->mac_check, "the ciphertext stream of instance", s->e->te.get(), [&mcks](size_t i, int64_t s0, uint64_t count, uint8_t* dst) { return mcks[i].read_states(s0, count, dst); });
-  if (want_check) {
-    std::vector<std::string> names(n_inst);
-    std::vector<const char*> ptrs(n_inst);
-    for (size_t i = 0; i < n_inst; ++i) { names[i] = CheckpointWriter::path(sink.mac_check_dir, sink.mac_check_indexes ? sink.mac_check_indexes[i] : sink.first_index + i); ptrs[i] = names[i].c_str(); }
-    const uint64_t records = stream_records(s);
-    std::string why;
-    if (!open_mac_checkpoints(ptrs.data(), n_inst, &records, &mcks, &why)) return fail(GSV_ERR_INVALID, why);
-    mac_claimed.resize(n_inst * 16);
-    for (size_t i = 0; i < n_inst; ++i) {
-      if (!mcks[i].commitment(mac_claimed.data() + 16 * i)) return fail(GSV_ERR_INVALID, "read error on " + mcks[i].path());
-      if (new_pass && sink.mac_check_expected && std::memcmp(mac_claimed.data() + 16 * i, sink.mac_check_expected + 16 * i, 16) != 0) {
-        s->mismatch = true; s->mismatch_instance = i; s->mismatch_group = s->mismatch_record = ~0ull;
-        return fail(GSV_ERR_MISMATCH, "the last checkpoint of instance " + std::to_string(i) + " does not match the commitment");
-      }
-    }
-    const int mrc = new_pass ? mac_rx.begin(n_inst, records, seg_records, mcks[0].head.k, mac_stream) : mac_rx.resume(n_inst, records, seg_records, mcks[0].head.k);
-    if (mrc) return mrc;
-  }
-  OutboardWriter outboards;  // (likewise; written by the absorbers' threads, and by this one when the pass ends)
-  if (std::string failed; sink.outboard_dir && !outboards.open(sink.outboard_dir, sink.first_index, n_inst, new_pass, s->b3->k, s->b3->total, &failed)) return fail(GSV_ERR_INVALID, "cannot create " + failed);
-  // (a later slice goes on behind the group values of the earlier ones: every chunk hashed so far but the pending ones is in a group)
-  if (sink.ob_fn && !sink.outboard_dir && !outboards.open(sink.ob_fn, sink.ob_user, n_inst, new_pass, s->b3->k, s->b3->total, (s->b3->chunks_done - s->b3->pend) >> s->b3->k))
-    return fail_drain(DrainError::OutboardSink);
+  if (int rc = commit.open(s->plan ? s->aux_stream.get() : s->e->stream.get())) return rc;  // (the stream the segments are gathered on)
   DrainShape shape;
   shape.device = s->e->device; shape.n_inst = n_inst; shape.group = GROUP; shape.n_workers = want_host ? T : 0;
   shape.chunk = want_host ? s->drain->chunk : 0; shape.seg_records = seg_records; shape.blocking_wait = T > 8;
@@ -436,16 +370,9 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
     if (s->plan) { n_units = 0; for (size_t w = pw0; w < pw1; ++w) n_units += s->sched.windows[w].seg1 - s->sched.windows[w].seg0; }
     shape.gate_bufs = drain_gate_buffers(s, n_units, n_inst, seg_records, want_host);
   }
-  // The pools are declared after everything their threads use — the gate-order buffers, `macs`, `files`: they are joined first, however
-  // this function returns.  Their threads run members of the pools (drain_pipeline.hpp), never a lambda over the locals here.
-  std::atomic<DrainError> err{DrainError::None};
-  DrainWorkers workers(s->drain.get(), shape, sink, macs, files, err, want_ckpt ? &checkpoints : nullptr);
-  B3Stream* const b3s = want_b3 ? s->b3.get() : nullptr;
-  OutboardWriter* const obf = sink.outboard() ? &outboards : nullptr;
-  B3Absorbers absorbers(want_b3 ? std::min<size_t>(4, n_inst) : 0, [b3s, obf, &err](const uint8_t* vals, uint32_t groups, size_t t, size_t n) {
-    if (obf && !obf->append(vals, groups, t, n)) drain_set_error(err, obf->to_callback() ? DrainError::OutboardSink : DrainError::FileWrite);  // thread t keeps the values of ITS instances as it receives them
-    return b3_absorb(*b3s, vals, groups, b3s->k, t, n);
-  }, err);
+  // The pool is declared after everything its threads use — the gate-order buffers, `macs`, `files`, the checkpoint files of `commit`:
+  // it is joined first, however this function returns.  Its threads run members of the pool (drain_pipeline.hpp), never a lambda over the locals here.
+  DrainWorkers workers(s->drain.get(), shape, sink, macs, files, commit.err, commit.checkpoints());
   DrainStats stats;
   s->ring_diag.clear();
   Event device_done;
@@ -458,7 +385,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
     if (hipEventRecord(s->pair->ready.get(), s->e->stream.get()) != hipSuccess || hipStreamWaitEvent(gs, s->pair->ready.get(), 0) != hipSuccess) return fail(GSV_ERR_DEVICE, "stream hand-over failed");
   }
   if (hipEventRecord(s->ev0.get(), gs) != hipSuccess) return fail(GSV_ERR_DEVICE, "hipEventRecord failed");
-  DrainPass p{s, ev, gate_id_base, pw0, n_inst, seg_records, want_drain, want_b3, shape.gate_bufs, workers, want_b3 ? &absorbers : nullptr, stats, want_check ? &mac_rx : nullptr, gs, device_done.get(), std::chrono::steady_clock::now(), 0.0};
+  DrainPass p{s, ev, gate_id_base, pw0, n_inst, seg_records, want_drain, shape.gate_bufs, workers, commit, stats, gs, device_done.get(), std::chrono::steady_clock::now(), 0.0};
   int rc = GSV_OK;
   for (uint64_t r0 = first; r0 < total && rc == GSV_OK; r0 += seg) rc = s->plan ? drain_plan_window(p, size_t(r0)) : drain_program_ring(p, r0, std::min(total, r0 + seg));
   if (s->ct_ring && rc != GSV_OK) {
@@ -467,7 +394,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
     (void)hipStreamSynchronize(gs);
   }
   const auto t_finish = std::chrono::steady_clock::now();
-  workers.finish(); absorbers.finish();
+  workers.finish(); commit.join();
   stats.t_wait_drain += drain_secs(t_finish);
   if (ev && hipStreamSynchronize(s->pair->stream.get()) != hipSuccess && rc == GSV_OK) rc = fail(GSV_ERR_DEVICE, "evaluation kernel failed");
   if (s->pass.drain_stats) stats.print(n_inst, T, GROUP, workers.depth());
@@ -480,22 +407,9 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   }
   if (rc == GSV_OK && s->plan) rc = check_plan_error(s);
   if (rc == GSV_OK && ev) rc = check_plan_error(ev);
-  if (rc == GSV_OK && err != DrainError::None) rc = fail_drain(err);
-  // every slice looks at what its last segments left behind: nothing of the check is in flight between two slices
-  if (rc == GSV_OK && want_check) rc = mac_rx.finish(!s->plan || c1 == s->plan->calls.size());
-  if (want_check && rc == GSV_ERR_MISMATCH) { s->mismatch = true; s->mismatch_instance = mac_rx.bad_instance; s->mismatch_group = mac_rx.bad_group; s->mismatch_record = mac_rx.bad_record; }
-  if (rc == GSV_OK && want_ckpt && !checkpoints.flush()) rc = fail(GSV_ERR_INVALID, "short write to a checkpoint file");
-  // the call that ends the pass finishes the BLAKE3 streams: pending chunk values and the last chunks come to the host (<= 1 KiB + 32 B x 2^k per instance)
-  if (rc == GSV_OK && want_b3 && (!s->plan || c1 == s->plan->calls.size()))
-    rc = b3_finish(*s->b3, s->e->stream.get(), sink.b3, obf ? std::function<int(const uint8_t*, uint32_t)>([obf](const uint8_t* vals, uint32_t pend) {
-      return !pend || obf->append(vals, pend, 0, 1) ? GSV_OK : obf->to_callback() ? fail_drain(DrainError::OutboardSink) : fail(GSV_ERR_INVALID, "short write to an outboard file");
-    }) : nullptr, sink.last_chunks);
-  if (rc == GSV_OK && obf && !obf->flush()) rc = fail(GSV_ERR_INVALID, "short write to an outboard file");
+  rc = commit.close(rc, !s->plan || c1 == s->plan->calls.size());
   if (rc != GSV_OK) return rc;
-  if (want_mac) for (size_t i = 0; i < n_inst; ++i) macs[i].digest(sink.hashes + 16 * i);
-  // the commitments a checked pass returns are the ones its checkpoint files claim — proven once the last slice has passed
-  if (want_check && sink.mac_check_hashes && (!s->plan || c1 == s->plan->calls.size())) std::memcpy(sink.mac_check_hashes, mac_claimed.data(), mac_claimed.size());
-  files.keep(); outboards.keep(); checkpoints.keep();
+  files.keep();
   s->garbled = true;
   return GSV_OK;
 }
@@ -571,6 +485,16 @@ static int garble_slice(gsv_session* s, uint64_t gate_id_base, uint64_t first_ca
   if (rc == GSV_OK) { s->next_call = first_call + n_calls; s->garbled = s->plan_retain && s->next_call == s->plan->calls.size(); }
   return rc;
 }
+// What the entry points that take a call range end in: a program session is garbled in one pass, (0, 0) on a plan session is the whole
+// plan.  `any_program_range`: gsv_session_garble_streaming_sink has always ignored a call range on a program session; it still does.
+static int garble_call_range(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const DrainSink& k, int n_threads, bool any_program_range = false) {
+  if (!s->plan) {
+    if (!any_program_range && (first_call || n_calls)) return fail(GSV_ERR_INVALID, "program sessions are garbled in one pass (first_call = n_calls = 0)");
+    return garble_streaming_range(s, gate_id_base, 0, 1, k, n_threads);
+  }
+  if (first_call == 0 && n_calls == 0) n_calls = s->plan->calls.size();
+  return garble_slice(s, gate_id_base, first_call, n_calls, k, n_threads);
+}
 int gsv_session_garble_streaming_calls(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* dir, uint64_t first_index, int n_threads, uint8_t* hashes) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   return garble_slice(s, gate_id_base, first_call, n_calls, mac_file_sink(hashes, dir, first_index), n_threads, dir && !hashes ? "null hash buffer" : nullptr);
@@ -585,16 +509,11 @@ int gsv_session_garble_streaming_commit_outboard(gsv_session* s, uint64_t gate_i
                                                  uint8_t* cbcmac_hashes, uint8_t* blake3_digests, const char* outboard_dir) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   if (!s) return fail(GSV_ERR_INVALID, "null argument");
-  if (outboard_dir && !blake3_digests) return fail(GSV_ERR_INVALID, "an outboard holds the values of the BLAKE3 commitment: blake3_digests must be given");
   DrainSink k = mac_file_sink(cbcmac_hashes, dir, first_index);
   k.b3 = blake3_digests;
   k.outboard_dir = outboard_dir;
-  if (!s->plan) {
-    if (first_call || n_calls) return fail(GSV_ERR_INVALID, "program sessions are garbled in one pass (first_call = n_calls = 0)");
-    return garble_streaming_range(s, gate_id_base, 0, 1, k, n_threads);
-  }
-  if (first_call == 0 && n_calls == 0) n_calls = s->plan->calls.size();
-  return garble_slice(s, gate_id_base, first_call, n_calls, k, n_threads);
+  if (const char* why = k.b3_refusal()) return fail(GSV_ERR_INVALID, why);
+  return garble_call_range(s, gate_id_base, first_call, n_calls, k, n_threads);
 }
 // gsv_session_garble_streaming_calls that also writes <checkpoint_dir>/gc_<first_index + i>.mck (include/gsv_engine.h, "CBC-MAC checkpoints"):
 // the chain states the MAC workers pass through anyway, k = GSV_MAC_GROUP_LOG2 of the pass
@@ -605,12 +524,7 @@ int gsv_session_garble_streaming_checkpoints(gsv_session* s, uint64_t gate_id_ba
   if ((dir || checkpoint_dir) && !hashes) return fail(GSV_ERR_INVALID, "null hash buffer");
   DrainSink k = mac_file_sink(hashes, dir, first_index);
   k.checkpoint_dir = checkpoint_dir;
-  if (!s->plan) {
-    if (first_call || n_calls) return fail(GSV_ERR_INVALID, "program sessions are garbled in one pass (first_call = n_calls = 0)");
-    return garble_streaming_range(s, gate_id_base, 0, 1, k, n_threads);
-  }
-  if (first_call == 0 && n_calls == 0) n_calls = s->plan->calls.size();
-  return garble_slice(s, gate_id_base, first_call, n_calls, k, n_threads);
+  return garble_call_range(s, gate_id_base, first_call, n_calls, k, n_threads);
 }
 // Garbles and verifies against checkpoint files where the ciphertexts are: nothing is drained, no MAC worker starts
 int gsv_session_garble_streaming_check(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, const char* checkpoint_dir, const uint64_t* indexes, uint64_t first_index,
@@ -620,12 +534,7 @@ int gsv_session_garble_streaming_check(gsv_session* s, uint64_t gate_id_base, ui
   DrainSink k;
   k.first_index = first_index;
   k.mac_check_dir = checkpoint_dir; k.mac_check_indexes = indexes; k.mac_check_expected = expected; k.mac_check_hashes = hashes;
-  if (!s->plan) {
-    if (first_call || n_calls) return fail(GSV_ERR_INVALID, "program sessions are garbled in one pass (first_call = n_calls = 0)");
-    return garble_streaming_range(s, gate_id_base, 0, 1, k, 0);
-  }
-  if (first_call == 0 && n_calls == 0) n_calls = s->plan->calls.size();
-  return garble_slice(s, gate_id_base, first_call, n_calls, k, 0);
+  return garble_call_range(s, gate_id_base, first_call, n_calls, k, 0);
 }
 // The generic CiphertextHandler: every drained run of records is handed to `sink` (gate order, per instance in stream order).
 int gsv_session_garble_streaming_sink(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, gsv_ct_sink_fn sink, void* user, int n_threads, uint8_t* hashes) {
@@ -633,9 +542,7 @@ int gsv_session_garble_streaming_sink(gsv_session* s, uint64_t gate_id_base, uin
   if (!s || !sink) return fail(GSV_ERR_INVALID, "null argument");
   DrainSink k;
   k.hashes = hashes; k.fn = sink; k.user = user;
-  if (!s->plan) return garble_streaming_range(s, gate_id_base, 0, 1, k, n_threads);
-  if (first_call == 0 && n_calls == 0) n_calls = s->plan->calls.size();
-  return garble_slice(s, gate_id_base, first_call, n_calls, k, n_threads);
+  return garble_call_range(s, gate_id_base, first_call, n_calls, k, n_threads, /*any_program_range=*/true);
 }
 // ... with either commitment or both, the outboards handed to a second callback and the last chunks returned (include/gsv_engine.h,
 // "Commitments on the callback paths"): gsv_session_garble_streaming_commit_outboard with the handler in place of `dir`, the callback in place of `outboard_dir`.
@@ -643,17 +550,11 @@ int gsv_session_garble_streaming_sink_commit(gsv_session* s, uint64_t gate_id_ba
                                              uint8_t* cbcmac_hashes, uint8_t* blake3_digests, gsv_outboard_sink_fn outboard_sink, void* outboard_user, uint8_t* last_chunks) {
   PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
   if (!s) return fail(GSV_ERR_INVALID, "null argument");
-  if (outboard_sink && !blake3_digests) return fail(GSV_ERR_INVALID, "an outboard holds the values of the BLAKE3 commitment: blake3_digests must be given");
-  if (last_chunks && !blake3_digests) return fail(GSV_ERR_INVALID, "the last chunks come with the BLAKE3 commitment: blake3_digests must be given");
   DrainSink k;
   k.hashes = cbcmac_hashes; k.fn = sink; k.user = user;
   k.b3 = blake3_digests; k.ob_fn = outboard_sink; k.ob_user = outboard_user; k.last_chunks = last_chunks;
-  if (!s->plan) {
-    if (first_call || n_calls) return fail(GSV_ERR_INVALID, "program sessions are garbled in one pass (first_call = n_calls = 0)");
-    return garble_streaming_range(s, gate_id_base, 0, 1, k, n_threads);
-  }
-  if (first_call == 0 && n_calls == 0) n_calls = s->plan->calls.size();
-  return garble_slice(s, gate_id_base, first_call, n_calls, k, n_threads);
+  if (const char* why = k.b3_refusal()) return fail(GSV_ERR_INVALID, why);
+  return garble_call_range(s, gate_id_base, first_call, n_calls, k, n_threads);
 }
 // Garble and evaluate side by side on the device (examples/groth16_garble.rs:171-230: the garbler thread feeds the evaluator thread
 // through a channel; here window k of the garbler's device block is evaluated while window k+1 is garbled).

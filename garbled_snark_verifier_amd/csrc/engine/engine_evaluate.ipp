@@ -144,7 +144,7 @@ static int evaluate_program_rings(EvalPass& p) {
 // A pass in slices (EvalRange): the wire file stays where the previous slice left it, the uploader starts at the slice's first record
 // with the MAC states of the slice before, the B3Stream and the outboard comparison go on where they stood (s->evs); a slice that does
 // not end the pass leaves no group value in flight, gathers no outputs and writes no digests.
-struct EvalVerify { B3Check& check; const uint8_t* expected; uint64_t expected_len; uint8_t kind; bool no_place = false; };  // kind: EvalCarry::commit's bit; no_place: the mismatch was the digest's, at the end of the pass
+struct EvalVerify { B3Check& check; const uint8_t* expected; uint64_t expected_len; EvalCommit kind; bool no_place = false; };  // kind: which Verified* of EvalCommit; no_place: the mismatch was the digest's, at the end of the pass
 static EvalCarry& eval_carry(gsv_session* s) { if (!s->evs) s->evs.reset(new EvalCarry()); return *s->evs; }
 static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests, EvalVerify* vf, const EvalRange& rg) {
   const Program& g = s->prog();
@@ -196,10 +196,10 @@ static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, 
   return GSV_OK;
 }
 static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests, EvalVerify* vf, const EvalRange& rg) {
-  if (vf) s->mismatch = false;
+  if (vf) clear_mismatch(s);
   const int rc = evaluate_streaming_pass_inner(s, gate_id_base, read, hashes, digests, vf, rg);
   if (rc == GSV_ERR_MISMATCH) {  // the stream differs from its outboard at the place the check holds
-    s->mismatch = true; s->mismatch_instance = vf->check.bad_instance; s->mismatch_group = vf->check.bad_group; s->mismatch_record = vf->check.bad_record;
+    set_mismatch(s, vf->check.bad_instance, vf->check.bad_group, vf->check.bad_record);
     s->ran = false;  // no outputs for a stream that did not verify: gsv_session_read_outputs fails as after a pass that never ran
   }
   return rc;
@@ -267,22 +267,20 @@ static int roll_back(gsv_session* s, const EvalRestart& r) {
 // that can be read again from the start (gc files) is then evaluated again at once; a restartable slice over such a source is repeated
 // alone, from its restart point (any call range is a range of the safe schedule's windows); any other source gets the error with the
 // remedy — its records have been consumed — and the host's repeat, of the pass or of the rolled-back slice, succeeds.
-// The commitments and the kind of verification every slice of a pass shares (kind: the verification's bit of EvalCarry::commit, 0 for
+// The commitments and the kind of verification every slice of a pass shares (kind: the verification's member of EvalCommit, None for
 // none).  The verified entry points ask in front of their up-front checks; evaluate_streaming_impl asks again where the slice runs.
-static int check_slice_commit(gsv_session* s, const uint8_t* hashes, const uint8_t* digests, uint8_t kind, const EvalRange& rg) {
+static int check_slice_commit(gsv_session* s, const uint8_t* hashes, const uint8_t* digests, EvalCommit kind, const EvalRange& rg) {
   EvalCarry& cy = eval_carry(s);
-  const uint8_t commit = uint8_t((hashes ? 1 : 0) | (digests ? 2 : 0) | kind);
+  const EvalCommit commit = (hashes ? EvalCommit::Mac : EvalCommit::None) | (digests ? EvalCommit::B3 : EvalCommit::None) | kind;
   if (!rg.first && commit != cy.commit) return fail(GSV_ERR_INVALID, "every slice of a streaming evaluation must ask for the same commitments and the same kind of verification as its first slice");
   cy.commit = commit;
   return GSV_OK;
 }
 static int evaluate_streaming_impl(gsv_session* s, uint64_t gate_id_base, const std::function<int(size_t, uint64_t, uint8_t*, uint64_t)>& read, uint8_t* hashes, uint8_t* digests, EvalRange rg, bool rereadable = false, EvalVerify* vf = nullptr) {
   EvalCarry& cy = eval_carry(s);
-  const uint8_t commit = uint8_t((hashes ? 1 : 0) | (digests ? 2 : 0) | (vf ? vf->kind : 0));
-  if (!rg.first && commit != cy.commit) return fail(GSV_ERR_INVALID, "every slice of a streaming evaluation must ask for the same commitments and the same kind of verification as its first slice");
+  if (int crc = check_slice_commit(s, hashes, digests, vf ? vf->kind : EvalCommit::None, rg)) return crc;  // (records cy.commit in front of the refusal below, not behind it: a verified slice's entry point has recorded the same value already)
   if (vf && rg.restartable && rg.ct1 - rg.ct0 < (64ull << s->pass.b3_subtree_log2))
     return fail(GSV_ERR_INVALID, "a verified restartable slice must hold at least one whole group of 2^k chunks per instance (" + std::to_string(64ull << s->pass.b3_subtree_log2) + " records): this one holds " + std::to_string(rg.ct1 - rg.ct0));
-  cy.commit = commit;
   // the restart points: [0] is this slice's, [1] stays the one of the restartable slice before it — unless this is the repeat of a slice
   // the session was rolled back to, whose predecessor's is still the one in [1]
   const bool repeat = cy.resumable && cy.resume_call == rg.c0 && cy.rp[0].held && cy.rp[0].call == rg.c0;
@@ -372,7 +370,7 @@ static int prepare_verified_pass(gsv_session* s, EvalVerify& vf, const LoadOutbo
     return GSV_OK;
   }
   c.shape(s->n_inst, k, total);
-  s->mismatch = false;
+  clear_mismatch(s);
   eval_carry(s).resumable = false;
   for (size_t i = 0; i < s->n_inst; ++i) if (!load(i, k, total, &c.bytes[i], &why)) return fail(GSV_ERR_INVALID, why);
   std::vector<uint8_t> last(size_t(total - first_of_last) * 16);
@@ -383,7 +381,7 @@ static int prepare_verified_pass(gsv_session* s, EvalVerify& vf, const LoadOutbo
     uint8_t root[32];
     if (!Outboard::parse(c.bytes[i].data(), c.bytes[i].size(), &o, &why) || !o.root(last.data(), last.size(), root, &why)) return fail(GSV_ERR_INVALID, why);
     if (std::memcmp(root, vf.expected + vf.expected_len * i, size_t(vf.expected_len)) != 0) {
-      s->mismatch = true; s->mismatch_instance = i; s->mismatch_group = s->mismatch_record = ~0ull;
+      set_mismatch(s, i, ~0ull, ~0ull);
       s->ran = false;
       return fail(GSV_ERR_MISMATCH, "outboard or last chunk of instance " + std::to_string(i) + " does not match the commitment");
     }
@@ -399,8 +397,8 @@ static int evaluate_from_files(gsv_session* s, uint64_t gate_id_base, const char
   std::string why;
   for (size_t i = 0; i < s->n_inst; ++i)
     if (!files.add(std::string(dir) + "/gc_" + std::to_string(index(i)) + ".bin", &why)) return fail(GSV_ERR_INVALID, why);
-  EvalVerify vf{eval_carry(s).check, expected, expected_len, 4};
-  if (int crc = check_slice_commit(s, hashes, digests, outboard_dir ? vf.kind : 0, rg)) return crc;
+  EvalVerify vf{eval_carry(s).check, expected, expected_len, EvalCommit::VerifiedFiles};
+  if (int crc = check_slice_commit(s, hashes, digests, outboard_dir ? vf.kind : EvalCommit::None, rg)) return crc;
   if (outboard_dir) {
     const int vrc = prepare_verified_pass(s, vf,
         [&](size_t i, uint32_t k, uint64_t n_records, std::vector<uint8_t>* out, std::string* w) { return load_outboard(OutboardWriter::path(outboard_dir, index(i)), k, n_records, out, w); },
@@ -467,7 +465,7 @@ int gsv_session_mismatch_info(const gsv_session* s, uint64_t* instance, uint64_t
 static int evaluate_from_source(gsv_session* s, uint64_t gate_id_base, gsv_ct_source_fn source, void* user, const uint8_t* const* outboards, const uint64_t* outboard_bytes,
                                 const uint8_t* last_chunks, const uint8_t* expected, uint64_t expected_len, uint8_t* cbcmac_hashes, uint8_t* blake3_digests, const EvalRange& rg) {
   if (!outboards) return evaluate_streaming_impl(s, gate_id_base, source_reader(source, user), cbcmac_hashes, blake3_digests, rg);
-  EvalVerify vf{eval_carry(s).check, expected, expected_len, uint8_t(last_chunks ? 8 : 16)};
+  EvalVerify vf{eval_carry(s).check, expected, expected_len, last_chunks ? EvalCommit::VerifiedUpFront : EvalCommit::VerifiedDeferred};
   if (int crc = check_slice_commit(s, cbcmac_hashes, blake3_digests, vf.kind, rg)) return crc;
   const int vrc = prepare_verified_pass(s, vf,
       [&](size_t i, uint32_t k, uint64_t n_records, std::vector<uint8_t>* out, std::string* why) {

@@ -19,6 +19,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -261,7 +262,7 @@ struct gsv_session {
   bool ran = false, last_eval = false, garbled = false;
   std::vector<uint64_t> ct_uploaded;  // per instance: records supplied by gsv_session_upload_ciphertexts
   std::unique_ptr<gsv_drain> drain;    // streaming drain: copy streams, pinned buffers, per-instance MAC states (created on first use)
-  uint8_t pass_commit = 0;             // commitments of the pass in progress (1 CBC-MAC, 2 BLAKE3, 4 outboards, 8 the CBC-MAC check on the device, 16 checkpoint files): a pass with BLAKE3 carries the same ones in every slice
+  PassCommit pass_commit = PassCommit::None;  // what the pass in progress carries, as its first slice asked (drain_pipeline.hpp: commit_slice_conflict)
   std::unique_ptr<B3Stream> b3;        // BLAKE3 commitments of the drained streams: device buffers and per-instance hashers, beside drain->macs (engine_blake3.ipp)
   std::unique_ptr<MacCheckStream> mac_check;  // the CBC-MAC check of a garbling pass against checkpoint files (engine_cbcmac.ipp): device buffers, carries, position — beside `b3`, chained from slice to slice
   uint32_t mck_k = 0;                  // log2 of the group size of the checkpoint files the pass in progress writes (GSV_MAC_GROUP_LOG2 when its first slice began)
@@ -278,6 +279,10 @@ struct gsv_session {
   ~gsv_session();  // selects the device and synchronises the engine's stream; the members then release what they hold
   uint64_t ct_stride() const { return plan ? (plan_retain ? plan->n_ct : plan_max_block) : ct_cap * p->prog.n_ct; }  // n_ct does not depend on the variant
 };
+// The one place a verified pass (evaluated against outboards, or garbled against checkpoint files) reports a differing stream at:
+// what gsv_session_mismatch_info reads.  group = record = ~0: the difference has no place in the stream (a commitment before the pass).
+static inline void set_mismatch(gsv_session* s, uint64_t instance, uint64_t group, uint64_t record) { s->mismatch = true; s->mismatch_instance = instance; s->mismatch_group = group; s->mismatch_record = record; }
+static inline void clear_mismatch(gsv_session* s) { s->mismatch = false; }
 // records of one instance's whole ciphertext stream: what a streaming pass drains or reads, and what a commitment covers
 static inline uint64_t stream_records(const gsv_session* s) { return s->plan ? s->plan->n_ct : s->replays * s->prog().n_ct; }
 PassGuard::PassGuard(gsv_session* s) { if (s) s->pass = knobs::Pass(); ReleaseGate& g = release_gate(); std::lock_guard<std::recursive_mutex> lk(g.mu); ++g.active; }

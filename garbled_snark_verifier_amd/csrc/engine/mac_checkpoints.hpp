@@ -122,11 +122,11 @@ inline bool open_mac_checkpoints(const char* const* paths, size_t n, const uint6
   return true;
 }
 
-// whole 16-byte records of the open file `fd` -> *n_records.  False: *why.
-inline bool mac_file_records(int fd, const std::string& path, uint64_t* n_records, std::string* why) {
+// whole 16-byte records of the open file `fd`, `most` at the most -> *n_records.  False: *why.
+inline bool mac_file_records(int fd, const std::string& path, uint64_t* n_records, std::string* why, uint64_t most = MacCheckpoints::MAX_RECORDS) {
   struct stat sb;
   if (fd < 0 || fstat(fd, &sb) != 0) { *why = "cannot open " + path; return false; }
-  if (sb.st_size < 0 || (uint64_t(sb.st_size) & 15) || uint64_t(sb.st_size) / 16 > MacCheckpoints::MAX_RECORDS) { *why = path + " does not hold whole 16-byte records"; return false; }
+  if (sb.st_size < 0 || (uint64_t(sb.st_size) & 15) || uint64_t(sb.st_size) / 16 > most) { *why = path + " does not hold whole 16-byte records"; return false; }
   *n_records = uint64_t(sb.st_size) / 16;
   return true;
 }
