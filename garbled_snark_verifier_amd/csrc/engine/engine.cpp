@@ -6,6 +6,7 @@
 //   upload_pipeline.hpp       host side of the streaming evaluator, no session in sight: staging buffers, H2D copies, MAC pool, the gc file source (tests/upload_pipeline)
 //   outboard.hpp              BLAKE3 outboards, host code only: format, host writer, loaders, and B3Check — what a receiver's streams are compared with (tests/drain_pipeline)
 //   mac_checkpoints.hpp       CBC-MAC checkpoint files, host code only: format, host writer, host checker (tests/mac_checkpoints)
+//   plan_layout.hpp           what a plan session derives from its schedule, host values only: the parameter policy (plan_sched_params) and the tables of the window launches (PlanLayout, build_plan_layout) (tests/plan_layout, tests/hostsim)
 //   engine_internal.hpp       error reporting, device allocation, the deferred-release gate, the objects behind the opaque handles
 //   engine_abi_record.ipp     gsv_recorder_*, gsv_program_*, gsv_engine_*, gsv_labels_from_seed
 //   engine_session.ipp        program sessions

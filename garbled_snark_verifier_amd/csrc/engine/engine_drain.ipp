@@ -43,9 +43,9 @@ static int garble_discard(gsv_session* s, uint64_t gate_id_base, size_t c0, size
   int rc = GSV_OK;
   if (s->plan) {
     size_t w0 = 0, w1 = 0;
-    if (c0 == 0) HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));
+    if (c0 == 0) HIPCHK(hipMemsetAsync(s->ps.d_error.get(), 0, 4, s->e->stream.get()));
     if (c0 == 0) s->windows_launched = 0;
-    if (s->ct_ring) __atomic_store_n(s->sd.ct_pos.get(), ~0ull, __ATOMIC_RELEASE);  // nothing reads the ciphertexts: every block of the ring is free at once
+    if (s->ring()) __atomic_store_n(s->ps.ct_pos.get(), ~0ull, __ATOMIC_RELEASE);  // nothing reads the ciphertexts: every block of the ring is free at once
     rc = window_range(s, c0, c1, &w0, &w1);
     for (size_t w = w0; w < w1 && rc == GSV_OK; ++w) rc = launch_plan_window(s, w, gate_id_base, false);
     if (rc == GSV_OK) {
@@ -55,7 +55,7 @@ static int garble_discard(gsv_session* s, uint64_t gate_id_base, size_t c0, size
   } else {
     rc = launch(s, gate_id_base, false);
   }
-  if (rc == GSV_OK) { HIPCHK(hipStreamSynchronize(s->e->stream.get())); s->garbled = !s->plan || s->plan_retain; }
+  if (rc == GSV_OK) { HIPCHK(hipStreamSynchronize(s->e->stream.get())); s->garbled = !s->plan || s->retain(); }
   if (rc == GSV_OK && s->plan) rc = check_plan_error(s);
   return rc;
 }
@@ -103,7 +103,7 @@ static int ensure_pair(gsv_session* s) {
     }
     if (!ps->stream) {
       std::vector<Stream> rejected;  // (destroyed when the search ends)
-      uint32_t* const word = s->sd.d_error.as<uint32_t>() + 4;
+      uint32_t* const word = s->ps.d_error.as<uint32_t>() + 4;
       for (int attempt = 0; attempt < 8 && !ps->stream; ++attempt) {
         Stream cand_owner;
         if (cand_owner.create(hipStreamNonBlocking) != hipSuccess) break;
@@ -132,7 +132,7 @@ static int ensure_pair(gsv_session* s) {
 // until calls [k0, k1) of the plan have completed for every instance group, or the window's launch itself has finished (*window_done).
 static int wait_calls_done(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, bool* window_done, hipStream_t launch_stream = nullptr) {
   if (!launch_stream) launch_stream = s->e->stream.get();  // the stream the running window was launched on
-  const Schedule::Window& win = s->sched.windows[w];
+  const Schedule::Window& win = s->sched().windows[w];
   const uint32_t n_wg = uint32_t(s->launch_groups());  // workgroups that count a call done (one per instance under BLAKE3)
   const auto t0 = std::chrono::steady_clock::now();
   bool reported = false;
@@ -145,7 +145,7 @@ static int wait_calls_done(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, b
   uint32_t polls = 0;
   while (!*window_done && k0 < k1) {
     bool all = true;
-    for (uint32_t k = k0; k < k1 && all; ++k) all = __atomic_load_n(s->sd.done.get() + k, __ATOMIC_ACQUIRE) == n_wg;
+    for (uint32_t k = k0; k < k1 && all; ++k) all = __atomic_load_n(s->ps.done.get() + k, __ATOMIC_ACQUIRE) == n_wg;
     if (all) break;
     const hipError_t q = hipStreamQuery(launch_stream);
     if (q == hipSuccess) { *window_done = true; break; }
@@ -156,7 +156,7 @@ static int wait_calls_done(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, b
     std::this_thread::sleep_for(std::chrono::microseconds(100));
     if ((++polls & 1023u) == 0) {  // every ~0.1 s: has any call of the window completed for another workgroup?
       uint64_t sum = 0;
-      for (uint32_t k = win.call0; k < win.call1; ++k) sum += __atomic_load_n(s->sd.done.get() + k, __ATOMIC_RELAXED);
+      for (uint32_t k = win.call0; k < win.call1; ++k) sum += __atomic_load_n(s->ps.done.get() + k, __ATOMIC_RELAXED);
       const auto now = std::chrono::steady_clock::now();
       if (sum != last_sum) { last_sum = sum; last_move = now; }
       else if (std::chrono::duration<double>(now - last_move).count() > deadline)
@@ -166,8 +166,8 @@ static int wait_calls_done(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, b
       reported = true;
       std::string msg;
       for (uint32_t k = win.call0; k < win.call1; ++k)
-        if (s->sd.done.get()[k] != n_wg) msg += " " + std::to_string(k) + "(" + std::to_string(s->sd.done.get()[k]) + "/" + std::to_string(n_wg) + (s->ct_ring ? ",need " + std::to_string(s->sched.ring_need[k]) + ",ready " + std::to_string(s->sched.seg_end[k]) : "") + ")";
-      std::fprintf(stderr, "drain debug: waiting > 3 s for calls [%u, %u) of window %zu; host position %llu; unfinished:%s\n", k0, k1, w, s->sd.ct_pos.get() ? (unsigned long long)*s->sd.ct_pos.get() : 0ull, msg.substr(0, 1500).c_str());
+        if (s->ps.done.get()[k] != n_wg) msg += " " + std::to_string(k) + "(" + std::to_string(s->ps.done.get()[k]) + "/" + std::to_string(n_wg) + (s->ring() ? ",need " + std::to_string(s->sched().ring_need[k]) + ",ready " + std::to_string(s->sched().seg_end[k]) : "") + ")";
+      std::fprintf(stderr, "drain debug: waiting > 3 s for calls [%u, %u) of window %zu; host position %llu; unfinished:%s\n", k0, k1, w, s->ps.ct_pos.get() ? (unsigned long long)*s->ps.ct_pos.get() : 0ull, msg.substr(0, 1500).c_str());
     }
   }
   return GSV_OK;
@@ -188,7 +188,7 @@ static int ensure_ct_gate(gsv_session* s, size_t bytes) {
 }
 static int ensure_aux(gsv_session* s) {
   if (!s->aux_stream) HIPCHK(create_side_stream(s->aux_stream, s->kn.side_stream_priority));
-  if (!s->sd.done) return fail(GSV_ERR_INVALID, "internal: a plan session without completion counters");  // (allocated with its call descriptors)
+  if (!s->ps.done) return fail(GSV_ERR_INVALID, "internal: a plan session without completion counters");  // (allocated with its call descriptors)
   return GSV_OK;
 }
 
@@ -253,10 +253,10 @@ static int drain_plan_window(DrainPass& p, size_t w) {
   // has completed for every instance group: the host follows the completion flags of the running launch (a page-locked copy,
   // refreshed through a side stream), brings the finished segment into gate order with a gather kernel on that side stream — the
   // session's schedule leaves it a few CUs — and hands it to the workers, while the window goes on garbling.
-  const Schedule::Window& win = s->sched.windows[w];
+  const Schedule::Window& win = s->sched().windows[w];
   bool window_done = false;
   for (uint32_t q = win.seg0; p.want_drain && q < win.seg1; ++q) {
-    const Schedule::Segment& sg = s->sched.segments[q];
+    const Schedule::Segment& sg = s->sched().segments[q];
     const bool last = q + 1 == win.seg1;
     const auto t0 = std::chrono::steady_clock::now();
     if (!last && (rc = wait_calls_done(s, w, sg.call0, sg.call1, &window_done, gs)) != GSV_OK) return rc;
@@ -275,8 +275,8 @@ static int drain_plan_window(DrainPass& p, size_t w) {
     if (hipStreamSynchronize(s->aux_stream.get()) != hipSuccess) return fail(GSV_ERR_DEVICE, "ciphertext gather failed");
     p.commit.submit();
     st.t_gather += drain_secs(tg);
-    if (s->ct_ring) {
-      __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);  // the calls whose blocks overlap this segment's may write now
+    if (s->ring()) {
+      __atomic_store_n(s->ps.ct_pos.get(), (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);  // the calls whose blocks overlap this segment's may write now
       const double gap = drain_secs(p.t_last_pub);
       if (gap > p.worst_gap) {
         p.worst_gap = gap;
@@ -318,20 +318,22 @@ static int drain_program_ring(DrainPass& p, uint64_t r0, uint64_t r1) {
 // `ev`: an evaluator session over the same plan / schedule (plan sessions that do not retain the stream): every window is evaluated
 // straight from the garbler's device block while the next window is garbled.
 static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c0, size_t c1, const DrainSink& sink, int n_threads, gsv_session* ev) {
+  if (int urc = plan_session_usable(s)) return urc;
+  if (ev) if (int urc = plan_session_usable(ev)) return urc;
   if (!sink.any() && !ev) return garble_discard(s, gate_id_base, c0, c1);  // garble only (output labels, device-rate measurements of long plans / chains)
   const Program& g = s->prog();
   // program sessions: segments of one ring (ct_cap replays of n_ct records); plan sessions: one WINDOW of the schedule per segment
   size_t pw0 = 0, pw1 = 0;
   if (s->plan) { int wrc = window_range(s, c0, c1, &pw0, &pw1); if (wrc) return wrc; }
   // (plan sessions: the stream leaves the device in SEGMENTS of a window, a gate-order buffer holds the largest segment)
-  const uint64_t n_ct = s->plan ? s->plan_max_segment : g.n_ct, seg = s->plan ? 1 : s->ct_cap;
+  const uint64_t n_ct = s->plan ? s->max_segment() : g.n_ct, seg = s->plan ? 1 : s->ct_cap;
   const uint64_t first = s->plan ? pw0 : 0, total = s->plan ? pw1 : s->replays;
   const bool new_pass = s->plan ? c0 == 0 : true;
   // the instances whose streams leave the device: all of them, or the first drain_instances (every instance is garbled either way)
   const size_t n_inst = s->drain_instances ? std::min(s->drain_instances, s->n_inst) : s->n_inst;
   const bool want_drain = sink.any();    // finished segments are brought into gate order ...
   const bool want_host = sink.host();    // ... and copied out by the workers
-  if (const char* why = sink.refusal(s->ct_ring, ev != nullptr)) return fail(GSV_ERR_INVALID, why);
+  if (const char* why = sink.refusal(s->ring(), ev != nullptr)) return fail(GSV_ERR_INVALID, why);
   if (sink.mac_check_dir) clear_mismatch(s);
   if (s->plan && new_pass) s->windows_launched = 0;
   const size_t GROUP = size_t(gsv_drain::group_for(n_inst, s->pass.drain_group));
@@ -350,12 +352,12 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   // Declared before the pools and the gc files: its own threads are joined, and its files removed, after theirs (engine_garble_commit.ipp)
   GarbleCommit commit(s, sink);
   if (int rc = commit.begin(new_pass, n_inst, seg_records)) return rc;
-  if (ev && (s->ct_ring || ev->ct_ring)) return fail(GSV_ERR_INVALID, "garble || evaluate pairs need sessions with explicit launch windows (window_ct_records, e.g. 1 << 28): the default is one whole-pass window over a ciphertext ring");
+  if (ev && (s->ring() || ev->ring())) return fail(GSV_ERR_INVALID, "garble || evaluate pairs need sessions with explicit launch windows (window_ct_records, e.g. 1 << 28): the default is one whole-pass window over a ciphertext ring");
   if (ev) { int rc = ensure_pair(s); if (rc) return rc; }
-  if (s->ct_ring) __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(s->plan && pw0 < s->sched.windows.size() ? s->sched.windows[pw0].ct0 : 0), __ATOMIC_RELEASE);
+  if (s->ring()) __atomic_store_n(s->ps.ct_pos.get(), (unsigned long long)(s->plan && pw0 < s->sched().windows.size() ? s->sched().windows[pw0].ct0 : 0), __ATOMIC_RELEASE);
   if (s->plan && want_drain) { int rc = ensure_aux(s); if (rc) return rc; }
-  if (s->plan && new_pass) HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));  // a new pass starts with a clean dependency-wait flag
-  if (ev && new_pass) HIPCHK(hipMemsetAsync(ev->sd.d_error.get(), 0, 4, s->e->stream.get()));
+  if (s->plan && new_pass) HIPCHK(hipMemsetAsync(s->ps.d_error.get(), 0, 4, s->e->stream.get()));  // a new pass starts with a clean dependency-wait flag
+  if (ev && new_pass) HIPCHK(hipMemsetAsync(ev->ps.d_error.get(), 0, 4, s->e->stream.get()));
   std::vector<CbcMacHost> no_macs;
   if (want_host && (new_pass || s->drain->macs.size() != n_inst)) s->drain->macs.assign(n_inst, CbcMacHost());  // a new pass starts from h = 0; later slices chain
   std::vector<CbcMacHost>& macs = want_host ? s->drain->macs : no_macs;
@@ -367,7 +369,7 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   shape.chunk = want_host ? s->drain->chunk : 0; shape.seg_records = seg_records; shape.blocking_wait = T > 8;
   if (want_drain) {
     size_t n_units = size_t((total - first + seg - 1) / seg);  // drain units of this call: segments (plans) or rings
-    if (s->plan) { n_units = 0; for (size_t w = pw0; w < pw1; ++w) n_units += s->sched.windows[w].seg1 - s->sched.windows[w].seg0; }
+    if (s->plan) { n_units = 0; for (size_t w = pw0; w < pw1; ++w) n_units += s->sched().windows[w].seg1 - s->sched().windows[w].seg0; }
     shape.gate_bufs = drain_gate_buffers(s, n_units, n_inst, seg_records, want_host);
   }
   // The pool is declared after everything its threads use — the gate-order buffers, `macs`, `files`, the checkpoint files of `commit`:
@@ -388,9 +390,9 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
   DrainPass p{s, ev, gate_id_base, pw0, n_inst, seg_records, want_drain, shape.gate_bufs, workers, commit, stats, gs, device_done.get(), std::chrono::steady_clock::now(), 0.0};
   int rc = GSV_OK;
   for (uint64_t r0 = first; r0 < total && rc == GSV_OK; r0 += seg) rc = s->plan ? drain_plan_window(p, size_t(r0)) : drain_program_ring(p, r0, std::min(total, r0 + seg));
-  if (s->ct_ring && rc != GSV_OK) {
+  if (s->ring() && rc != GSV_OK) {
     // a failed pass: calls of the running window may still wait for room in the ring — let them run out (the results are discarded)
-    __atomic_store_n(s->sd.ct_pos.get(), ~0ull, __ATOMIC_RELEASE);
+    __atomic_store_n(s->ps.ct_pos.get(), ~0ull, __ATOMIC_RELEASE);
     (void)hipStreamSynchronize(gs);
   }
   const auto t_finish = std::chrono::steady_clock::now();
@@ -418,22 +420,33 @@ static int garble_streaming_pass(gsv_session* s, uint64_t gate_id_base, size_t c
 // is switched, in place, to the SAFE schedule: one call per launch, in stream order, no dependency wait on the device at all (the stream
 // orders the launches) and no ciphertext ring.  Same plan images, same wire-file and ciphertext allocations (the safe schedule needs
 // less of both; re-allocated if not), the host's last inputs re-staged.  Slower (every call ends with a launch boundary), never wrong.
+// The safe PlanState is built whole beside the installed one (tables of KBs to MBs: no memory peak) and then swapped in: a failure up
+// to there leaves the session exactly as it was, on its old schedule.  A failure while W / VB / CT grow afterwards leaves the session
+// without a schedule and with the reason in `unusable`: it refuses to stage inputs or to run from then on (plan_session_usable).
 static int fall_back_to_safe_schedule(gsv_session* s) {
-  if (!s->plan || s->safe_mode) return fail(GSV_ERR_DEVICE, "internal: no safe schedule to fall back to");
+  if (int rc = plan_session_usable(s)) return rc;
+  if (!s->plan || s->safe()) return fail(GSV_ERR_DEVICE, "internal: no safe schedule to fall back to");
   HIPCHK(hipSetDevice(s->e->device));
   HIPCHK(hipDeviceSynchronize());
-  drop_schedule(s);
   gsv_plan_session_opts o = s->opts;
   o.max_concurrent_calls = 1;
   o.max_window_calls = 1;
   if (o.retain_stream == GSV_STREAM_RING) o.retain_stream = 0;
-  s->safe_mode = true;
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, s->e->device));
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  int rc = install_schedule(s, o, prop.multiProcessorCount, free_b);
-  if (rc || (rc = alloc_session_buffers(s, s->facade))) return rc;  // (W / VB / CT grow where the safe schedule needs more; VB cleared)
+  gsv_session::PlanState safe;
+  int rc = make_plan_state(s, o, true, prop.multiProcessorCount, free_b, &safe);
+  if (rc) return rc;
+  s->ps = std::move(safe);  // (the device is idle: the old tables go here)
+  s->next_call = 0;
+  if ((rc = alloc_session_buffers(s, s->prog()))) {  // (W / VB / CT grow where the safe schedule needs more; VB cleared)
+    s->unusable = "the fall-back to the safe schedule failed while the session's buffers were growing (" + g_err + "): the session has no schedule left and cannot run; destroy it";
+    s->ps = gsv_session::PlanState();
+    s->garbled = s->ran = false;
+    return rc;
+  }
   ++s->n_fallbacks;
   s->dep_fault = false;
   s->garbled = false;
@@ -453,7 +466,7 @@ int gsv_session_fallback_count(const gsv_session* s, uint64_t* n) {
 // but leaves the session on the safe schedule, so that the host's own repeat of the pass (from gsv_session_set_garble_inputs on) succeeds.
 static int garble_streaming_range(gsv_session* s, uint64_t gate_id_base, size_t c0, size_t c1, const DrainSink& sink, int n_threads, gsv_session* ev = nullptr) {
   int rc = garble_streaming_pass(s, gate_id_base, c0, c1, sink, n_threads, ev);
-  if (rc != GSV_ERR_DEVICE || !s->plan || !(s->dep_fault || (ev && ev->dep_fault)) || s->safe_mode) return rc;
+  if (rc != GSV_ERR_DEVICE || !s->plan || !(s->dep_fault || (ev && ev->dep_fault)) || s->safe()) return rc;
   const std::string first_error = g_err;
   const bool whole = c0 == 0 && c1 == s->plan->calls.size();
   int frc = fall_back_to_safe_schedule(s);
@@ -482,7 +495,7 @@ static int garble_slice(gsv_session* s, uint64_t gate_id_base, uint64_t first_ca
                                      " (gsv_session_set_unchecked_slices for timing runs)");
   if (arg_error) return fail(GSV_ERR_INVALID, arg_error);
   const int rc = garble_streaming_range(s, gate_id_base, size_t(first_call), size_t(first_call + n_calls), k, n_threads);
-  if (rc == GSV_OK) { s->next_call = first_call + n_calls; s->garbled = s->plan_retain && s->next_call == s->plan->calls.size(); }
+  if (rc == GSV_OK) { s->next_call = first_call + n_calls; s->garbled = s->retain() && s->next_call == s->plan->calls.size(); }
   return rc;
 }
 // What the entry points that take a call range end in: a program session is garbled in one pass, (0, 0) on a plan session is the whole
@@ -564,9 +577,9 @@ int gsv_session_garble_evaluate(gsv_session* gs, gsv_session* es, uint64_t gate_
   es->pass = gs->pass;
   if (!gs->plan || gs->plan != es->plan || gs->e != es->e || gs->n_inst != es->n_inst || gs->ni != es->ni || gs->hasher != es->hasher)
     return fail(GSV_ERR_INVALID, "garbler and evaluator must be plan sessions of the same plan, engine, instance count and hasher");
-  if (gs->plan_retain || es->plan_retain) return fail(GSV_ERR_INVALID, "gsv_session_garble_evaluate is for sessions that do not retain the stream (retain_stream = 0)");
-  const auto &wa = gs->sched.windows, &wb = es->sched.windows;
-  if (wa.size() != wb.size() || gs->plan_max_block != es->plan_max_block) return fail(GSV_ERR_INVALID, "garbler and evaluator sessions have different schedules (create both with the same options)");
+  if (gs->retain() || es->retain()) return fail(GSV_ERR_INVALID, "gsv_session_garble_evaluate is for sessions that do not retain the stream (retain_stream = 0)");
+  const auto &wa = gs->sched().windows, &wb = es->sched().windows;
+  if (wa.size() != wb.size() || gs->max_block() != es->max_block()) return fail(GSV_ERR_INVALID, "garbler and evaluator sessions have different schedules (create both with the same options)");
   for (size_t i = 0; i < wa.size(); ++i) if (wa[i].call0 != wb[i].call0 || wa[i].call1 != wb[i].call1) return fail(GSV_ERR_INVALID, "garbler and evaluator sessions have different schedules (create both with the same options)");
   DrainSink k;
   k.hashes = hashes;

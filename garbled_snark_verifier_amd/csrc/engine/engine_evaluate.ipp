@@ -11,7 +11,7 @@ static int check_resident_stream(const gsv_session* s, uint64_t need) {
 int gsv_session_evaluate(gsv_session* s, uint64_t gate_id_base) {
   if (!s) return fail(GSV_ERR_INVALID, "null session");
   s->pass = knobs::Pass();  // this pass's knobs
-  if (s->ct_cap != s->replays || (s->plan && !s->plan_retain)) return fail(GSV_ERR_INVALID, "evaluate needs the whole ciphertext stream resident (ct_capacity_replays == replays)");
+  if (s->ct_cap != s->replays || (s->plan && !s->retain())) return fail(GSV_ERR_INVALID, "evaluate needs the whole ciphertext stream resident (ct_capacity_replays == replays)");
   if (int rc = check_resident_stream(s, s->prog().n_ct * s->replays)) return rc;
   return launch(s, gate_id_base, true);
 }
@@ -32,7 +32,7 @@ static int eval_range(const gsv_session* s, size_t c0, size_t c1, bool restartab
   if (!s->plan) return GSV_OK;
   rg->c0 = c0; rg->c1 = c1;
   if (int rc = window_range(s, c0, c1, &rg->w0, &rg->w1)) return rc;
-  const auto& ws = s->sched.windows;
+  const auto& ws = s->sched().windows;
   rg->ct0 = rg->w0 < ws.size() ? ws[rg->w0].ct0 : s->plan->n_ct;
   rg->ct1 = rg->w1 < ws.size() ? ws[rg->w1].ct0 : s->plan->n_ct;
   rg->first = c0 == 0; rg->last = c1 == s->plan->calls.size();
@@ -66,14 +66,14 @@ static int evaluate_plan_ring(EvalPass& p) {
   gsv_session* const s = p.s;
   int rc = ensure_aux(s);
   for (size_t w = p.rg.w0; w < p.rg.w1 && rc == GSV_OK; ++w) {  // (a ring's schedule is one window: the slice is the pass)
-    const Schedule::Window& win = s->sched.windows[w];
-    __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)win.ct0, __ATOMIC_RELEASE);
+    const Schedule::Window& win = s->sched().windows[w];
+    __atomic_store_n(s->ps.ct_pos.get(), (unsigned long long)win.ct0, __ATOMIC_RELEASE);
     rc = launch_plan_window(s, w, p.gate_id_base, true);
     bool window_done = false;
     for (uint32_t q = win.seg0; q < win.seg1 && rc == GSV_OK; ++q) {
-      const Schedule::Segment& sg = s->sched.segments[q];
+      const Schedule::Segment& sg = s->sched().segments[q];
       uint32_t o0 = ~0u, o1 = 0;
-      for (uint32_t k = sg.call0; k < sg.call1; ++k) if (s->sched.ovl1[k] > s->sched.ovl0[k]) { o0 = std::min(o0, s->sched.ovl0[k]); o1 = std::max(o1, s->sched.ovl1[k]); }
+      for (uint32_t k = sg.call0; k < sg.call1; ++k) if (s->sched().ovl1[k] > s->sched().ovl0[k]) { o0 = std::min(o0, s->sched().ovl0[k]); o1 = std::max(o1, s->sched().ovl1[k]); }
       // [ovl0, ovl1) is a RANGE around the overwritten calls: the calls it spans beside them are earlier calls too, but those of this
       // very segment cannot run before this upload — and are never among the overwritten ones (the ring holds two segments and a call)
       o1 = std::min(o1, sg.call0);
@@ -85,11 +85,11 @@ static int evaluate_plan_ring(EvalPass& p) {
       if (rc == GSV_OK) rc = p.hash(sg.n_ct, s->aux_stream.get());
       if (rc == GSV_OK) rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, p.seg_records, 1, nullptr, nullptr, s->aux_stream.get());
       if (rc == GSV_OK && hipStreamSynchronize(s->aux_stream.get()) != hipSuccess) rc = fail(GSV_ERR_DEVICE, "ciphertext scatter failed");
-      if (rc == GSV_OK) __atomic_store_n(s->sd.ct_pos.get(), (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);
+      if (rc == GSV_OK) __atomic_store_n(s->ps.ct_pos.get(), (unsigned long long)(sg.ct0 + sg.n_ct), __ATOMIC_RELEASE);
     }
     if (rc != GSV_OK) {
       // let the calls that still wait for ciphertexts run out (their results are discarded with the error) instead of hanging the stream
-      __atomic_store_n(s->sd.ct_pos.get(), ~0ull, __ATOMIC_RELEASE);
+      __atomic_store_n(s->ps.ct_pos.get(), ~0ull, __ATOMIC_RELEASE);
       (void)hipStreamSynchronize(s->e->stream.get());
       break;
     }
@@ -102,9 +102,9 @@ static int evaluate_plan_windows(EvalPass& p) {
   gsv_session* const s = p.s;
   int rc = GSV_OK;
   for (size_t w = p.rg.w0; w < p.rg.w1 && rc == GSV_OK; ++w) {
-    const Schedule::Window& win = s->sched.windows[w];
+    const Schedule::Window& win = s->sched().windows[w];
     for (uint32_t q = win.seg0; q < win.seg1 && rc == GSV_OK; ++q) {
-      const Schedule::Segment& sg = s->sched.segments[q];
+      const Schedule::Segment& sg = s->sched().segments[q];
       // (the stream orders this segment's uploads behind the scatter of the previous one, which read the same buffer)
       rc = p.upload(sg.ct0, sg.n_ct, s->e->stream.get());
       if (rc == GSV_OK) rc = p.hash(sg.n_ct, s->e->stream.get());
@@ -147,6 +147,7 @@ static int evaluate_program_rings(EvalPass& p) {
 struct EvalVerify { B3Check& check; const uint8_t* expected; uint64_t expected_len; EvalCommit kind; bool no_place = false; };  // kind: which Verified* of EvalCommit; no_place: the mismatch was the digest's, at the end of the pass
 static EvalCarry& eval_carry(gsv_session* s) { if (!s->evs) s->evs.reset(new EvalCarry()); return *s->evs; }
 static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests, EvalVerify* vf, const EvalRange& rg) {
+  if (int urc = plan_session_usable(s)) return urc;
   const Program& g = s->prog();
   EvalCarry& cy = eval_carry(s);
   if (s->plan && rg.first) s->windows_launched = 0;
@@ -154,7 +155,7 @@ static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, 
   // holds the largest segment, the program-order device block the largest window); program sessions: one ring per launch
   const size_t n_inst = s->n_inst;
   HIPCHK(hipSetDevice(s->e->device));
-  const uint64_t seg_records = s->plan ? s->plan_max_segment : s->ct_cap * g.n_ct;  // per instance: stride of the gate-order buffer
+  const uint64_t seg_records = s->plan ? s->max_segment() : s->ct_cap * g.n_ct;  // per instance: stride of the gate-order buffer
   if (seg_records) { int grc = ensure_ct_gate(s, n_inst * size_t(seg_records) * 16); if (grc) return grc; }  // (a sample drain before may have sized it for fewer instances)
   // With hashes asked for, T workers fold the chunks into the per-instance CBC-MACs beside the uploads (upload_pipeline.hpp; the
   // reference folds while reading, ciphertext_source.rs:36-107, and runs its finalized cases under into_par_iter: cut_and_choose/evaluator.rs:118-181)
@@ -172,9 +173,9 @@ static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, 
     const int brc = rg.first ? b3.begin(n_inst, stream_records(s), seg_records, s->pass.b3_subtree_log2) : b3.resume(n_inst, stream_records(s), seg_records, s->pass.b3_subtree_log2);
     if (brc) return brc;
   }
-  if (s->plan && rg.first) HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));
+  if (s->plan && rg.first) HIPCHK(hipMemsetAsync(s->ps.d_error.get(), 0, 4, s->e->stream.get()));
   HIPCHK(hipEventRecord(s->ev0.get(), s->e->stream.get()));
-  int rc = s->plan ? (s->ct_ring ? evaluate_plan_ring(p) : evaluate_plan_windows(p)) : evaluate_program_rings(p);
+  int rc = s->plan ? (s->ring() ? evaluate_plan_ring(p) : evaluate_plan_windows(p)) : evaluate_program_rings(p);
   if (hipStreamSynchronize(s->e->stream.get()) != hipSuccess && rc == GSV_OK) rc = fail(GSV_ERR_DEVICE, "kernel failed");
   if (rc != GSV_OK) return rc;
   if (s->plan) {
@@ -217,7 +218,7 @@ static int take_restart_point(gsv_session* s, EvalRestart& r, const EvalRange& r
   if (int rc = ensure_dev(r.VB, n * slots, "a restart point's plaintext bits")) return rc;
   HIPCHK(hipMemcpyAsync(r.W.get(), s->W.get(), n * slots * 16, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(r.VB.get(), s->VB.get(), n * slots, hipMemcpyDeviceToDevice, st));
-  r.n_slots = uint32_t(slots); r.global_base = s->global_base;
+  r.n_slots = uint32_t(slots); r.global_base = s->ps.L.global_base;
   r.b3 = false;
   if (want_b3 && !rg.first) {
     if (!s->b3_eval) return fail(GSV_ERR_INVALID, "this slice continues a pass whose earlier slices computed no BLAKE3 commitment");
@@ -238,14 +239,14 @@ static int roll_back(gsv_session* s, const EvalRestart& r) {
   const hipStream_t st = s->e->stream.get();
   HIPCHK(hipSetDevice(s->e->device));
   HIPCHK(hipStreamSynchronize(st));  // whatever the failed slice left queued
-  if (r.n_slots == slots && r.global_base == s->global_base) {
+  if (r.n_slots == slots && r.global_base == s->ps.L.global_base) {
     HIPCHK(hipMemcpyAsync(s->W.get(), r.W.get(), n * slots * 16, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(s->VB.get(), r.VB.get(), n * slots, hipMemcpyDeviceToDevice, st));
   } else {
     const size_t n_glob = s->plan ? s->plan->n_globals : 0;
-    if (!s->plan || r.n_slots - r.global_base != n_glob || slots - s->global_base != n_glob) return fail(GSV_ERR_INVALID, "internal: a restart point of another wire file");
+    if (!s->plan || r.n_slots - r.global_base != n_glob || slots - s->ps.L.global_base != n_glob) return fail(GSV_ERR_INVALID, "internal: a restart point of another wire file");
     for (int part = 0; part < 2; ++part) {
-      const size_t from = part ? r.global_base : 0, to = part ? s->global_base : 0, count = part ? n_glob : SLOT_FIRST_INPUT;
+      const size_t from = part ? r.global_base : 0, to = part ? s->ps.L.global_base : 0, count = part ? n_glob : SLOT_FIRST_INPUT;
       if (!count) continue;
       HIPCHK(hipMemcpy2DAsync(s->W.as<uint8_t>() + to * 16, slots * 16, r.W.as<uint8_t>() + from * 16, size_t(r.n_slots) * 16, count * 16, n, hipMemcpyDeviceToDevice, st));
       HIPCHK(hipMemcpy2DAsync(s->VB.as<uint8_t>() + to, slots, r.VB.as<uint8_t>() + from, size_t(r.n_slots), count, n, hipMemcpyDeviceToDevice, st));
@@ -291,7 +292,7 @@ static int evaluate_streaming_impl(gsv_session* s, uint64_t gate_id_base, const 
     if (int rc = take_restart_point(s, cy.rp[0], rg, digests != nullptr)) { cy.rp[0].held = cy.rp[1].held = false; cy.next_call = 0; return rc; }
   } else cy.rp[0].held = cy.rp[1].held = false;
   int rc = evaluate_streaming_pass(s, gate_id_base, read, hashes, digests, vf, rg);
-  if (rc == GSV_ERR_DEVICE && s->plan && s->dep_fault && !s->safe_mode) {
+  if (rc == GSV_ERR_DEVICE && s->plan && s->dep_fault && !s->safe()) {
     const std::string first_error = g_err;
     const bool whole = rg.first && rg.last;
     if (fall_back_to_safe_schedule(s)) { cy.next_call = 0; return fail(GSV_ERR_DEVICE, first_error + "; the fall-back to the safe schedule failed too: " + g_err); }
@@ -344,7 +345,7 @@ static int eval_slice_range(gsv_session* s, uint64_t first_call, uint64_t n_call
   if (first_call != 0 && first_call != cy.next_call && !s->unchecked_slices)
     return fail(GSV_ERR_INVALID, "slice starts at call " + std::to_string(first_call) + " but the previous evaluate slice ended at call " + std::to_string(cy.next_call) +
                                      " (gsv_session_set_unchecked_slices for timing runs)");
-  if (restartable && s->ct_ring) return fail(GSV_ERR_INVALID, "restart points are not available over a ciphertext ring (retain_stream = GSV_STREAM_RING): its pass is one launch; use launch windows (retain_stream = 0)");
+  if (restartable && s->ring()) return fail(GSV_ERR_INVALID, "restart points are not available over a ciphertext ring (retain_stream = GSV_STREAM_RING): its pass is one launch; use launch windows (retain_stream = 0)");
   return eval_range(s, size_t(first_call), size_t(first_call + n_calls), restartable != 0, rg);
 }
 static int eval_whole_range(gsv_session* s, EvalRange* rg) { return eval_range(s, 0, s->plan ? s->plan->calls.size() : 0, false, rg); }
@@ -441,7 +442,7 @@ static const char* const VERIFIED_OVER_A_RING =
 static int check_verified_args(const gsv_session* s, const uint8_t* expected, uint64_t expected_len, const uint8_t* blake3_digests) {
   if (!expected || !blake3_digests) return fail(GSV_ERR_INVALID, "null argument");
   if (expected_len != 16 && expected_len != 32) return fail(GSV_ERR_INVALID, "expected_len must be 16 (a truncated digest) or 32");
-  if (s->plan && s->ct_ring) return fail(GSV_ERR_INVALID, VERIFIED_OVER_A_RING);
+  if (s->plan && s->ring()) return fail(GSV_ERR_INVALID, VERIFIED_OVER_A_RING);
   return GSV_OK;
 }
 int gsv_session_evaluate_streaming_verified(gsv_session* s, uint64_t gate_id_base, const char* dir, const uint64_t* indexes, uint64_t first_index, const char* outboard_dir, const uint8_t* expected,

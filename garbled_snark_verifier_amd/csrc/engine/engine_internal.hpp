@@ -33,6 +33,7 @@
 #include "knobs.hpp"
 #include "mac_checkpoints.hpp"
 #include "plan_builder.hpp"
+#include "plan_layout.hpp"
 #include "schedule.hpp"
 #include "program.hpp"
 #include "upload_pipeline.hpp"
@@ -220,45 +221,44 @@ struct gsv_session {
   // the layout, and the hasher may change after creation.  Everything that counts workgroups or indexes by blockIdx.x asks here.
   uint32_t launch_ni() const { return hasher == 1 ? 1u : ni; }
   size_t launch_groups() const { return (n_inst + launch_ni() - 1) / launch_ni(); }  // grid.x of a launch = instance groups
-  // plan sessions: `facade` stands in for the program (slots = wire-file stride, inputs / outputs in the global region)
   const gsv_plan* plan = nullptr;
-  Program facade;
-  uint32_t global_base = 0;  // first slot of the plan's global region
-  bool plan_retain = true;   // plan sessions: whole ciphertext stream kept on the device (else one call block: streaming only)
-  uint64_t plan_max_block = 0;  // ciphertext records per instance of the device block: the largest WINDOW of the schedule
-  uint64_t plan_max_segment = 0;  // ... of a gate-order buffer: the largest drain SEGMENT (schedule.hpp)
-  bool ct_ring = false;              // the device block is a ring of plan_max_block records (schedule.hpp, SchedParams::ring_ct)
   std::string ring_diag;  // ring mode: the longest interval between two publications of the host's position in the last pass, and where it went
   Stream aux_stream;  // gather kernels and flag polls of the drain, beside the running window
   std::vector<const DevProgram*> call_dev;  // per call of the plan: its program's image (owned by that program)
   // Call-level schedule (schedule.hpp): windows of consecutive calls; the calls of a window run as a dataflow inside ONE launch
-  // (grid.y = calls), each waiting for the completion flags of the calls it depends on.  Device tables in stream order: the call
-  // descriptors, the concatenated wire hand-over lists (globals -> the call's scratch region -> globals), the dependency lists
-  // (window-relative call indices) and the completion flags [instance group][call] (compared with the launch epoch: never reset).
-  Schedule sched;
-  struct ScheduleState {  // what install_schedule allocates for `sched`; drop_schedule assigns a fresh one
+  // (grid.y = calls), each waiting for the completion flags of the calls it depends on.  Everything of the session that depends on the
+  // schedule is ONE value: the layout (plan_layout.hpp: schedule, facade, wire-file layout, the tables in stream order) and what
+  // make_plan_state puts on the device for it — the tables, the completion flags [instance group][call] (compared with the launch epoch:
+  // never reset) and the two mapped counters.  Built whole, then assigned: the session never holds half of one.
+  struct PlanState {
+    PlanLayout L;
     DevBuf d_calls, d_copy_src, d_copy_dst, d_deps, d_flags, d_error, plan_out_slots;
     MappedHost<uint32_t> done;  // per call of the plan: workgroups that have finished it in the current pass (mapped host memory, written by the device)
     MappedHost<unsigned long long> ct_pos;  // ring mode: the host's stream-position counter (page-locked, mapped into the device)
-    uint32_t flag_stride = 0;
-  } sd;
+  } ps;
+  const Schedule& sched() const { return ps.L.sched; }
+  bool retain() const { return ps.L.retain; }              // plan sessions: whole ciphertext stream kept on the device (else one block: streaming only)
+  bool ring() const { return ps.L.ring; }                  // the device block is a ring of max_block() records
+  bool safe() const { return ps.L.safe; }                  // the schedule is the safe one
+  uint64_t max_block() const { return ps.L.max_block; }    // ciphertext records per instance of the device block
+  uint64_t max_segment() const { return ps.L.max_segment; }  // ... of a gate-order buffer
+  // A fall-back to the safe schedule that failed while the session's buffers were growing leaves `ps` empty and says why here: the
+  // session then refuses to stage inputs or to run (plan_session_usable)
+  std::string unusable;
   uint32_t epoch = 0;
-  // Safe-schedule fallback (round 6): the options the session was created with, the host's last inputs (re-staged when a pass is
-  // repeated) and what the big allocations hold, so that a second schedule can be installed into the same session.
+  // Safe-schedule fallback (round 6): the options the session was created with and the host's last inputs (re-staged when a pass is
+  // repeated), so that a second schedule can be installed into the same session.
   gsv_plan_session_opts opts{};
-  bool safe_mode = false;                    // the schedule is the safe one: ONE call per launch, no dependency waits on the device
   bool dep_fault = false;                    // the last pass ended with status 1 (a dependency wait gave up)
   uint64_t n_fallbacks = 0;
-  size_t w_slots_cap = 0;                    // 16-byte slots per instance W / VB were allocated for
-  uint64_t ct_records_cap = 0;               // ciphertext records per instance CT was allocated for
   std::vector<uint8_t> stash_delta, stash_consts, stash_inputs, stash_bits;
   int stash_kind = 0;                        // 0 nothing, 1 garble inputs, 2 evaluate inputs
   size_t drain_instances = 0;               // streaming calls: only the first this-many instances' streams leave the device (0 = all)
   uint64_t next_call = 0;                   // streaming slices: the call the next slice must start with
   bool unchecked_slices = false;            // benchmarks may garble slices out of order (results are then meaningless)
-  const Program& prog() const { return plan ? facade : p->variant(ni); }
+  const Program& prog() const { return plan ? ps.L.facade : p->variant(ni); }
   const Program& call_prog(size_t k) const { return plan->calls[k].prog->variant(ni); }
-  uint32_t first_input_slot() const { return plan ? global_base : SLOT_FIRST_INPUT; }
+  uint32_t first_input_slot() const { return plan ? ps.L.global_base : SLOT_FIRST_INPUT; }
   bool ran = false, last_eval = false, garbled = false;
   std::vector<uint64_t> ct_uploaded;  // per instance: records supplied by gsv_session_upload_ciphertexts
   std::unique_ptr<gsv_drain> drain;    // streaming drain: copy streams, pinned buffers, per-instance MAC states (created on first use)
@@ -277,12 +277,14 @@ struct gsv_session {
   std::unique_ptr<PairState> pair;     // ... and its stream / events (created on first use)
   gsv_session();   // (both in engine_drain.ipp, where PairState, B3Stream and EvalCarry are complete)
   ~gsv_session();  // selects the device and synchronises the engine's stream; the members then release what they hold
-  uint64_t ct_stride() const { return plan ? (plan_retain ? plan->n_ct : plan_max_block) : ct_cap * p->prog.n_ct; }  // n_ct does not depend on the variant
+  uint64_t ct_stride() const { return plan ? (retain() ? plan->n_ct : max_block()) : ct_cap * p->prog.n_ct; }  // n_ct does not depend on the variant
 };
 // The one place a verified pass (evaluated against outboards, or garbled against checkpoint files) reports a differing stream at:
 // what gsv_session_mismatch_info reads.  group = record = ~0: the difference has no place in the stream (a commitment before the pass).
 static inline void set_mismatch(gsv_session* s, uint64_t instance, uint64_t group, uint64_t record) { s->mismatch = true; s->mismatch_instance = instance; s->mismatch_group = group; s->mismatch_record = record; }
 static inline void clear_mismatch(gsv_session* s) { s->mismatch = false; }
+// what stage_labels, launch and the streaming passes ask first: a session left without a schedule (gsv_session::unusable) refuses
+static inline int plan_session_usable(const gsv_session* s) { return s->unusable.empty() ? GSV_OK : fail(GSV_ERR_DEVICE, s->unusable); }
 // records of one instance's whole ciphertext stream: what a streaming pass drains or reads, and what a commitment covers
 static inline uint64_t stream_records(const gsv_session* s) { return s->plan ? s->plan->n_ct : s->replays * s->prog().n_ct; }
 PassGuard::PassGuard(gsv_session* s) { if (s) s->pass = knobs::Pass(); ReleaseGate& g = release_gate(); std::lock_guard<std::recursive_mutex> lk(g.mu); ++g.active; }

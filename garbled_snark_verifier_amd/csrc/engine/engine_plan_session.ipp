@@ -1,78 +1,14 @@
-// Part of engine.cpp: plan sessions — schedule, wire-file layout and device tables (install_schedule), inputs, window launches, the non-streaming garble.
+// Part of engine.cpp: plan sessions — schedule, wire-file layout and device tables (make_plan_state), inputs, window launches, the non-streaming garble.
 int gsv_session_create_plan(gsv_engine* e, const gsv_plan* plan, size_t n_instances, gsv_session** out) { return gsv_session_create_plan_ex(e, plan, n_instances, 1, out); }
 int gsv_session_create_plan_ex(gsv_engine* e, const gsv_plan* plan, size_t n_instances, int retain_stream, gsv_session** out) {
   gsv_plan_session_opts o{};
   o.retain_stream = retain_stream;
   return gsv_session_create_plan_opts(e, plan, n_instances, &o, out);
 }
-// The call-level schedule of a plan session (schedule.hpp) for `n_wg` workgroups per call on a device with `n_cus` CUs.
-static int install_schedule(gsv_session* s, const gsv_plan_session_opts& o, int n_cus, size_t free_b);
-static Schedule make_schedule(const gsv_plan* plan, uint32_t ni, size_t n_instances, int n_cus, size_t free_bytes, const gsv_plan_session_opts& o, const knobs::Sched& kn, uint64_t* max_call_ct) {
-  std::vector<SchedCall> calls(plan->calls.size());
-  uint64_t max_block = 0;
-  uint32_t max_slots = 0;
-  for (size_t k = 0; k < plan->calls.size(); ++k) {
-    const PlanCall& c = plan->calls[k];
-    const Program& g = c.prog->variant(ni);
-    calls[k].in = c.in_globals.data(); calls[k].n_in = c.in_globals.size();
-    calls[k].out = c.out_globals.data(); calls[k].n_out = c.out_globals.size();
-    calls[k].n_slots = g.n_slots; calls[k].n_ct = g.n_ct; calls[k].n_steps = g.n_steps;
-    max_block = std::max<uint64_t>(max_block, g.n_ct);
-    max_slots = std::max(max_slots, g.n_slots);
-  }
-  *max_call_ct = max_block;
-  SchedParams sp;
-  const size_t n_wg = (n_instances + ni - 1) / ni;
-  // calls side by side: as many as it takes to give every CU a workgroup (GSV_PLAN_CONCURRENCY / opts override)
-  uint32_t conc = o.max_concurrent_calls ? o.max_concurrent_calls : uint32_t(std::max<size_t>(1, size_t(n_cus) / std::max<size_t>(1, n_wg)));
-  if (!o.max_concurrent_calls && kn.plan_concurrency) conc = kn.plan_concurrency;
-  // a session that drains its stream leaves a few CUs to the gather kernels that bring finished segments into gate order beside the
-  // running window (a workgroup of the garbling kernel takes a whole CU, also while it waits for a dependency)
-  if (!o.max_concurrent_calls && o.retain_stream != 1 && conc > 1 && n_wg * size_t(conc) + 16 > size_t(n_cus)) conc = uint32_t(std::max<size_t>(1, (size_t(n_cus) - std::min<size_t>(16, size_t(n_cus) / 2)) / n_wg));
-  sp.max_calls_in_flight = std::min<uint32_t>(conc, 65535u);
-  // the scratch ring: at most ~1/16 of the free device memory over all instances, and 2^30 slots (slot offsets are 32 bits)
-  uint64_t slots = o.max_scratch_slots ? o.max_scratch_slots : uint64_t(free_bytes / 16 / 16 / std::max<size_t>(1, n_instances));
-  sp.max_scratch_slots = std::min<uint64_t>(std::max<uint64_t>(slots, max_slots), 1ull << 30);
-  if (conc == 1) sp.max_scratch_slots = max_slots;
-  // ciphertext window: the whole stream when it is retained, else about a quarter of the free memory for the two window buffers
-  if (o.retain_stream == 1) sp.max_window_ct = ~0ull;
-  else {
-    // Default for sessions that do not retain the stream: the device block (= one window, the scope inside which independent call chains
-    // overlap: schedule.hpp) takes up to 40 % of the free memory, at most 48 GB over all instances (one instance of the verifier, 47.7 GB
-    // of ciphertexts, is ONE window: 26.7 s instead of the 27.6 s of two — profiles/r04_e2e/verifier_mixed_units.log).  The stream leaves the
-    // device in SEGMENTS of a window (below), so a large window costs the drain nothing.  Round 3's default cut one instance's pass into
-    // 2 windows and drained whole windows (48.2 s with the commitment: half of the 27-s CBC-MAC chain uncovered); 46 windows of 1 GB hid
-    // the chain but cost the garbling 4.7 s — the verifier's line-coefficient chain precedes the Miller loop in stream order and only
-    // runs beside it inside one window (29.6 s with 2 windows, 33.4 s with 18, 34.3 s with 46: profiles/r04_e2e/one_instance_windows.log).
-    // (... and at most 48 GB over all instances: device memory that has been freed is scrubbed before it is handed out again, ~25 GB/s,
-    // so a session of 16 instances with a 96-GB block took 6 s to create; its garbling is 3 % faster with 6-GB windows than with 2-GB ones)
-    const double block_bytes = std::min(double(free_bytes) * 0.4, 48e9);
-    uint64_t w = o.window_ct_records ? o.window_ct_records : uint64_t(block_bytes / 16.0 / double(std::max<size_t>(1, n_instances)));
-    if (!o.window_ct_records && conc == 1) w = 0;  // sequential sessions keep the one-call block of rounds 1-2 (smallest footprint)
-    sp.max_window_ct = std::max<uint64_t>(w, max_block);
-  }
-  // Drain segments: at most 64 M records (1 GB) per instance — the serial CBC-MAC chain of a segment takes 0.6 s —, less when three
-  // gate-order buffers of that size would take more than a tenth of the free memory; never smaller than the largest call.
-  {
-    uint64_t sg = o.drain_segment_records ? o.drain_segment_records : std::min<uint64_t>(uint64_t(double(free_bytes) * 0.1 / (3.0 * 16.0) / double(std::max<size_t>(1, n_instances))), 1ull << 26);
-    if (kn.drain_segment_records && !o.drain_segment_records) sg = kn.drain_segment_records;
-    sp.segment_ct = std::min<uint64_t>(std::max<uint64_t>(sg, max_block), sp.max_window_ct);
-  }
-  // Ciphertext ring (schedule.hpp), retain_stream = GSV_STREAM_RING or GSV_CT_RING=1 in the environment: a session that does not
-  // retain the stream and runs calls side by side keeps THREE
-  // segments' worth of ciphertexts on the device instead of a window's, and the window becomes the whole pass (one instance: 48 GB of
-  // device block -> 3.2 GB, 2 windows -> 1; sixteen: 17 windows -> 1 over a 27-GB ring).  Opt-in: with large windows + segments the
-  // pass is already bounded by the dependent depth and the host's MAC chain (tools/ring_ab.py: 30.7 s either way for one instance,
-  // 32.9 s vs 32.5-33.4 s for sixteen), and a ring makes the running launch WAIT for the host — it must never share a hardware queue
-  // with the side streams (create_side_stream).  Not with an explicit window_ct_records (the caller sizes the launches: garble ||
-  // evaluate pairs, tests), not for sequential sessions, and not when the whole stream fits the ring anyway.
-  const bool ring_wanted = o.retain_stream == GSV_STREAM_RING || (o.retain_stream == 0 && kn.ct_ring);
-  if (ring_wanted && !o.window_ct_records && conc > 1) {
-    uint64_t ring = std::max<uint64_t>(3 * sp.segment_ct, 2 * sp.segment_ct + max_block);
-    if (kn.ct_ring_records) ring = std::max<uint64_t>(kn.ct_ring_records, 2 * sp.segment_ct + max_block);  // tests: small rings on small circuits
-    if (ring < plan->n_ct && ring <= sp.max_window_ct) { sp.ring_ct = ring; sp.max_window_ct = ~0ull; }
-  }
-  sp.max_window_calls = std::min<uint32_t>(o.max_window_calls ? o.max_window_calls : 32768u, 65535u);
+static int make_plan_state(gsv_session* s, const gsv_plan_session_opts& o, bool safe, int n_cus, size_t free_b, gsv_session::PlanState* out);
+// The call-level schedule of a plan session (schedule.hpp) under the parameters plan_sched_params chose (plan_layout.hpp).
+static Schedule make_schedule(const std::vector<PlanCallView>& views, const gsv_plan* plan, const SchedParams& sp, const knobs::Sched& kn) {
+  const std::vector<SchedCall> calls = sched_calls(views);
   Schedule sc = schedule_calls(calls, plan->n_globals, plan->outputs, sp);
   {  // always: the O(calls) ring checks (a violation would otherwise show up as a 60 s device stall and status 2)
     const std::string err = verify_ring_bounds(calls, sc);
@@ -120,120 +56,79 @@ int gsv_session_create_plan_opts(gsv_engine* e, const gsv_plan* plan, size_t n_i
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
   s->opts = o;
   {
-    int rc = install_schedule(s.get(), o, prop.multiProcessorCount, free_b);
-    if (rc || (rc = alloc_session_buffers(s.get(), s->facade))) return rc;
+    int rc = make_plan_state(s.get(), o, false, prop.multiProcessorCount, free_b, &s->ps);
+    if (rc || (rc = alloc_session_buffers(s.get(), s->prog()))) return rc;
   }
   *out = s.release();
   return GSV_OK;
 }
-// Everything of a plan session that depends on its SCHEDULE: the schedule itself, the wire-file layout (scratch regions in front of the
-// global wires), the ring's position counter, the completion counters, and the device tables of the window launches (call descriptors,
-// hand-over lists, dependency lists, completion flags).  Called by gsv_session_create_plan_opts and again, with the safe options, by
-// fall_back_to_safe_schedule (after drop_schedule).  A failure leaves what was allocated so far in s->sd: it goes with the session.
-static int install_schedule(gsv_session* s, const gsv_plan_session_opts& o, int n_cus, size_t free_b) {
+// Everything of a plan session that depends on its SCHEDULE, built whole: the layout (plan_layout.hpp: the schedule under `o`, the wire-file
+// layout, the tables of the window launches) and its device half — the tables uploaded, the completion flags, the ring's position counter
+// and the completion counters in mapped host memory.  Built into a local; *out is assigned only on success, so a failure leaves the
+// session as it was.  Called by gsv_session_create_plan_opts and again, with the safe options, by fall_back_to_safe_schedule.
+static int make_plan_state(gsv_session* s, const gsv_plan_session_opts& o, bool safe, int n_cus, size_t free_b, gsv_session::PlanState* out) {
   const gsv_plan* plan = s->plan;
-  const size_t n_instances = s->n_inst;
-  uint64_t max_call_ct = 0;
+  const size_t n = plan->calls.size();
   const knobs::Sched kn;
+  gsv_session::PlanState st;
   GSV_TRY
-  s->sched = make_schedule(plan, s->ni, n_instances, n_cus, free_b, o, kn, &max_call_ct);
+  std::vector<PlanCallView> views(n);
+  uint64_t max_block = 0;
+  uint32_t max_slots = 0;
+  for (size_t k = 0; k < n; ++k) {
+    const PlanCall& c = plan->calls[k];
+    PlanCallView& v = views[k];
+    v.prog = &s->call_prog(k);
+    v.in_globals = PlanCallView::ids(c.in_globals); v.out_globals = PlanCallView::ids(c.out_globals);
+    v.gid_off = c.gid_off; v.ct_off = c.ct_off;
+    v.steps = s->call_dev[k]->steps.get(); v.ands = s->call_dev[k]->ands.get(); v.xors = s->call_dev[k]->xors.get();
+    max_block = std::max<uint64_t>(max_block, v.prog->n_ct);
+    max_slots = std::max(max_slots, v.prog->n_slots);
+  }
+  const SchedParams sp = plan_sched_params(o, s->n_inst, s->ni, n_cus, free_b, kn, plan->n_ct, max_block, max_slots);
+  const std::string err = build_plan_layout(views, plan->n_globals, plan->n_inputs, plan->outputs, plan->n_gates, plan->n_ct, make_schedule(views, plan, sp, kn), o.retain_stream == 1, safe,
+                                            kn.fault_withhold_dep, &st.L);
+  if (!err.empty()) return fail(GSV_ERR_CIRCUIT, err);
   GSV_CATCH
-  const Schedule& sc = s->sched;
-  const uint32_t scratch = uint32_t((std::max<uint64_t>(sc.scratch_slots, SLOT_FIRST_INPUT) + 7) / 8 * 8);
-  s->global_base = scratch;
-  s->plan_retain = o.retain_stream == 1;
-  s->ct_ring = sc.ring_ct != 0;
-  s->plan_max_block = s->ct_ring ? sc.ring_ct : sc.max_window_ct;
-  s->plan_max_segment = sc.max_segment_ct;
-  gsv_session::ScheduleState& sd = s->sd;
-  if (s->ct_ring) {
-    HIPCHK(sd.ct_pos.alloc(64, hipHostMallocMapped | hipHostMallocCoherent));
-    *sd.ct_pos.get() = 0;
+  PlanLayout& L = st.L;
+  if (L.ring) {
+    HIPCHK(st.ct_pos.alloc(64, hipHostMallocMapped | hipHostMallocCoherent));
+    *st.ct_pos.get() = 0;
   }
-  if (uint64_t(scratch) + plan->n_globals > 0xFFFFFFF0ull) return fail(GSV_ERR_CIRCUIT, "plan wire file too large");
-  Program& f = s->facade;
-  f = Program();
-  f.n_slots = scratch + plan->n_globals;
-  f.n_gates = plan->n_gates; f.n_ct = plan->n_ct;
-  for (uint32_t i = 0; i < plan->n_inputs; ++i) f.input_slots.push_back(scratch + i);
-  auto global_slot = [&](uint32_t w) -> uint32_t { return w == PLAN_WIRE_FALSE ? SLOT_FALSE : w == PLAN_WIRE_TRUE ? SLOT_TRUE : scratch + w; };
-  for (uint32_t w : plan->outputs) f.output_slots.push_back(global_slot(w));
+  // the device-written completion counters (one per call of the PLAN: windows enqueued back to back never share a counter), in mapped host memory
+  HIPCHK(st.done.alloc(n * 4 + 64, hipHostMallocMapped | hipHostMallocCoherent));
+  std::memset(st.done.get(), 0, n * 4 + 64);
+  for (size_t k = 0; k < n; ++k) { L.calls[k].ct_pos = st.ct_pos.dev(); L.calls[k].done_host = st.done.dev() + k; }
   auto up = [&](DevBuf& dst, const void* src, size_t bytes) -> int { return upload_padded(dst, src, bytes, 64, false); };
-  // descriptors, wire hand-over lists and dependency lists, all in stream order
-  {
-    const size_t n = plan->calls.size();
-    std::vector<dev::CallDesc> cds(n);
-    std::vector<uint32_t> csrc, cdst, deps;
-    {
-      // the device-written completion counters (one per call of the PLAN: windows enqueued back to back never share a counter), in mapped host memory
-      HIPCHK(sd.done.alloc(n * 4 + 64, hipHostMallocMapped | hipHostMallocCoherent));
-      std::memset(sd.done.get(), 0, n * 4 + 64);
-    }
-    for (const Schedule::Window& w : sc.windows) {
-      for (uint32_t k = w.call0; k < w.call1; ++k) {
-        const PlanCall& c = plan->calls[k];
-        const Program& g = s->call_prog(k);
-        const uint32_t base = sc.scratch_base[k];
-        dev::CallDesc& d = cds[k];
-        std::memset(&d, 0, sizeof d);
-        d.steps = s->call_dev[k]->steps.get(); d.ands = s->call_dev[k]->ands.get(); d.xors = s->call_dev[k]->xors.get();
-        d.gid_off = c.gid_off; d.ct_off = s->plan_retain ? c.ct_off : s->ct_ring ? sc.ring_off[k] : c.ct_off - w.ct0;
-        if (s->ct_ring) { d.ct_need = sc.ring_need[k]; d.ct_ready = sc.seg_end[k]; d.ct_pos = sd.ct_pos.dev(); }
-        d.done_host = sd.done.dev() + k;
-        d.w_base = base; d.n_steps = g.n_steps; d.and_terms = g.and_terms;
-        d.pre_off = uint32_t(csrc.size());
-        if (base != 0)  // the call's own copies of the constant labels (FALSE, TRUE, the all-zero label) in front of its scratch region
-          for (uint32_t q = 0; q < SLOT_FIRST_INPUT; ++q) { csrc.push_back(q); cdst.push_back(base + q); }
-        for (size_t i = 0; i < c.in_globals.size(); ++i) { csrc.push_back(global_slot(c.in_globals[i])); cdst.push_back(base + g.input_slots[i]); }
-        d.n_pre = uint32_t(csrc.size()) - d.pre_off;
-        d.post_off = uint32_t(csrc.size());
-        for (size_t i = 0; i < c.out_globals.size(); ++i) {
-          if (g.output_slots[i] & SLOT_LDS_FLAG) return fail(GSV_ERR_CIRCUIT, "internal: a program output lives in the LDS window");
-          csrc.push_back(base + g.output_slots[i]); cdst.push_back(scratch + c.out_globals[i]);
-        }
-        d.n_post = uint32_t(csrc.size()) - d.post_off;
-        d.dep_off = uint32_t(deps.size());
-        for (uint32_t q = sc.dep_off[k]; q < sc.dep_off[k + 1]; ++q) deps.push_back(sc.deps[q] - w.call0);
-        d.n_deps = uint32_t(deps.size()) - d.dep_off;
-        if (csrc.size() > 0xFFFFFF00ull) return fail(GSV_ERR_CIRCUIT, "plan hand-over lists too large");
-      }
-      sd.flag_stride = std::max<uint32_t>(sd.flag_stride, w.call1 - w.call0 + 2);  // + a slot nobody writes (fault injection below) + the group's progress counter (kernels.hip, watchdog)
-    }
-    // GSV_FAULT_WITHHOLD_DEP=1 (tests): the first dependency of the first call that has one is pointed at the slot nobody writes — on
-    // the device exactly what a violated dispatch-order assumption looks like (a dependency that never completes).  Never for the safe schedule.
-    if (!s->safe_mode && kn.fault_withhold_dep)
-      for (size_t k = 0; k < n; ++k) if (cds[k].n_deps) { deps[cds[k].dep_off] = sd.flag_stride - 2; break; }
-    // one flag row per instance: the rows are indexed by blockIdx.x, and a session switched to BLAKE3 after its creation launches one
-    // workgroup per instance whatever s->ni says (gsv_session::launch_ni) — flag_stride * 4 bytes per instance
-    const size_t n_rows = n_instances;
-    int rc;
-    if ((rc = up(sd.d_calls, cds.data(), cds.size() * sizeof(dev::CallDesc))) || (rc = up(sd.d_copy_src, csrc.data(), csrc.size() * 4)) || (rc = up(sd.d_copy_dst, cdst.data(), cdst.size() * 4)) ||
-        (rc = up(sd.d_deps, deps.data(), deps.size() * 4)))
-      return rc;
-    HIPCHK(sd.d_flags.alloc(n_rows * size_t(sd.flag_stride) * 4 + 64));
-    HIPCHK(hipMemset(sd.d_flags.get(), 0, sd.d_flags.bytes()));
-    HIPCHK(sd.d_error.alloc(64));
-    HIPCHK(hipMemset(sd.d_error.get(), 0, 64));
-    if ((rc = up(sd.plan_out_slots, f.output_slots.data(), f.output_slots.size() * 4))) return rc;
-  }
+  // one flag row per instance: the rows are indexed by blockIdx.x, and a session switched to BLAKE3 after its creation launches one
+  // workgroup per instance whatever s->ni says (gsv_session::launch_ni) — flag_stride * 4 bytes per instance
+  const size_t n_rows = s->n_inst;
+  int rc;
+  if ((rc = up(st.d_calls, L.calls.data(), L.calls.size() * sizeof(dev::CallDesc))) || (rc = up(st.d_copy_src, L.copy_src.data(), L.copy_src.size() * 4)) ||
+      (rc = up(st.d_copy_dst, L.copy_dst.data(), L.copy_dst.size() * 4)) || (rc = up(st.d_deps, L.deps.data(), L.deps.size() * 4)))
+    return rc;
+  HIPCHK(st.d_flags.alloc(n_rows * size_t(L.flag_stride) * 4 + 64));
+  HIPCHK(hipMemset(st.d_flags.get(), 0, st.d_flags.bytes()));
+  HIPCHK(st.d_error.alloc(64));
+  HIPCHK(hipMemset(st.d_error.get(), 0, 64));
+  if ((rc = up(st.plan_out_slots, L.facade.output_slots.data(), L.facade.output_slots.size() * 4))) return rc;
+  *out = std::move(st);
   return GSV_OK;
 }
-// the schedule-dependent state of a session, released (the caller has synchronised the device's streams)
-static void drop_schedule(gsv_session* s) { s->sd = gsv_session::ScheduleState(); s->next_call = 0; }
 int gsv_session_plan_schedule_info(const gsv_session* s, gsv_plan_schedule_info* info) {
   if (!s || !s->plan || !info) return fail(GSV_ERR_INVALID, "null argument / not a plan session");
-  const Schedule& sc = s->sched;
+  const Schedule& sc = s->sched();
   info->n_calls = s->plan->calls.size(); info->n_windows = sc.windows.size(); info->n_dependencies = sc.deps.size();
   info->max_width = sc.max_width;
-  info->scratch_slots = s->global_base; info->wire_file_slots = s->facade.n_slots; info->window_ct_records = sc.max_window_ct;
+  info->scratch_slots = s->ps.L.global_base; info->wire_file_slots = s->prog().n_slots; info->window_ct_records = sc.max_window_ct;
   info->critical_steps = sc.critical_steps; info->total_steps = sc.total_steps;
   info->n_segments = sc.segments.size(); info->segment_ct_records = sc.max_segment_ct;
   info->ct_ring_records = sc.ring_ct;
   return GSV_OK;
 }
 int gsv_session_plan_window(const gsv_session* s, uint64_t window, uint64_t* first_call, uint64_t* n_calls, uint64_t* max_width) {
-  if (!s || !s->plan || window >= s->sched.windows.size()) return fail(GSV_ERR_INVALID, "null argument / window index out of range");
-  const Schedule::Window& w = s->sched.windows[size_t(window)];
+  if (!s || !s->plan || window >= s->sched().windows.size()) return fail(GSV_ERR_INVALID, "null argument / window index out of range");
+  const Schedule::Window& w = s->sched().windows[size_t(window)];
   if (first_call) *first_call = w.call0;
   if (n_calls) *n_calls = w.call1 - w.call0;
   if (max_width) *max_width = w.max_width;
@@ -252,13 +147,14 @@ int gsv_session_set_unchecked_slices(gsv_session* s, int on) {
 
 static int stage_labels(gsv_session* s, const uint8_t* consts, const uint8_t* inputs) {
   // Per instance the wire file starts [FALSE, TRUE, ZERO, input0, input1, ...]: one strided copy.
+  if (int rc = plan_session_usable(s)) return rc;
   const Program& g = s->prog();
   const size_t n_in = g.input_slots.size();
   if (s->plan) {  // constants at slots 0..2, inputs at the head of the global region: two strided copies
     std::vector<uint8_t> host(s->n_inst * 48, 0);
     for (size_t i = 0; i < s->n_inst; ++i) std::memcpy(&host[i * 48], consts + 32 * i, 32);
     HIPCHK(hipMemcpy2D(s->W.get(), size_t(g.n_slots) * 16, host.data(), 48, 48, s->n_inst, hipMemcpyHostToDevice));
-    if (n_in) HIPCHK(hipMemcpy2D(static_cast<uint8_t*>(s->W.get()) + size_t(s->global_base) * 16, size_t(g.n_slots) * 16, inputs, n_in * 16, n_in * 16, s->n_inst, hipMemcpyHostToDevice));
+    if (n_in) HIPCHK(hipMemcpy2D(static_cast<uint8_t*>(s->W.get()) + size_t(s->ps.L.global_base) * 16, size_t(g.n_slots) * 16, inputs, n_in * 16, n_in * 16, s->n_inst, hipMemcpyHostToDevice));
     return GSV_OK;
   }
   const size_t row = (SLOT_FIRST_INPUT + n_in) * 16;
@@ -379,6 +275,7 @@ static dev::KernelArgs session_kernel_args(const gsv_session* s, void* ct_block,
   return ka;
 }
 static int launch(gsv_session* s, uint64_t gate_id_base, bool eval, uint64_t rep_base = 0, uint64_t n_replays = 0) {
+  if (int rc = plan_session_usable(s)) return rc;
   if (s->plan) return launch_plan(s, gate_id_base, eval);
   const Program& g = s->prog();
   HIPCHK(hipSetDevice(s->e->device));
@@ -409,10 +306,10 @@ static int launch(gsv_session* s, uint64_t gate_id_base, bool eval, uint64_t rep
 // and publishes its outputs (kernels.hip).  A sequential schedule (one call in flight) is the same launch with each call depending on
 // its predecessor: the instance groups still drift apart instead of meeting at a launch boundary after every call.
 static int launch_plan_window(gsv_session* s, size_t w, uint64_t gate_id_base, bool eval, void* ct_block = nullptr, hipStream_t stream = nullptr) {
-  const gsv_session::ScheduleState& sd = s->sd;
+  const gsv_session::PlanState& sd = s->ps;
   if (!ct_block) ct_block = s->CT.get();       // (garble -> evaluate: the garbler's current block, for both sessions)
   if (!stream) stream = s->e->stream.get();
-  const Schedule::Window& win = s->sched.windows[w];
+  const Schedule::Window& win = s->sched().windows[w];
   dev::KernelArgs ka = session_kernel_args(s, ct_block, gate_id_base);
   ka.calls = sd.d_calls.as<const dev::CallDesc>() + win.call0;
   ka.copy_src = sd.d_copy_src.as<const uint32_t>(); ka.copy_dst = sd.d_copy_dst.as<const uint32_t>();
@@ -421,7 +318,7 @@ static int launch_plan_window(gsv_session* s, size_t w, uint64_t gate_id_base, b
     std::memset(sd.done.get() + win.call0, 0, size_t(win.call1 - win.call0) * 4);
     __atomic_thread_fence(__ATOMIC_RELEASE);
   }
-  ka.flag_stride = sd.flag_stride; ka.epoch = ++s->epoch;
+  ka.flag_stride = sd.L.flag_stride; ka.epoch = ++s->epoch;
   ka.wait_ticks = (unsigned long long)(s->pass.dep_wait_seconds * 1e8);  // dependency watchdog (kernels.hip): seconds without ANY completed call of the instance group before a wait gives up
   ka.replays = 1; ka.ct_cap_replays = 1;  // (n_gates, n_ct, n_steps, rep_base: 0 — the calls' descriptors carry their own)
   for (uint32_t k = win.call0; k < win.call1 && !ka.any_four_wire; ++k) ka.any_four_wire = s->call_prog(k).and_terms == 4;
@@ -438,31 +335,31 @@ int gsv_session_windows_launched(const gsv_session* s, uint64_t* n) {
 // after a synchronisation: did a dependency wait give up?
 static int check_plan_error(gsv_session* s) {
   uint32_t ew[16] = {0};
-  HIPCHK(hipMemcpy(ew, s->sd.d_error.get(), 64, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ew, s->ps.d_error.get(), 64, hipMemcpyDeviceToHost));
   const uint32_t err = ew[0];
+  s->dep_fault = err == 1;
   if (err == 2) {
     // which calls of the last window have not finished everywhere, and where the host's position stood (diagnostics)
     std::string open_calls;
-    if (s->sd.done.get() && !s->sched.windows.empty()) {
+    if (s->ps.done.get() && !s->sched().windows.empty()) {
       const uint32_t n_wg = uint32_t(s->launch_groups());
-      const Schedule::Window& win = s->sched.windows.back();
+      const Schedule::Window& win = s->sched().windows.back();
       int shown = 0;
       for (uint32_t k = win.call0; k < win.call1 && shown < 12; ++k)
-        if (s->sd.done.get()[k] != n_wg) { open_calls += " " + std::to_string(k) + "(" + std::to_string(s->sd.done.get()[k]) + "/" + std::to_string(n_wg) + ", need " + std::to_string(s->sched.ring_need[k]) + ")"; ++shown; }
+        if (s->ps.done.get()[k] != n_wg) { open_calls += " " + std::to_string(k) + "(" + std::to_string(s->ps.done.get()[k]) + "/" + std::to_string(n_wg) + ", need " + std::to_string(s->sched().ring_need[k]) + ")"; ++shown; }
     }
-    return fail(GSV_ERR_DEVICE, "a call waited for the host's stream position (ciphertext ring) and saw it stand still at " + std::to_string(s->sd.ct_pos.get() ? *s->sd.ct_pos.get() : 0) +
+    return fail(GSV_ERR_DEVICE, "a call waited for the host's stream position (ciphertext ring) and saw it stand still at " + std::to_string(s->ps.ct_pos.get() ? *s->ps.ct_pos.get() : 0) +
                                     "; unfinished calls:" + open_calls + "; the call that gave up: " + std::to_string(ew[8]) + " of the window (instance group " + std::to_string(ew[9]) + "), it wanted position " +
                                     std::to_string((uint64_t(ew[11]) << 32) | ew[10]) + ", saw " + std::to_string((uint64_t(ew[13]) << 32) | ew[12]) + " unchanged for " +
                                     std::to_string(double((uint64_t(ew[15]) << 32) | ew[14]) * 1e-8) + " s" + (s->ring_diag.empty() ? "" : "; host: " + s->ring_diag) + "; results are invalid");
   }
-  s->dep_fault = err == 1;
   if (err) return fail(GSV_ERR_DEVICE, "a call of the plan waited for a dependency that never completed (dispatch-order assumption of schedule.hpp violated); results are invalid");
   return GSV_OK;
 }
 // Gate order <-> program order for calls [k0, k1) of window w (a drain segment, or the whole window): gate-order buffer, records
 // relative to `gate_ct0` (the stream index of the buffer's first record) <-> the window's device block.
 static int permute_plan_calls(gsv_session* s, size_t w, uint32_t k0, uint32_t k1, uint64_t gate_ct0, uint64_t gate_stride, int scatter, void* ct_block, void* gate_buf, hipStream_t stream) {
-  const Schedule::Window& win = s->sched.windows[w];
+  const Schedule::Window& win = s->sched().windows[w];
   if (!ct_block) ct_block = s->CT.get();
   if (!gate_buf) gate_buf = s->ct_gate.get();
   if (!stream) stream = s->e->stream.get();
@@ -470,7 +367,7 @@ static int permute_plan_calls(gsv_session* s, size_t w, uint32_t k0, uint32_t k1
     const Program& cp = s->call_prog(k);
     if (!cp.n_ct) continue;
     const uint64_t rel = s->plan->calls[k].ct_off - win.ct0;
-    uint8_t* block = static_cast<uint8_t*>(ct_block) + (s->plan_retain ? s->plan->calls[k].ct_off : s->ct_ring ? s->sched.ring_off[k] : rel) * 16;
+    uint8_t* block = static_cast<uint8_t*>(ct_block) + (s->retain() ? s->plan->calls[k].ct_off : s->ring() ? s->sched().ring_off[k] : rel) * 16;
     const size_t n_gather = (!scatter && s->drain_instances) ? std::min(s->drain_instances, s->n_inst) : s->n_inst;  // gsv_session_set_drain_instances
     if (gsvk_gather_segment(block, s->ct_stride(), s->call_dev[k]->ct_pos.as<const uint32_t>(), cp.n_ct, 1, uint32_t(n_gather), static_cast<uint8_t*>(gate_buf) + (s->plan->calls[k].ct_off - gate_ct0) * 16, gate_stride, scatter, stream) != 0)
       return fail(GSV_ERR_DEVICE, scatter ? "ciphertext scatter launch failed" : "ciphertext gather launch failed");
@@ -479,7 +376,7 @@ static int permute_plan_calls(gsv_session* s, size_t w, uint32_t k0, uint32_t k1
 }
 // windows [w0, w1) that cover exactly the calls [c0, c1), or an error: a slice of a plan starts and ends on window boundaries
 static int window_range(const gsv_session* s, size_t c0, size_t c1, size_t* w0, size_t* w1) {
-  const auto& ws = s->sched.windows;
+  const auto& ws = s->sched().windows;
   size_t a = 0;
   while (a < ws.size() && ws[a].call0 < c0) ++a;
   size_t b = a;
@@ -491,21 +388,21 @@ static int window_range(const gsv_session* s, size_t c0, size_t c1, size_t* w0, 
   return GSV_OK;
 }
 static int gather_plan_outputs(gsv_session* s, bool eval) {
-  const Program& f = s->facade;
+  const Program& f = s->prog();
   if (!f.output_slots.empty()) {
-    if (gsvk_gather_outputs(s->W.get(), s->VB.get(), f.n_slots, s->sd.plan_out_slots.as<const uint32_t>(), uint32_t(f.output_slots.size()), uint32_t(s->n_inst), s->out.get(),
+    if (gsvk_gather_outputs(s->W.get(), s->VB.get(), f.n_slots, s->ps.plan_out_slots.as<const uint32_t>(), uint32_t(f.output_slots.size()), uint32_t(s->n_inst), s->out.get(),
                             eval ? s->out_bits.get() : nullptr, s->e->stream.get()) != 0) return fail(GSV_ERR_DEVICE, "gather launch failed");
   }
   s->ran = true; s->last_eval = eval;
   return GSV_OK;
 }
 static int launch_plan(gsv_session* s, uint64_t gate_id_base, bool eval) {
-  if (!s->plan_retain) return fail(GSV_ERR_INVALID, "this plan session keeps one window of ciphertexts only: use gsv_session_garble_streaming");
+  if (!s->retain()) return fail(GSV_ERR_INVALID, "this plan session keeps one window of ciphertexts only: use gsv_session_garble_streaming");
   HIPCHK(hipSetDevice(s->e->device));
-  HIPCHK(hipMemsetAsync(s->sd.d_error.get(), 0, 4, s->e->stream.get()));  // every pass starts with a clean dependency-wait flag
+  HIPCHK(hipMemsetAsync(s->ps.d_error.get(), 0, 4, s->e->stream.get()));  // every pass starts with a clean dependency-wait flag
   HIPCHK(hipEventRecord(s->ev0.get(), s->e->stream.get()));
   s->windows_launched = 0;
-  for (size_t w = 0; w < s->sched.windows.size(); ++w) {
+  for (size_t w = 0; w < s->sched().windows.size(); ++w) {
     int rc = launch_plan_window(s, w, gate_id_base, eval);
     if (rc) return rc;
   }

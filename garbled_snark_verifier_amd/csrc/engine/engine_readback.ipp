@@ -84,7 +84,7 @@ int gsv_session_read_outputs(gsv_session* s, uint8_t* labels, uint8_t* bits) {
 }
 int gsv_session_read_ciphertexts(gsv_session* s, size_t instance, uint64_t first, uint64_t n_records, uint8_t* out) {
   if (!s || instance >= s->n_inst || (!out && n_records)) return fail(GSV_ERR_INVALID, "bad argument");
-  if (s->plan && !s->plan_retain) return fail(GSV_ERR_INVALID, "this plan session does not retain the ciphertext stream");
+  if (s->plan && !s->retain()) return fail(GSV_ERR_INVALID, "this plan session does not retain the ciphertext stream");
   if (first + n_records > s->ct_stride()) return fail(GSV_ERR_INVALID, "range exceeds the retained ciphertext stream");
   HIPCHK(hipSetDevice(s->e->device));
   HIPCHK(hipStreamSynchronize(s->e->stream.get()));
@@ -97,7 +97,7 @@ int gsv_session_read_ciphertexts(gsv_session* s, size_t instance, uint64_t first
 }
 int gsv_session_ciphertext_hash(gsv_session* s, size_t instance, uint8_t hash[16]) {
   if (!s || instance >= s->n_inst || !hash) return fail(GSV_ERR_INVALID, "bad argument");
-  if (s->ct_cap != s->replays || (s->plan && !s->plan_retain)) return fail(GSV_ERR_INVALID, "the session retains only part of the stream (ct_capacity_replays < replays)");
+  if (s->ct_cap != s->replays || (s->plan && !s->retain())) return fail(GSV_ERR_INVALID, "the session retains only part of the stream (ct_capacity_replays < replays)");
   HIPCHK(hipSetDevice(s->e->device));
   HIPCHK(hipStreamSynchronize(s->e->stream.get()));
   const uint64_t total = s->ct_stride();
@@ -119,7 +119,7 @@ int gsv_session_ciphertext_hash(gsv_session* s, size_t instance, uint8_t hash[16
 int gsv_session_ciphertext_blake3(gsv_session* s, uint8_t* digests) {
   if (!s || !digests) return fail(GSV_ERR_INVALID, "null argument");
   const knobs::ResidentB3 kn;
-  if (s->ct_cap != s->replays || (s->plan && !s->plan_retain)) return fail(GSV_ERR_INVALID, "the session retains only part of the stream (ct_capacity_replays < replays)");
+  if (s->ct_cap != s->replays || (s->plan && !s->retain())) return fail(GSV_ERR_INVALID, "the session retains only part of the stream (ct_capacity_replays < replays)");
   const uint64_t total = s->ct_stride();
   if (int rc = check_resident_stream(s, total)) return rc;
   HIPCHK(hipSetDevice(s->e->device));

@@ -59,20 +59,19 @@ static int upload_program(gsv_engine* e, gsv_program* p, uint32_t ni, const DevP
 }
 // The per-instance buffers and the two timing events of a session whose wire file and outputs are those of `g` (the program, or a plan
 // session's facade).  Called again after a second schedule was installed (fall_back_to_safe_schedule): the wire files and the
-// ciphertext block are then re-allocated only where the new schedule needs more, the rest exists.  VB is cleared either way.
+// ciphertext block are then re-allocated only where the new schedule needs more (released first: the peak does not double), the rest
+// exists.  VB is cleared either way.
 static int alloc_session_buffers(gsv_session* s, const Program& g) {
   const size_t n = s->n_inst;
-  if (!s->W || g.n_slots > s->w_slots_cap) {
+  if (!s->W || !s->VB || s->W.bytes() < n * size_t(g.n_slots) * 16) {
     s->W.reset(); s->VB.reset();
     DEVALLOC(s->W, n * size_t(g.n_slots) * 16, "the wire files");
     HIPCHK(s->VB.alloc(n * size_t(g.n_slots)));
-    s->w_slots_cap = g.n_slots;
   }
   HIPCHK(hipMemset(s->VB.get(), 0, n * size_t(g.n_slots)));
-  if (!s->CT || s->ct_stride() > s->ct_records_cap) {
+  if (!s->CT || s->CT.bytes() < n * size_t(s->ct_stride()) * 16) {
     s->CT.reset(); s->ct_alt.reset();
     DEVALLOC(s->CT, n * size_t(s->ct_stride()) * 16, "the ciphertext blocks");
-    s->ct_records_cap = s->ct_stride();
   }
   if (s->delta) return GSV_OK;
   HIPCHK(s->delta.alloc(n * 16));

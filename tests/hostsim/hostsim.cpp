@@ -15,6 +15,7 @@
 #include "../../garbled_snark_verifier_amd/csrc/engine/host_crypto.hpp"
 #include "../../garbled_snark_verifier_amd/csrc/engine/knobs.hpp"
 #include "../../garbled_snark_verifier_amd/csrc/engine/plan_builder.hpp"
+#include "../../garbled_snark_verifier_amd/csrc/engine/plan_layout.hpp"
 #include "../../garbled_snark_verifier_amd/csrc/engine/program.hpp"
 #include "../../garbled_snark_verifier_amd/csrc/engine/schedule.hpp"
 #include "../../garbled_snark_verifier_amd/csrc/gadgets/circuits.hpp"
@@ -222,9 +223,18 @@ int hostsim_run(SimProgram* sp, int evaluate, uint32_t replays, uint64_t gid_bas
 struct SimPlan {
   BuiltPlan bp;
   uint64_t n_ct = 0;
-  Schedule sched;        // hostsim_plan_schedule: the engine's call-level schedule (schedule.hpp); empty = stream order
+  std::vector<PlanCallView> views;  // hostsim_plan_schedule: what the engine's tables are built from (plan_layout.hpp)
+  PlanLayout lay;                   // ... and those tables, over the engine's call-level schedule (schedule.hpp); not scheduled = stream order
   bool scheduled = false;
 };
+static uint32_t plan_n_globals(const BuiltPlan& bp) {
+  uint32_t n_globals = bp.n_inputs;
+  for (auto& c : bp.calls) {
+    for (uint32_t w : c.in_globals) if (w < PLAN_WIRE_FALSE) n_globals = std::max(n_globals, w + 1);
+    for (uint32_t w : c.out_globals) n_globals = std::max(n_globals, w + 1);
+  }
+  return n_globals;
+}
 int hostsim_plan_build(const char* spec, const char* units_csv, SimPlan** out, uint64_t* info /* 8: n_inputs n_outputs n_gates n_ct n_calls n_programs n_globals n_unit_programs */) {
   try {
     std::vector<std::string> names;
@@ -245,12 +255,8 @@ int hostsim_plan_build(const char* spec, const char* units_csv, SimPlan** out, u
     const size_t n_units = mode.units.size();
     sp->bp = finish_plan(mode, in_ssa, out_ssa, opt, kn);
     if (sp->bp.n_gates != mode.n_gates()) gsv_panic("plan gate count differs from the recorded stream");
-    uint32_t n_globals = sp->bp.n_inputs;
-    for (auto& c : sp->bp.calls) {
-      sp->n_ct += sp->bp.programs[size_t(c.program)].n_ct;
-      for (uint32_t w : c.in_globals) if (w < PLAN_WIRE_FALSE) n_globals = std::max(n_globals, w + 1);
-      for (uint32_t w : c.out_globals) n_globals = std::max(n_globals, w + 1);
-    }
+    for (auto& c : sp->bp.calls) sp->n_ct += sp->bp.programs[size_t(c.program)].n_ct;
+    const uint32_t n_globals = plan_n_globals(sp->bp);
     if (info) {
       info[0] = sp->bp.n_inputs; info[1] = sp->bp.outputs.size(); info[2] = sp->bp.n_gates; info[3] = sp->n_ct; info[4] = sp->bp.calls.size();
       info[5] = sp->bp.programs.size(); info[6] = n_globals; info[7] = n_units;
@@ -260,79 +266,93 @@ int hostsim_plan_build(const char* spec, const char* units_csv, SimPlan** out, u
   } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }
 void hostsim_plan_free(SimPlan* p) { delete p; }
-static uint32_t plan_n_globals(const BuiltPlan& bp) {
-  uint32_t n_globals = bp.n_inputs;
-  for (auto& c : bp.calls) {
-    for (uint32_t w : c.in_globals) if (w < PLAN_WIRE_FALSE) n_globals = std::max(n_globals, w + 1);
-    for (uint32_t w : c.out_globals) n_globals = std::max(n_globals, w + 1);
-  }
-  return n_globals;
-}
-// The engine's scheduler (schedule.hpp, the very code engine.cpp runs at session creation) over this plan; the schedule is checked by
-// brute force (every hazard and every scratch overlap covered by a dependency path) and kept: hostsim_plan_run then executes it the
-// way the device may — window by window, inside a window ANY order the dependencies allow: here always the ready call with the
-// LARGEST stream index, all calls in one shared scratch ring.  info: n_windows n_dependencies max_width scratch_slots
-// critical_steps total_steps max_window_ct.
+// The engine's scheduler (schedule.hpp) and table builder (plan_layout.hpp: the very code engine.cpp runs at session creation) over this
+// plan; the schedule is checked by brute force (every hazard and every scratch overlap covered by a dependency path) and its layout
+// kept: hostsim_plan_run then executes the engine's own tables the way the device may — window by window, inside a window ANY order
+// the dependency lists allow: here always the ready call with the LARGEST stream index, all calls in one wire file.  retain / safe /
+// withhold_first_dep: build_plan_layout's.  info: n_windows n_dependencies max_width scratch_slots critical_steps total_steps max_window_ct.
 static uint64_t g_segment_ct = 0, g_ring_ct = 0;  // hostsim_set_segment_ct / _ring_ct: SchedParams::segment_ct / ring_ct of the next hostsim_plan_schedule
 void hostsim_set_segment_ct(uint64_t v) { g_segment_ct = v; }
 void hostsim_set_ring_ct(uint64_t v) { g_ring_ct = v; }
 // ring tables of the last schedule: per call {ring_off, ring_need, seg_end, ovl0, ovl1}
 uint64_t hostsim_plan_ring(SimPlan* sp, uint64_t* out, uint64_t cap) {
-  const Schedule& sc = sp->sched;
+  const Schedule& sc = sp->lay.sched;
   if (!sc.ring_ct) return 0;
   for (size_t k = 0; k < sc.ring_off.size() && out && k < cap; ++k) { out[5 * k] = sc.ring_off[k]; out[5 * k + 1] = sc.ring_need[k]; out[5 * k + 2] = sc.seg_end[k]; out[5 * k + 3] = sc.ovl0[k]; out[5 * k + 4] = sc.ovl1[k]; }
   return sc.ring_off.size();
 }
 // The drain segments of the last schedule: per segment {window, call0, call1, ct0, n_ct}; returns their number (out may be NULL).
 uint64_t hostsim_plan_segments(SimPlan* sp, uint64_t* out, uint64_t cap) {
-  const Schedule& sc = sp->sched;
+  const Schedule& sc = sp->lay.sched;
   uint64_t n = 0;
   for (size_t w = 0; w < sc.windows.size(); ++w)
     for (uint32_t q = sc.windows[w].seg0; q < sc.windows[w].seg1; ++q, ++n)
       if (out && n < cap) { out[5 * n] = w; out[5 * n + 1] = sc.segments[q].call0; out[5 * n + 2] = sc.segments[q].call1; out[5 * n + 3] = sc.segments[q].ct0; out[5 * n + 4] = sc.segments[q].n_ct; }
   return n;
 }
-int hostsim_plan_schedule(SimPlan* sp, uint32_t max_calls, uint64_t max_slots, uint64_t window_ct, uint32_t window_calls, uint64_t* info /* 7 */) {
+int hostsim_plan_schedule(SimPlan* sp, uint32_t max_calls, uint64_t max_slots, uint64_t window_ct, uint32_t window_calls, int retain, int safe, int withhold_first_dep, uint64_t* info /* 7 */) {
   try {
     const BuiltPlan& bp = sp->bp;
-    std::vector<SchedCall> calls(bp.calls.size());
+    std::vector<PlanCallView> views(bp.calls.size());
+    uint64_t gid = 0, ct = 0;
     for (size_t k = 0; k < bp.calls.size(); ++k) {
       const BuiltPlan::Call& c = bp.calls[k];
-      const Program& g = bp.programs[size_t(c.program)];
-      calls[k].in = c.in_globals.data(); calls[k].n_in = c.in_globals.size();
-      calls[k].out = c.out_globals.data(); calls[k].n_out = c.out_globals.size();
-      calls[k].n_slots = g.n_slots; calls[k].n_ct = g.n_ct; calls[k].n_steps = g.n_steps;
+      views[k].prog = &bp.programs[size_t(c.program)];
+      views[k].in_globals = PlanCallView::ids(c.in_globals); views[k].out_globals = PlanCallView::ids(c.out_globals);
+      views[k].gid_off = gid; views[k].ct_off = ct;
+      gid += views[k].prog->n_gates; ct += views[k].prog->n_ct;
     }
+    const std::vector<SchedCall> calls = sched_calls(views);
     SchedParams p;
     p.max_calls_in_flight = max_calls; p.max_scratch_slots = max_slots ? max_slots : ~0ull; p.max_window_ct = window_ct ? window_ct : ~0ull;
     p.max_window_calls = window_calls ? window_calls : 32768;
     p.segment_ct = g_segment_ct;
     p.ring_ct = g_ring_ct;
     const uint32_t n_ids = plan_n_globals(bp);
-    sp->sched = schedule_calls(calls, n_ids, bp.outputs, p);
-    const std::string err = verify_schedule(calls, n_ids, bp.outputs, sp->sched);
+    Schedule sc = schedule_calls(calls, n_ids, bp.outputs, p);
+    std::string err = verify_schedule(calls, n_ids, bp.outputs, sc);
     if (!err.empty()) gsv_panic("schedule violates a hazard: " + err);
+    err = build_plan_layout(views, n_ids, bp.n_inputs, bp.outputs, bp.n_gates, sp->n_ct, std::move(sc), retain != 0, safe != 0, withhold_first_dep != 0, &sp->lay);
+    if (!err.empty()) gsv_panic(err);
+    sp->views = std::move(views);
     sp->scheduled = true;
     if (info) {
-      info[0] = sp->sched.windows.size(); info[1] = sp->sched.deps.size(); info[2] = sp->sched.max_width;
-      info[3] = sp->sched.scratch_slots; info[4] = sp->sched.critical_steps; info[5] = sp->sched.total_steps; info[6] = sp->sched.max_window_ct;
+      const Schedule& s = sp->lay.sched;
+      info[0] = s.windows.size(); info[1] = s.deps.size(); info[2] = s.max_width;
+      info[3] = s.scratch_slots; info[4] = s.critical_steps; info[5] = s.total_steps; info[6] = s.max_window_ct;
     }
     return 0;
   } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }
+// One pass over the engine's tables (PlanLayout), the way a window launch reads them (kernels.hip): ONE wire file of facade.n_slots slots
+// — constants at slots 0..2, the scratch regions, the globals from global_base —, per call its `pre` hand-over list, its program at
+// w_base, its `post` list; readiness from the window-relative dependency lists; ciphertexts at CallDesc::ct_off inside a block of the
+// layout's size (retained: the stream itself; windows: copied out at the window's end; ring: after each call).
 static int plan_run_scheduled(SimPlan* sp, int evaluate, uint64_t gid_base, const uint8_t delta[16], const uint8_t consts[32], const uint8_t* inputs,
                               const uint8_t* input_bits, uint8_t* cts, uint8_t* out_labels, uint8_t* out_bits) {
-  const BuiltPlan& bp = sp->bp;
-  const Schedule& sc = sp->sched;
-  const uint32_t n_globals = plan_n_globals(bp);
-  std::vector<uint8_t> G(size_t(n_globals) * 16, 0xC3), GB(n_globals, 0);
-  for (uint32_t i = 0; i < bp.n_inputs; ++i) { std::memcpy(&G[size_t(i) * 16], inputs + 16 * i, 16); if (evaluate) GB[i] = input_bits[i] ? 1 : 0; }
+  const PlanLayout& L = sp->lay;
+  const Program& f = L.facade;
+  std::vector<uint8_t> W(size_t(f.n_slots) * 16, 0xC3), VB(f.n_slots, 0);
+  std::memcpy(&W[0], consts, 32);
+  std::memset(&W[size_t(SLOT_ZERO) * 16], 0, 16);
+  VB[SLOT_FALSE] = 0; VB[SLOT_TRUE] = 1; VB[SLOT_ZERO] = 0;
+  for (size_t i = 0; i < f.input_slots.size(); ++i) { std::memcpy(&W[size_t(f.input_slots[i]) * 16], inputs + 16 * i, 16); if (evaluate) VB[f.input_slots[i]] = input_bits[i] ? 1 : 0; }
   const Label d = evaluate ? Label{{0, 0, 0, 0}} : load(delta);
-  std::vector<uint64_t> gid_off(bp.calls.size()), ct_off(bp.calls.size());
-  { uint64_t g = 0, c = 0; for (size_t k = 0; k < bp.calls.size(); ++k) { gid_off[k] = g; ct_off[k] = c; const Program& pr = bp.programs[size_t(bp.calls[k].program)]; g += pr.n_gates; c += pr.n_ct; } }
-  std::vector<uint8_t> W(size_t(std::max<uint64_t>(sc.scratch_slots, 8)) * 16, 0xA5), VB(std::max<uint64_t>(sc.scratch_slots, 8), 0);
-  for (const Schedule::Window& win : sc.windows) {
+  const uint64_t block_records = L.retain ? f.n_ct : L.max_block;
+  std::vector<uint8_t> own_block(L.retain ? 0 : size_t(block_records) * 16, 0xE7);
+  uint8_t* const block = L.retain ? cts : own_block.data();
+  auto copy_slots = [&](uint32_t off, uint32_t n) {
+    for (uint32_t q = off; q < off + n; ++q) { std::memcpy(&W[size_t(L.copy_dst[q]) * 16], &W[size_t(L.copy_src[q]) * 16], 16); VB[L.copy_dst[q]] = VB[L.copy_src[q]]; }
+  };
+  // a stretch of the gate-order stream <-> where it lies in the block: into the block before an evaluation reads it, out of it after a garbling wrote it
+  auto move_cts = [&](uint64_t stream_off, uint64_t block_off, uint64_t n, bool before) {
+    if (L.retain || !n || before != (evaluate != 0)) return;
+    if (evaluate) std::memcpy(block + block_off * 16, cts + stream_off * 16, size_t(n) * 16); else std::memcpy(cts + stream_off * 16, block + block_off * 16, size_t(n) * 16);
+  };
+  for (const Schedule::Window& win : L.sched.windows) {
     const size_t m = win.call1 - win.call0;
+    const dev::CallDesc* cd = &L.calls[win.call0];
+    if (!L.ring) move_cts(win.ct0, 0, win.n_ct, true);
     std::vector<uint8_t> done(m, 0);
     for (size_t executed = 0; executed < m; ++executed) {
       // the ready call with the largest stream index: as far from the stream order as the dependencies allow
@@ -340,43 +360,33 @@ static int plan_run_scheduled(SimPlan* sp, int evaluate, uint64_t gid_base, cons
       for (size_t kk = m; kk-- > 0;) {
         if (done[kk]) continue;
         bool ready = true;
-        for (uint32_t q = sc.dep_off[win.call0 + kk]; q < sc.dep_off[win.call0 + kk + 1] && ready; ++q) ready = done[sc.deps[q] - win.call0] != 0;
+        for (uint32_t q = cd[kk].dep_off; q < cd[kk].dep_off + cd[kk].n_deps && ready; ++q) ready = L.deps[q] < m && done[L.deps[q]] != 0;  // (a flag nobody sets: never ready)
         if (ready) { pick = kk; break; }
       }
       if (pick == m) gsv_panic("schedule deadlocks");
-      const uint32_t k = uint32_t(win.call0 + pick);
-      const BuiltPlan::Call& c = bp.calls[k];
-      const Program& g = bp.programs[size_t(c.program)];
-      const size_t base = sc.scratch_base[k];
-      std::memset(&W[base * 16], 0xA5, size_t(g.n_slots) * 16);  // poison: whatever an earlier occupant of the region left behind
-      std::memcpy(&W[base * 16], consts, 32);
-      std::memset(&W[(base + SLOT_ZERO) * 16], 0, 16);
-      VB[base + 0] = 0; VB[base + 1] = 1; VB[base + SLOT_ZERO] = 0;
-      for (size_t i = 0; i < c.in_globals.size(); ++i) {
-        const uint32_t w = c.in_globals[i];
-        const size_t dst = base + g.input_slots[i];
-        if (w == PLAN_WIRE_FALSE) { std::memcpy(&W[dst * 16], consts, 16); VB[dst] = 0; }
-        else if (w == PLAN_WIRE_TRUE) { std::memcpy(&W[dst * 16], consts + 16, 16); VB[dst] = 1; }
-        else { std::memcpy(&W[dst * 16], &G[size_t(w) * 16], 16); VB[dst] = GB[w]; }
-      }
+      const dev::CallDesc& c = cd[pick];
+      const PlanCallView& v = sp->views[win.call0 + pick];
+      const Program& g = *v.prog;
+      const size_t base = c.w_base;
+      if (base + g.n_slots > L.global_base) gsv_panic("a call's scratch region runs into the global wires");
+      if (c.ct_off + g.n_ct > block_records) gsv_panic("a call's ciphertext block leaves the device block");
+      const size_t own = base ? 0 : SLOT_FIRST_INPUT;  // (the region at slot 0 shares the wire file's constants)
+      if (g.n_slots > own) std::memset(&W[(base + own) * 16], 0xA5, (size_t(g.n_slots) - own) * 16);  // poison: whatever an earlier occupant of the region left behind
+      copy_slots(c.pre_off, c.n_pre);
+      if (L.ring) move_cts(v.ct_off, c.ct_off, g.n_ct, true);
       std::vector<uint8_t> w(W.begin() + base * 16, W.begin() + (base + g.n_slots) * 16), vb(VB.begin() + base, VB.begin() + base + g.n_slots);
-      interpret(g, evaluate != 0, gid_base + gid_off[k], d, w, vb, cts + ct_off[k] * 16);
+      interpret(g, evaluate != 0, gid_base + c.gid_off, d, w, vb, block + c.ct_off * 16);
       std::memcpy(&W[base * 16], w.data(), w.size());
       std::memcpy(&VB[base], vb.data(), vb.size());
-      for (size_t i = 0; i < c.out_globals.size(); ++i) {
-        const uint32_t src = g.output_slots[i];
-        if (src & SLOT_LDS_FLAG) gsv_panic("program output in the LDS window");
-        std::memcpy(&G[size_t(c.out_globals[i]) * 16], &W[(base + src) * 16], 16);
-        GB[c.out_globals[i]] = VB[base + src];
-      }
+      copy_slots(c.post_off, c.n_post);
+      if (L.ring) move_cts(v.ct_off, c.ct_off, g.n_ct, false);
       done[pick] = 1;
     }
+    if (!L.ring) move_cts(win.ct0, 0, win.n_ct, false);
   }
-  for (size_t i = 0; i < bp.outputs.size(); ++i) {
-    const uint32_t w = bp.outputs[i];
-    if (w == PLAN_WIRE_FALSE) { std::memcpy(out_labels + 16 * i, consts, 16); if (out_bits) out_bits[i] = 0; }
-    else if (w == PLAN_WIRE_TRUE) { std::memcpy(out_labels + 16 * i, consts + 16, 16); if (out_bits) out_bits[i] = 1; }
-    else { std::memcpy(out_labels + 16 * i, &G[size_t(w) * 16], 16); if (out_bits) out_bits[i] = GB[w]; }
+  for (size_t i = 0; i < f.output_slots.size(); ++i) {
+    std::memcpy(out_labels + 16 * i, &W[size_t(f.output_slots[i]) * 16], 16);
+    if (out_bits) out_bits[i] = VB[f.output_slots[i]];
   }
   return 0;
 }

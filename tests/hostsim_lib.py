@@ -173,12 +173,14 @@ class SimPlan:
         if getattr(self, "h", None):
             lib().hostsim_plan_free(self.h)
 
-    def schedule(self, max_calls, max_slots=0, window_ct=0, window_calls=0):
-        """Compute (and verify against the hazard rules) the engine's call-level schedule; garble / evaluate then execute it with the
-        freedom of the device's dataflow execution (any order the dependencies allow).  Returns {n_windows, n_dependencies, max_width,
-        scratch_slots, critical_steps, total_steps, max_window_ct}."""
+    def schedule(self, max_calls, max_slots=0, window_ct=0, window_calls=0, retain=True, safe=False, withhold_first_dep=False):
+        """Compute (and verify against the hazard rules) the engine's call-level schedule and build the engine's tables for it
+        (plan_layout.hpp: build_plan_layout with this retain mode, `safe` and `withhold_first_dep`); garble / evaluate then execute those
+        tables with the freedom of the device's dataflow execution (any order the dependency lists allow).  Returns {n_windows,
+        n_dependencies, max_width, scratch_slots, critical_steps, total_steps, max_window_ct}."""
         info = np.zeros(7, np.uint64)
-        if lib().hostsim_plan_schedule(self.h, C.c_uint32(max_calls), C.c_uint64(max_slots), C.c_uint64(window_ct), C.c_uint32(window_calls), info.ctypes.data_as(C.POINTER(C.c_uint64))):
+        if lib().hostsim_plan_schedule(self.h, C.c_uint32(max_calls), C.c_uint64(max_slots), C.c_uint64(window_ct), C.c_uint32(window_calls), C.c_int(bool(retain)), C.c_int(bool(safe)),
+                                       C.c_int(bool(withhold_first_dep)), info.ctypes.data_as(C.POINTER(C.c_uint64))):
             raise RuntimeError(lib().hostsim_last_error().decode())
         return dict(zip(["n_windows", "n_dependencies", "max_width", "scratch_slots", "critical_steps", "total_steps", "max_window_ct"], (int(x) for x in info)))
 

@@ -253,27 +253,52 @@ def test_plan_builder_matches_flat_stream(spec, units, seed):
     ("g1_mux_add", ["bigint::multiplexer", "g1::add_montgomery"], 3, dict(max_calls=16, max_slots=1)),  # scratch ring of ONE region: every call waits for its predecessor
     ("driver_mix", ["test::inner", "bigint::add"], 6, dict(max_calls=32, window_ct=300)),      # ciphertext windows
     ("driver_mix", ["test::inner", "bigint::add"], 6, dict(max_calls=3, max_slots=400)),       # a small ring: regions are reused while other calls are in flight
+    ("g1_mux_add", ["bigint::multiplexer", "g1::add_montgomery"], 3, dict(max_calls=1, window_calls=1, safe=True)),  # the safe layout: one call per window, no dependency
+    ("driver_mix", ["test::inner", "bigint::add"], 6, dict(max_calls=32, retain=False, ring=(3, 9))),  # a ciphertext ring of 9 records under a stream of 12: ct_off = ring_off, the last call wraps
+    ("driver_mix", ["test::inner", "bigint::add"], 6, dict(max_calls=32, window_ct=300, retain=False)),  # not retained: ct_off relative to the window's first record
+    ("driver_mix", ["test::inner", "bigint::add"], 6, dict(max_calls=32, window_ct=5, retain=False)),    # ... in three windows
 ])
 def test_scheduled_plan_matches_flat_stream(spec, units, seed, sched):
-    """schedule.hpp — the code engine.cpp runs at session creation — over a plan: windows of consecutive calls, inside a window a
-    dataflow over the RAW / WAW / WAR hazards on the (recycled) global ids, the in-flight bound and the scratch ring.  The schedule is
-    verified by brute force (every hazard and every scratch overlap covered by a dependency path) and the host interpreter executes
-    it as far from the stream order as the dependencies allow (always the ready call with the LARGEST index), all calls in one
-    shared scratch ring: the stream, its CBC-MAC, the output labels and the evaluation must still be the oracle's."""
+    """schedule.hpp and plan_layout.hpp — the code engine.cpp runs at session creation — over a plan: windows of consecutive calls,
+    inside a window a dataflow over the RAW / WAW / WAR hazards on the (recycled) global ids, the in-flight bound and the scratch ring.
+    The schedule is verified by brute force (every hazard and every scratch overlap covered by a dependency path) and the host
+    interpreter executes the ENGINE'S TABLES for it (call descriptors, hand-over lists with the constants' copies, window-relative
+    dependency lists, the three forms of ct_off) as far from the stream order as the dependencies allow (always the ready call with the
+    LARGEST index), all calls in one wire file: the stream, its CBC-MAC, the output labels and the evaluation must still be the oracle's."""
     sp = h.SimPlan(spec, units)
-    info = sp.schedule(**sched)
+    sched = dict(sched)
+    ring = sched.pop("ring", None)  # (drain segment records, ring records)
+    info = sp.ring(*ring, **sched)[0] if ring else sp.schedule(**sched)
     assert info["critical_steps"] <= info["total_steps"]
+    if sched.get("safe"):
+        assert info["n_windows"] == sp.info["n_calls"] and info["n_dependencies"] == 0
     ref = o.garble(spec, seed)
     n_in = ref.n_in
     labs = h.labels_from_seed(seed, 3 + n_in)
     delta, consts, inputs = labs[0], labs[1:3], labs[3:]
     out, cts = sp.garble(delta, consts, inputs)
     assert ref.n_ciphertexts == cts.shape[0] and (ref.ciphertexts == cts).all() and (ref.output_label0 == out).all()
+    assert h.cbcmac(cts) == ref.ct_hash.tobytes()
     bits = np.random.default_rng(seed).integers(0, 2, n_in).astype(np.uint8)
     act = np.where(bits[:, None] == 1, inputs ^ delta[None, :], inputs)
     oa, ob = sp.evaluate(np.stack([consts[0], consts[1] ^ delta]), act, bits, cts)
     eo, _, _ = o.execute(spec, bits)
     assert (ob == eo).all() and (oa == np.where(ob[:, None] == 1, out ^ delta[None, :], out)).all()
+
+
+def test_withheld_dependency_deadlocks_the_interpreter():
+    """withhold_first_dep (plan_layout.hpp; GSV_FAULT_WITHHOLD_DEP=1 in the engine) points the first dependency of the first call that
+    has one at the flag nobody sets: the interpreter, which takes readiness from the engine's dependency lists, finds no ready call.
+    The safe layout has no dependency to withhold and runs."""
+    sp = h.SimPlan("driver_mix", ["test::inner", "bigint::add"])
+    labs = h.labels_from_seed(6, 3 + sp.info["n_inputs"])
+    assert sp.schedule(max_calls=32, withhold_first_dep=True)["n_dependencies"] > 0
+    with pytest.raises(RuntimeError, match="schedule deadlocks"):
+        sp.garble(labs[0], labs[1:3], labs[3:])
+    ref_out, ref_cts = (sp.schedule(max_calls=32), sp.garble(labs[0], labs[1:3], labs[3:]))[1]
+    sp.schedule(max_calls=1, window_calls=1, safe=True, withhold_first_dep=True)
+    out, cts = sp.garble(labs[0], labs[1:3], labs[3:])
+    assert (out == ref_out).all() and (cts == ref_cts).all()
 
 
 def test_schedule_finds_the_independent_calls():
