@@ -170,6 +170,12 @@ extern "C" {
     // The source form is declared with the other callback calls below.
     pub fn gsv_session_evaluate_streaming_calls(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, restartable: c_int, dir: *const c_char, indexes: *const u64, first_index: u64, outboard_dir: *const c_char, expected: *const u8, expected_len: u64, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int;
     pub fn gsv_session_evaluate_resume_info(s: *const GsvSession, next_call: *mut u64, next_record: *mut u64) -> c_int;
+    // CBC-MAC checkpoints while evaluating (include/gsv_engine.h): the gc files verified against gc_<index>.mck on the
+    // device while they are evaluated — no MAC worker starts —, in slices and with restart points as above (first_call = n_calls = 0: the
+    // whole pass, the only form a program session takes); and the resident stream checked where it lies.  GSV_ERR_MISMATCH names the
+    // place through gsv_session_mismatch_info.  The source form is declared with the other callback calls below.
+    pub fn gsv_session_evaluate_streaming_mac_calls(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, restartable: c_int, dir: *const c_char, indexes: *const u64, first_index: u64, checkpoint_dir: *const c_char, expected: *const u8, cbcmac_hashes: *mut u8) -> c_int;
+    pub fn gsv_session_ciphertext_cbcmac_check(s: *mut GsvSession, checkpoint_dir: *const c_char, indexes: *const u64, first_index: u64, expected: *const u8, hashes: *mut u8) -> c_int;
 }
 
 /// The source form of a sliced evaluation: its outboards come as an array of pointers (`const uint8_t* const*`, null: unverified),
@@ -178,7 +184,14 @@ mod sliced_source {
     use super::*;
     extern "C" {
         pub(super) fn gsv_session_evaluate_streaming_source_calls(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, restartable: c_int, source: GsvCtSourceFn, user: *mut std::ffi::c_void, outboards: *const *const u8, outboard_bytes: *const u64, last_chunks: *const u8, expected: *const u8, expected_len: u64, cbcmac_hashes: *mut u8, blake3_digests: *mut u8) -> c_int;
+        pub(super) fn gsv_session_evaluate_streaming_source_mac_calls(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, restartable: c_int, source: GsvCtSourceFn, user: *mut std::ffi::c_void, checkpoints: *const *const u8, checkpoint_bytes: *const u64, expected: *const u8, cbcmac_hashes: *mut u8) -> c_int;
     }
+}
+/// gsv_session_evaluate_streaming_source_mac_calls: the generic source verified against CBC-MAC checkpoints held in memory
+/// (`checkpoints[i]`: byte for byte a gc_<i>.mck, handed in with every slice); `expected` (n x 16) may be null.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn evaluate_streaming_source_mac_calls(s: *mut GsvSession, gate_id_base: u64, first_call: u64, n_calls: u64, restartable: c_int, source: GsvCtSourceFn, user: *mut std::ffi::c_void, checkpoints: *const *const u8, checkpoint_bytes: *const u64, expected: *const u8, cbcmac_hashes: *mut u8) -> c_int {
+    sliced_source::gsv_session_evaluate_streaming_source_mac_calls(s, gate_id_base, first_call, n_calls, restartable, source, user, checkpoints, checkpoint_bytes, expected, cbcmac_hashes)
 }
 /// gsv_session_evaluate_streaming_source_calls: one slice of a plan session's evaluation from the generic source; with `outboards` as
 /// evaluate_streaming_source_verified (the same outboards in every slice).  `restartable`: see gsv_session_evaluate_resume_info.

@@ -148,6 +148,7 @@ EXPORTS = [
     "gsv_session_evaluate_streaming_calls", "gsv_session_evaluate_streaming_source_calls", "gsv_session_evaluate_resume_info",
     "gsv_cbcmac_checkpoints_size", "gsv_cbcmac_file_checkpoints", "gsv_cbcmac_file_check", "gsv_engine_cbcmac_streams_check", "gsv_engine_cbcmac_streams_check_seconds",
     "gsv_engine_cbcmac_files", "gsv_session_garble_streaming_checkpoints", "gsv_session_garble_streaming_check",
+    "gsv_session_evaluate_streaming_mac_calls", "gsv_session_evaluate_streaming_source_mac_calls", "gsv_session_ciphertext_cbcmac_check",
 ]
 
 # CiphertextHandler / CiphertextSource as host callbacks (include/gsv_engine.h: gsv_ct_sink_fn, gsv_ct_source_fn)
@@ -284,6 +285,9 @@ def lib():
         L.gsv_engine_cbcmac_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(C.c_char_p), u8p, u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.gsv_session_garble_streaming_checkpoints.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int, u8p, C.c_char_p]
         L.gsv_session_garble_streaming_check.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, u8p, u8p]
+        L.gsv_session_evaluate_streaming_mac_calls.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_char_p, u8p, u8p]
+        L.gsv_session_evaluate_streaming_source_mac_calls.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, CT_SOURCE_FN, vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64), u8p, u8p]
+        L.gsv_session_ciphertext_cbcmac_check.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, u8p, u8p]
         _lib = L
     return _lib
 
@@ -1103,9 +1107,52 @@ class Session:
         m, d = _rows(macs), _rows(dig)
         return (m, d) if commitment == "both" else m if d is None else d
 
-    def _evaluate_files(self, commitment, gate_id_base, directory, idx_p, first_index, outboard_dir, expected):
+    def _pack_mac_expected(self, expected):
+        """The CBC-MAC commitments a checkpoint-verified pass trusts, one of 16 bytes per instance -> one uint8 array; None stays None."""
+        if expected is None:
+            return None
+        exp = np.frombuffer(b"".join(bytes(e) for e in expected), np.uint8)
+        if len(expected) != self.n or exp.size != 16 * self.n:
+            raise ValueError("expected: one 16-byte commitment per instance")
+        return exp
+
+    def _evaluate_mac_files(self, gate_id_base, first_call, n_calls, restartable, directory, idx_p, first_index, checkpoint_dir, expected):
+        """gsv_session_evaluate_streaming_mac_calls: gc files verified against the checkpoint files of checkpoint_dir while they are
+        evaluated.  Returns the verified CBC-MACs from the slice that ends the pass, None before."""
+        exp = self._pack_mac_expected(expected)
+        out = np.zeros((self.n, 16), np.uint8)
+        with _gc_paused():
+            rc = lib().gsv_session_evaluate_streaming_mac_calls(self.h, gate_id_base, first_call, n_calls, int(bool(restartable)), os.fsencode(directory), idx_p, first_index,
+                                                                os.fsencode(checkpoint_dir), _p(exp), _p(out))
+        _chk_mismatch(rc, self.mismatch_info, self._resume_call)
+        return _rows(out) if self._ends_pass(first_call, n_calls) else None
+
+    def _evaluate_mac_source(self, gate_id_base, first_call, n_calls, restartable, source, checkpoints, expected):
+        """gsv_session_evaluate_streaming_source_mac_calls: `checkpoints` holds one bytes object per instance, byte for byte a gc_<i>.mck."""
+        cks = [np.frombuffer(bytes(c), np.uint8) for c in checkpoints]
+        if len(cks) != self.n:
+            raise ValueError("checkpoints: one per instance")
+        exp = self._pack_mac_expected(expected)
+        nothing = np.zeros(1, np.uint8)
+        ck_p = (C.POINTER(C.c_uint8) * self.n)(*[_p(c) if c.size else _p(nothing) for c in cks])
+        ck_n = (C.c_uint64 * self.n)(*[c.size for c in cks])
+        cb, failure = self._source_callback(source)
+        out = np.zeros((self.n, 16), np.uint8)
+        with _gc_paused():
+            rc = lib().gsv_session_evaluate_streaming_source_mac_calls(self.h, gate_id_base, first_call, n_calls, int(bool(restartable)), cb, None, ck_p, ck_n, _p(exp), _p(out))
+        if failure:
+            raise failure[0]
+        _chk_mismatch(rc, self.mismatch_info, self._resume_call)
+        return _rows(out) if self._ends_pass(first_call, n_calls) else None
+
+    def _evaluate_files(self, commitment, gate_id_base, directory, idx_p, first_index, outboard_dir, expected, checkpoint_dir=None):
         """evaluate_streaming / evaluate_streaming_indexed (idx_p: the index list, or None for first_index + i); with outboard_dir or
-        expected gsv_session_evaluate_streaming_verified, where GSV_ERR_MISMATCH raises CiphertextMismatch with the place."""
+        expected gsv_session_evaluate_streaming_verified, where GSV_ERR_MISMATCH raises CiphertextMismatch with the place; with
+        checkpoint_dir gsv_session_evaluate_streaming_mac_calls over the whole pass."""
+        if checkpoint_dir is not None:
+            if commitment != "cbcmac" or outboard_dir is not None:
+                raise ValueError("checkpoint_dir needs commitment='cbcmac' and no outboard_dir: the files hold the states of the CBC-MAC")
+            return self._evaluate_mac_files(gate_id_base, 0, 0, False, directory, idx_p, first_index, checkpoint_dir, expected)
         verified = outboard_dir is not None or expected is not None
         if verified:
             if commitment == "cbcmac":
@@ -1136,16 +1183,16 @@ class Session:
         unknown = (1 << 64) - 1
         return int(a.value), None if b.value == unknown else int(b.value), None if c.value == unknown else int(c.value)
 
-    def evaluate_streaming_indexed(self, directory, indexes, gate_id_base=0, commitment="cbcmac", outboard_dir=None, expected=None):
+    def evaluate_streaming_indexed(self, directory, indexes, gate_id_base=0, commitment="cbcmac", outboard_dir=None, expected=None, checkpoint_dir=None):
         """Evaluate with instance i reading gc_<indexes[i]>.bin: the finalized instances of a cut-and-choose run in one session.
-        commitment, outboard_dir and expected as for evaluate_streaming."""
+        commitment, outboard_dir, checkpoint_dir and expected as for evaluate_streaming."""
         _check_commitment(commitment, False)
         idx = np.ascontiguousarray(indexes, np.uint64)
         assert idx.size == self.n
         idx_p = idx.ctypes.data_as(C.POINTER(C.c_uint64))
-        return self._evaluate_files(commitment, gate_id_base, directory, idx_p, 0, outboard_dir, expected)
+        return self._evaluate_files(commitment, gate_id_base, directory, idx_p, 0, outboard_dir, expected, checkpoint_dir)
 
-    def evaluate_from_source(self, source, gate_id_base=0, commitment="cbcmac", outboards=None, expected=None, last_chunks=None):
+    def evaluate_from_source(self, source, gate_id_base=0, commitment="cbcmac", outboards=None, expected=None, last_chunks=None, checkpoints=None):
         """Evaluate with the ciphertexts pulled from `source(instance, first_record, n) -> [n,16] uint8` (None / short = exhausted):
         the generic CiphertextSource (ciphertext_source.rs:14-34).  Returns the CBC-MACs of what was read; commitment as for
         evaluate_streaming.
@@ -1154,8 +1201,15 @@ class Session:
         bytes, as garble_to_sink returns them) the outboards are checked against the commitments before `source` is called at all;
         without, they are checked for form only and the commitments are compared at the end of the pass — until then the outboards
         are unauthenticated.  Either way the pass stops at the first group that differs from its outboard: CiphertextMismatch names
-        (instance, group, first_record), and read_outputs then fails."""
+        (instance, group, first_record), and read_outputs then fails.
+        Verified against CBC-MAC checkpoints (gsv_session_evaluate_streaming_source_mac_calls, with "cbcmac"): `checkpoints`, one bytes
+        object per instance (byte for byte a gc_<i>.mck), with an optional `expected` of 16-byte commitments; malformed checkpoints are
+        refused before `source` is called at all.  Returns the verified CBC-MACs."""
         _check_commitment(commitment, False)
+        if checkpoints is not None:
+            if commitment != "cbcmac" or outboards is not None or last_chunks is not None:
+                raise ValueError("checkpoints need commitment='cbcmac' and neither outboards nor last_chunks: they hold the states of the CBC-MAC")
+            return self._evaluate_mac_source(gate_id_base, 0, 0, False, source, checkpoints, expected)
         ob_p, ob_n, last_a, exp_a, exp_len = self._pack_outboards(commitment, outboards, expected, last_chunks)
         cb, failure = self._source_callback(source)
 
@@ -1222,7 +1276,7 @@ class Session:
         return CT_SOURCE_FN(_cb), failure
 
     def evaluate_calls(self, first_call, n_calls, directory=None, indexes=None, first_index=0, source=None, gate_id_base=0, commitment="cbcmac", outboard_dir=None, outboards=None,
-                       expected=None, last_chunks=None, restartable=False):
+                       expected=None, last_chunks=None, restartable=False, checkpoint_dir=None, checkpoints=None):
         """Plan sessions: evaluate calls [first_call, first_call + n_calls) only, whole windows of the schedule (windows()), from gc files
         (`directory`, with `indexes` or `first_index`) or from `source` — evaluate_streaming / evaluate_streaming_indexed /
         evaluate_from_source in slices (gsv_session_evaluate_streaming_calls / _source_calls).  The wire file, gate ids, the stream
@@ -1233,12 +1287,30 @@ class Session:
         [+ last_chunks] (source), in every slice.
         restartable=True keeps a restart point in front of the slice: when the slice fails with a CiphertextMismatch that has a place
         or because a file or the source ran dry, the session is rolled back — resume_info() says to which call and from which record
-        the ciphertexts are needed again (CiphertextMismatch.resume_call is that call) — and the repaired slice is simply repeated."""
+        the ciphertexts are needed again (CiphertextMismatch.resume_call is that call) — and the repaired slice is simply repeated.
+        Verified against CBC-MAC checkpoints, with commitment="cbcmac": checkpoint_dir (files) or checkpoints (source; one bytes object
+        per instance), with an optional `expected` of 16-byte commitments, in every slice.  Then the verified CBC-MACs come back from
+        the slice that ends the pass, None before."""
         _check_commitment(commitment, False)
         if (directory is None) == (source is None):
             raise ValueError("a directory of gc files or a source")
         if first_call == 0 and n_calls == 0:
             raise ValueError("an empty slice")  # (0, 0 means the whole pass to the C entry points)
+        if checkpoint_dir is not None or checkpoints is not None:
+            if commitment != "cbcmac" or outboard_dir is not None or outboards is not None or last_chunks is not None:
+                raise ValueError("checkpoint_dir / checkpoints need commitment='cbcmac' and no outboards: they hold the states of the CBC-MAC")
+            if (checkpoint_dir is not None) != (directory is not None) or (checkpoints is not None) != (source is not None):
+                raise ValueError("checkpoint_dir belongs to gc files, checkpoints to a source")
+            if source is not None:
+                if indexes is not None:
+                    raise ValueError("indexes belong to gc files")
+                return self._evaluate_mac_source(gate_id_base, first_call, n_calls, restartable, source, checkpoints, expected)
+            idx_p = None
+            if indexes is not None:
+                idx = np.ascontiguousarray(indexes, np.uint64)
+                assert idx.size == self.n
+                idx_p = idx.ctypes.data_as(C.POINTER(C.c_uint64))
+            return self._evaluate_mac_files(gate_id_base, first_call, n_calls, restartable, directory, idx_p, first_index, checkpoint_dir, expected)
         macs = np.zeros((self.n, 16), np.uint8) if commitment != "blake3" else None
         dig = np.zeros((self.n, 32), np.uint8) if commitment != "cbcmac" else None
         failure = []
@@ -1322,16 +1394,20 @@ class Session:
         """Timing harnesses only: allow garble_calls slices that do not continue the previous one (stale wires, meaningless MACs)."""
         _chk(lib().gsv_session_set_unchecked_slices(self.h, int(bool(on))))
 
-    def evaluate_streaming(self, directory, first_index=0, gate_id_base=0, commitment="cbcmac", outboard_dir=None, expected=None):
+    def evaluate_streaming(self, directory, first_index=0, gate_id_base=0, commitment="cbcmac", outboard_dir=None, expected=None, checkpoint_dir=None):
         """Evaluate with the ciphertexts read from gc_<first_index+i>.bin segment by segment; returns the files' CBC-MACs.
         commitment="blake3": the files' 32-byte BLAKE3 digests instead, computed on the device from the uploaded segments (no MAC
         worker runs); "both": (CBC-MACs, BLAKE3 digests).  Comparing them with the garbler's commitments is the caller's part —
         unless outboard_dir and expected are given (verified streaming, with "blake3" / "both"): `expected` holds the commitment of
         every instance (32 bytes, or the first 16), the outboards gc_<index>.b3o in outboard_dir are checked against them before
         anything is uploaded, and the pass stops at the first group of 2^k chunks that differs from its outboard: CiphertextMismatch
-        names (instance, group), and read_outputs then fails."""
+        names (instance, group), and read_outputs then fails.
+        checkpoint_dir (with "cbcmac"; gsv_session_evaluate_streaming_mac_calls): the files are verified against the CBC-MAC checkpoint
+        files gc_<index>.mck of that directory on the device while they are evaluated, and no host MAC worker runs.  With `expected`
+        (16-byte commitments) the files' last states are compared before anything is uploaded.  Returns the verified CBC-MACs; a group
+        of 2^k records that does not hold raises CiphertextMismatch(instance, group, first_record) at the launch that would read it."""
         _check_commitment(commitment, False)
-        return self._evaluate_files(commitment, gate_id_base, directory, None, first_index, outboard_dir, expected)
+        return self._evaluate_files(commitment, gate_id_base, directory, None, first_index, outboard_dir, expected, checkpoint_dir)
 
     def set_evaluate_inputs(self, const_active, input_active, input_bits):
         c = _u8(const_active, (self.n, 32))
@@ -1390,6 +1466,23 @@ class Session:
         h = np.zeros(16, np.uint8)
         _chk(lib().gsv_session_ciphertext_hash(self.h, instance, _p(h)))
         return h.tobytes()
+
+    def ciphertext_cbcmac_check(self, checkpoint_dir, first_index=0, indexes=None, expected=None):
+        """Verify every instance's resident stream (after garble(), or after upload_ciphertexts of every instance) against the CBC-MAC
+        checkpoint files <checkpoint_dir>/gc_<index>.mck (index = indexes[i], or first_index + i) on the device, where it lies.
+        expected: one trusted 16-byte commitment per instance, compared with the files' last states first.  Returns the verified
+        CBC-MACs — what ciphertext_hash(i) folds on the host —; a stream that differs raises CiphertextMismatch(instance, group,
+        first_record).  Sessions that retain the whole stream only."""
+        idx_p = None
+        if indexes is not None:
+            idx = np.ascontiguousarray(indexes, np.uint64)
+            assert idx.size == self.n
+            idx_p = idx.ctypes.data_as(C.POINTER(C.c_uint64))
+        exp = self._pack_mac_expected(expected)
+        out = np.zeros((self.n, 16), np.uint8)
+        rc = lib().gsv_session_ciphertext_cbcmac_check(self.h, os.fsencode(checkpoint_dir), idx_p, first_index, _p(exp), _p(out))
+        _chk_mismatch(rc, self.mismatch_info)
+        return _rows(out)
 
     def ciphertext_blake3(self, with_seconds=False):
         """BLAKE3 of every instance's resident stream in gate order (after garble(), or after upload_ciphertexts of every instance),

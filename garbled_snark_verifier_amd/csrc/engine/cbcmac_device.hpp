@@ -65,6 +65,20 @@ GSV_HD bool mac_chain_run(const Tab& T, const MacChain& m, uint64_t first, uint3
   return ((st.w[0] ^ want.w[0]) | (st.w[1] ^ want.w[1]) | (st.w[2] ^ want.w[2]) | (st.w[3] ^ want.w[3])) != 0;
 }
 
+// A stream that is RESIDENT in program order (gsv_session_ciphertext_cbcmac_check) is checked where it lies: record q of a block's
+// gate-order stream is block[(q / n_ct) * n_ct + ct_pos[q % n_ct]] (kernel_api.h, gsvk_b3_chunks_indexed: n_ct records per replay, ct_pos
+// the position table).  A chain asks for ascending q, so the replay it stands in is kept and the division is taken only where a
+// request leaves it by more than one replay; any order of requests gives the same positions.
+struct MacIndexedPos {
+  const uint32_t* ct_pos;
+  uint64_t n_ct, rep_base = 0;  // rep_base: first record of the replay the last request lay in
+  GSV_HD MacIndexedPos(const uint32_t* ct_pos_, uint64_t n_ct_) : ct_pos(ct_pos_), n_ct(n_ct_) {}
+  GSV_HD uint64_t at(uint64_t q) {
+    if (q - rep_base >= n_ct) rep_base = q - rep_base - n_ct < n_ct ? rep_base + n_ct : (q / n_ct) * n_ct;
+    return rep_base + ct_pos[q - rep_base];
+  }
+};
+
 }  // namespace dev
 }  // namespace gsv
 
@@ -83,8 +97,9 @@ namespace dev {
 // records of a 128-byte line in its next trips, so the line should stay in L2 / the CU's L1 meanwhile (a non-temporal load would fetch it
 // eight times).  Round keys: through the scalar cache (LdsBankedTable::rk, c_rk), 44 SGPRs live across the chain loop; LDS holds the
 // bank-replicated Te0 / Te2 only.
-__global__ __launch_bounds__(GSV_MAC_BLOCK_THREADS) void cbcmac_check_kernel(const uint32_t* te, const uint4* seg_, uint64_t seg_stride, uint64_t first, uint64_t n, uint32_t k, uint64_t total,
-                                                                              const uint4* slice_, uint64_t slice_stride, const uint4* carry_in_, uint4* carry_out_, unsigned long long* bad) {
+template <class Rec>
+__device__ __forceinline__ void mac_check_lane(const uint32_t* te, Rec rec, uint64_t first, uint64_t n, uint32_t k, uint64_t total, const uint4* slice_, uint64_t slice_stride, const uint4* carry_in_,
+                                               uint4* carry_out_, unsigned long long* bad) {
   extern __shared__ __attribute__((aligned(16))) char s_mac_mem[];
   (void)s_mac_mem;  // the dynamic LDS block starts at LDS address 0
   // this kernel's own copy of the table fill of run_program_kernel: dword i of the table region, entry x = i / 64; first 32 dwords Te0[x], next 32 Te2[x]
@@ -94,14 +109,56 @@ __global__ __launch_bounds__(GSV_MAC_BLOCK_THREADS) void cbcmac_check_kernel(con
   if (c >= mac_chain_count(first, n, k)) return;
   const uint32_t inst = blockIdx.y;
   const LdsBankedTable aes{(threadIdx.x & 31u) * 4u, (cst_u32*)c_rk};
-  const glb_u128* seg = (const glb_u128*)(seg_) + uint64_t(inst) * seg_stride;
   const MacChain m = mac_chain(first, n, k, total, c);
   const Label* slice = reinterpret_cast<const Label*>(slice_ + uint64_t(inst) * slice_stride);
-  const bool differs = mac_chain_run(aes, m, first, k, [seg](uint64_t q) { const u32x4 v = seg[q]; return Label{{v.x, v.y, v.z, v.w}}; }, slice,
-                                     reinterpret_cast<const Label*>(carry_in_ + inst), reinterpret_cast<Label*>(carry_out_ + inst));
+  const bool differs = mac_chain_run(aes, m, first, k, rec, slice, reinterpret_cast<const Label*>(carry_in_ + inst), reinterpret_cast<Label*>(carry_out_ + inst));
   if (differs) __hip_atomic_fetch_min(bad + inst, (unsigned long long)m.group, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+__global__ __launch_bounds__(GSV_MAC_BLOCK_THREADS) void cbcmac_check_kernel(const uint32_t* te, const uint4* seg_, uint64_t seg_stride, uint64_t first, uint64_t n, uint32_t k, uint64_t total,
+                                                                              const uint4* slice_, uint64_t slice_stride, const uint4* carry_in_, uint4* carry_out_, unsigned long long* bad) {
+  const glb_u128* seg = (const glb_u128*)(seg_) + uint64_t(blockIdx.y) * seg_stride;
+  mac_check_lane(te, [seg](uint64_t q) { const u32x4 v = seg[q]; return Label{{v.x, v.y, v.z, v.w}}; }, first, n, k, total, slice_, slice_stride, carry_in_, carry_out_, bad);
+}
+// The same with the segment read where a resident stream lies: record q of the segment is record block_first + q of the gate-order stream
+// of block[inst] (MacIndexedPos; block_stride in records), which is only read.  Read pattern: a lane walks 2^k gate positions of its
+// group, at the scattered program-order addresses the position table names — a permutation of 16-byte records; plain loads, as above.
+__global__ __launch_bounds__(GSV_MAC_BLOCK_THREADS) void cbcmac_check_indexed_kernel(const uint32_t* te, const uint4* block_, uint64_t block_stride, const uint32_t* ct_pos, uint64_t n_ct, uint64_t block_first,
+                                                                                      uint64_t first, uint64_t n, uint32_t k, uint64_t total, const uint4* slice_, uint64_t slice_stride,
+                                                                                      const uint4* carry_in_, uint4* carry_out_, unsigned long long* bad) {
+  const glb_u128* block = (const glb_u128*)(block_) + uint64_t(blockIdx.y) * block_stride;
+  MacIndexedPos pos(ct_pos, n_ct);
+  mac_check_lane(te, [block, block_first, pos](uint64_t q) mutable { const u32x4 v = block[pos.at(block_first + q)]; return Label{{v.x, v.y, v.z, v.w}}; }, first, n, k, total, slice_, slice_stride,
+                 carry_in_, carry_out_, bad);
+}
 
+}  // namespace dev
+}  // namespace gsv
+
+namespace gsv {
+namespace dev {
+// once per device and kernel: the tables are addressed from LDS byte 0, so there must be no static LDS in front of the dynamic block
+inline int mac_kernel_ready(const void* kf, std::set<int>& done) {
+  static std::mutex attr_mu;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return int(hipErrorInvalidDevice);
+  std::lock_guard<std::mutex> lk(attr_mu);
+  if (done.count(dev)) return 0;
+  hipFuncAttributes fa;
+  if (hipFuncGetAttributes(&fa, kf) != hipSuccess || fa.sharedSizeBytes != 0) return int(hipErrorInvalidValue);
+  const hipError_t e0 = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, int(GSV_LDS_TABLE_BYTES));
+  if (e0 != hipSuccess) return int(e0);
+  done.insert(dev);
+  return 0;
+}
+// what both launchers ask of a segment and its slice; *blocks = grid.x
+inline bool mac_launch_shape(uint64_t first, uint64_t n, uint32_t k, uint64_t total, uint64_t slice_stride, uint32_t n_instances, uint32_t* blocks) {
+  if (n_instances == 0 || n_instances > 65535u || k > 30u || first + n < first || first + n > total) return false;
+  if (n == 0) { *blocks = 0; return true; }
+  const uint64_t chains = mac_chain_count(first, n, k);
+  if (chains + 1 > slice_stride || (chains + GSV_MAC_BLOCK_THREADS - 1) / GSV_MAC_BLOCK_THREADS > 0x7fffffffull) return false;
+  *blocks = uint32_t((chains + GSV_MAC_BLOCK_THREADS - 1) / GSV_MAC_BLOCK_THREADS);
+  return true;
+}
 }  // namespace dev
 }  // namespace gsv
 
@@ -109,28 +166,32 @@ extern "C" {
 // One segment of n_instances streams against its slice of claimed states (cbcmac_check_kernel).  n == 0: nothing is launched.
 int gsvk_cbcmac_check(const void* te, const void* seg, uint64_t seg_stride, uint64_t first, uint64_t n, uint32_t k, uint64_t total, const void* slice, uint64_t slice_stride,
                       const void* carry_in, void* carry_out, void* bad, uint32_t n_instances, hipStream_t s) {
-  if (n_instances == 0 || n_instances > 65535u || k > 30u || first + n < first || first + n > total || n > seg_stride) return int(hipErrorInvalidValue);
+  uint32_t blocks = 0;
+  if (!gsv::dev::mac_launch_shape(first, n, k, total, slice_stride, n_instances, &blocks) || n > seg_stride) return int(hipErrorInvalidValue);
   if (n == 0) return 0;
-  const uint64_t chains = gsv::dev::mac_chain_count(first, n, k);
-  if (chains + 1 > slice_stride || (chains + GSV_MAC_BLOCK_THREADS - 1) / GSV_MAC_BLOCK_THREADS > 0x7fffffffull) return int(hipErrorInvalidValue);
-  {  // once per device: the tables are addressed from LDS byte 0, so there must be no static LDS in front of the dynamic block
-    static std::mutex attr_mu;
-    static std::set<int> attr_done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return int(hipErrorInvalidDevice);
-    std::lock_guard<std::mutex> lk(attr_mu);
-    if (!attr_done.count(dev)) {
-      hipFuncAttributes fa;
-      const void* kf = reinterpret_cast<const void*>(gsv::dev::cbcmac_check_kernel);
-      if (hipFuncGetAttributes(&fa, kf) != hipSuccess || fa.sharedSizeBytes != 0) return int(hipErrorInvalidValue);
-      const hipError_t e0 = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, int(GSV_LDS_TABLE_BYTES));
-      if (e0 != hipSuccess) return int(e0);
-      attr_done.insert(dev);
-    }
-  }
-  hipLaunchKernelGGL(gsv::dev::cbcmac_check_kernel, dim3(uint32_t((chains + GSV_MAC_BLOCK_THREADS - 1) / GSV_MAC_BLOCK_THREADS), n_instances), dim3(GSV_MAC_BLOCK_THREADS), GSV_LDS_TABLE_BYTES, s,
+  static std::set<int> attr_done;
+  if (const int rc = gsv::dev::mac_kernel_ready(reinterpret_cast<const void*>(gsv::dev::cbcmac_check_kernel), attr_done)) return rc;
+  hipLaunchKernelGGL(gsv::dev::cbcmac_check_kernel, dim3(blocks, n_instances), dim3(GSV_MAC_BLOCK_THREADS), GSV_LDS_TABLE_BYTES, s,
                      static_cast<const uint32_t*>(te), static_cast<const uint4*>(seg), seg_stride, first, n, k, total, static_cast<const uint4*>(slice), slice_stride,
                      static_cast<const uint4*>(carry_in), static_cast<uint4*>(carry_out), static_cast<unsigned long long*>(bad));
+  return int(hipGetLastError());
+}
+// ... of streams that lie in program order (cbcmac_check_indexed_kernel): the segment is records [block_first, block_first + n) of the
+// gate-order stream of a block of block_records records, whole replays of n_ct records, inside block_stride.  What is checked here is
+// the segment against the block and the block against its stride; that block + n_instances x block_stride lies inside the caller's
+// buffer (a plan session passes CT + the call's offset with the stream's full stride) and that ct_pos holds n_ct positions below n_ct
+// rests on the caller: the session's own tables.
+int gsvk_cbcmac_check_indexed(const void* te, const void* block, uint64_t block_stride, const void* ct_pos, uint64_t n_ct, uint64_t block_records, uint64_t block_first, uint64_t first, uint64_t n,
+                              uint32_t k, uint64_t total, const void* slice, uint64_t slice_stride, const void* carry_in, void* carry_out, void* bad, uint32_t n_instances, hipStream_t s) {
+  uint32_t blocks = 0;
+  if (!gsv::dev::mac_launch_shape(first, n, k, total, slice_stride, n_instances, &blocks)) return int(hipErrorInvalidValue);
+  if (n_ct == 0 || block_records % n_ct != 0 || block_records > block_stride || block_first + n < block_first || block_first + n > block_records) return int(hipErrorInvalidValue);
+  if (n == 0) return 0;
+  static std::set<int> attr_done;
+  if (const int rc = gsv::dev::mac_kernel_ready(reinterpret_cast<const void*>(gsv::dev::cbcmac_check_indexed_kernel), attr_done)) return rc;
+  hipLaunchKernelGGL(gsv::dev::cbcmac_check_indexed_kernel, dim3(blocks, n_instances), dim3(GSV_MAC_BLOCK_THREADS), GSV_LDS_TABLE_BYTES, s,
+                     static_cast<const uint32_t*>(te), static_cast<const uint4*>(block), block_stride, static_cast<const uint32_t*>(ct_pos), n_ct, block_first, first, n, k, total,
+                     static_cast<const uint4*>(slice), slice_stride, static_cast<const uint4*>(carry_in), static_cast<uint4*>(carry_out), static_cast<unsigned long long*>(bad));
   return int(hipGetLastError());
 }
 }  // extern "C"

@@ -86,6 +86,21 @@ inline const char* commit_slice_conflict(PassCommit first, PassCommit now) {
   if (has(first | now, PassCommit::MacCheck | PassCommit::Checkpoints)) return "every slice of a pass that writes or checks CBC-MAC checkpoints must ask for the same as its first slice";
   return nullptr;
 }
+// What a streaming EVALUATION asks for, as a set: every slice of a pass asks for the same (EvalCarry::commit holds the first slice's).
+// At most one kind of verification: BLAKE3 outboards from files; outboards in memory, authenticated up front with the last chunks, or
+// at the end of the pass; CBC-MAC checkpoints from files, or in memory (engine_cbcmac.ipp).  A checkpoint pass computes no commitment
+// beside the one it proves: no MAC worker starts and no BLAKE3 digest is taken.
+enum class EvalCommit : uint8_t { None = 0, Mac = 1, B3 = 2, VerifiedFiles = 4, VerifiedUpFront = 8, VerifiedDeferred = 16, CheckpointFiles = 32, CheckpointMemory = 64 };
+constexpr EvalCommit operator|(EvalCommit a, EvalCommit b) { return EvalCommit(uint8_t(a) | uint8_t(b)); }
+constexpr bool has(EvalCommit set, EvalCommit any_of) { return (uint8_t(set) & uint8_t(any_of)) != 0; }
+// The first rule the set `now` breaks behind a pass whose slice at call 0 asked for `first` (first_slice: `now` is that slice), or null
+inline const char* eval_commit_refusal(EvalCommit first, EvalCommit now, bool first_slice) {
+  const EvalCommit checkpoints = EvalCommit::CheckpointFiles | EvalCommit::CheckpointMemory;
+  if (has(now, checkpoints) && (now != EvalCommit::CheckpointFiles && now != EvalCommit::CheckpointMemory))
+    return "a streaming evaluation verified against CBC-MAC checkpoints computes no other commitment and takes no other kind of verification";
+  if (!first_slice && first != now) return "every slice of a streaming evaluation must ask for the same commitments and the same kind of verification as its first slice";
+  return nullptr;
+}
 // Where a drained stream goes (any combination): the per-instance CBC-MAC (AESAccumulatingHash), gc_<index>.bin files, a host callback,
 // the per-instance BLAKE3 tree hash on the device (engine_blake3.ipp) — the one destination for which no ciphertext leaves the device.
 using DrainSinkFn = int (*)(void* user, size_t instance, uint64_t first_record, const uint8_t* records, uint64_t n_records);  // (gsv_ct_sink_fn of include/gsv_engine.h)

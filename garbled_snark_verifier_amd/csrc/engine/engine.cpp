@@ -13,10 +13,10 @@
 //   engine_plan.ipp           gsv_plan_*: built-in builder (single / dual), plan files, background compilation, plan recorder
 //   engine_plan_session.ipp   plan sessions: schedule + device tables, inputs, window launches
 //   engine_blake3.ipp         BLAKE3 commitments: gsv_blake3_*, the device tree hash of segmented streams, B3Receiver: its one single-threaded consumer; FilesOnDevice / StreamsOnDevice: the loops that bring n equally long streams to the device, for this part and the next
-//   engine_cbcmac.ipp         CBC-MAC commitments verified against chain checkpoints (mac_checkpoints.hpp): gsv_cbcmac_file_*, MacCheckReceiver, the device check of segmented streams and of files
+//   engine_cbcmac.ipp         CBC-MAC commitments verified against chain checkpoints (mac_checkpoints.hpp): gsv_cbcmac_file_*, MacCheckReceiver, the device check of segmented streams and of files, the check's half of a restart point
 //   engine_garble_commit.ipp  GarbleCommit: the commitments of one slice of a streaming garbling pass (BLAKE3 state and absorbers, outboards, checkpoint files, the check on the device)
 //   engine_drain.ipp          streaming garbler: the device side of the drain (plan windows, program rings), garble || evaluate, safe-schedule fallback
-//   engine_evaluate.ipp       evaluation: the resident stream, streaming sources (plan ring, plan windows, program rings)
+//   engine_evaluate.ipp       evaluation: the resident stream, streaming sources (plan ring, plan windows, program rings), unverified or verified against BLAKE3 outboards or CBC-MAC checkpoints
 //   engine_readback.ipp       read-back, step clock and step statistics, commitments to the resident stream, CBC-MAC helpers
 // (The parts share file-local helpers and are included in this order inside one extern "C" block; build.py's dependency scan covers them.)
 #include "engine_internal.hpp"

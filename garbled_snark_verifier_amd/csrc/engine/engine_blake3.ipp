@@ -202,11 +202,10 @@ struct EvalRestart {
   std::vector<Blake3Host> hashers;
   std::vector<CbcMacHost> macs;
   uint64_t check_position = 0, windows_launched = 0;
+  bool mac = false;                               // the CBC-MAC check's half below was taken (the pass verifies against checkpoints; engine_cbcmac.ipp, mac_save)
+  DevBuf mac_carry[2];                            // the per-instance carries, 16 bytes each; the failing-group words are all ones at a restart point
+  MacCheckPosition mac_position;                  // ... and the host half (mac_checkpoints.hpp)
 };
-// What a streaming evaluation asks for, as a set: every slice of a pass asks for the same.  At most one of the three kinds of
-// verification: outboards from files; outboards in memory, authenticated up front with the last chunks; or at the end of the pass.
-enum class EvalCommit : uint8_t { None = 0, Mac = 1, B3 = 2, VerifiedFiles = 4, VerifiedUpFront = 8, VerifiedDeferred = 16 };
-constexpr EvalCommit operator|(EvalCommit a, EvalCommit b) { return EvalCommit(uint8_t(a) | uint8_t(b)); }
 struct EvalCarry {
   uint64_t next_call = 0;            // the call the next slice must start with (garbling has a counter of its own: gsv_session::next_call)
   EvalCommit commit = EvalCommit::None;  // what the pass in progress asked for

@@ -6,19 +6,20 @@
 // Soundness: every group starts from the CLAIMED state in front of it, so the groups are independent chains; if all of
 // them arrive at their claimed states, and state -1 is zero, the stream's true CBC-MAC is the last claimed state.  The checkpoint
 // files are untrusted input: a wrong one can only make the check fail.
-struct MacCheckStream {
+struct MacCheckStream : MacCheckPosition {  // (cpar; records_done, fed: records per stream, and segments, enqueued so far)
   size_t n_inst = 0;
   uint32_t k = 0;
   uint64_t total = 0, seg_cap = 0, slice_cap = 0;  // slice_cap: most claimed states per instance a segment touches
   DevBuf slice, carry[2], bad;
   MappedHost<uint8_t> stage[2];                    // the slice of a segment on its way up, [instance][state] dense: ping-pong
   MappedHost<unsigned long long> bad_host[2];      // the failing-group words behind a segment
-  int cpar = 0;
-  uint64_t records_done = 0, fed = 0;              // records per stream, and segments, enqueued so far
 };
 static int check_mac_k(uint32_t k) { return k > MacCheckpoints::MAX_K ? fail(GSV_ERR_INVALID, "GSV_MAC_GROUP_LOG2 must be an integer in [0, 30]") : GSV_OK; }
 // states [s0, s0 + count) of instance i -> dst; s0 = -1: the zero state in front of the stream.  False: they cannot be read.
 using MacStateSource = std::function<bool(size_t i, int64_t s0, uint64_t count, uint8_t* dst)>;
+// A segment that lies in program order (gsv_session_ciphertext_cbcmac_check): records [first, first + n) of the gate-order stream of a
+// block of block_records records, read through the position table (cbcmac_check_indexed_kernel); `buf` is then the block, `stride` its stride
+struct MacIndexed { const void* ct_pos; uint64_t n_ct, block_records, first; };
 
 struct MacCheckReceiver {
   std::unique_ptr<MacCheckStream>& slot;  // the caller's
@@ -49,7 +50,7 @@ struct MacCheckReceiver {
     }
     MacCheckStream& m = *slot;
     m.n_inst = n_inst; m.k = k; m.total = total; m.seg_cap = seg_cap;
-    m.cpar = 0; m.records_done = 0; m.fed = 0;
+    static_cast<MacCheckPosition&>(m) = MacCheckPosition();
     for (int i = 0; i < 2; ++i) { HIPCHK(ev[i].create(hipEventDisableTiming)); in_flight[i] = false; }
     HIPCHK(hipMemsetAsync(m.bad.get(), 0xff, n_inst * 8, st));
     on = true;
@@ -82,21 +83,23 @@ struct MacCheckReceiver {
     return mismatch();
   }
   // the next n records of every stream: buf[inst * stride + r], r < n.  The words of the segment before are looked at once this one is enqueued.
-  int feed(const void* buf, uint64_t stride, uint64_t n, hipStream_t st) {
+  int feed(const void* buf, uint64_t stride, uint64_t n, hipStream_t st, const MacIndexed* ix = nullptr) {
     if (!on || n == 0) return GSV_OK;
     MacCheckStream& m = *slot;
-    if (n > m.seg_cap || m.records_done + n > m.total || n > stride) return fail(GSV_ERR_INVALID, "internal: CBC-MAC check segment outside the stream");
+    if (n > m.seg_cap || m.records_done + n > m.total || (!ix && n > stride)) return fail(GSV_ERR_INVALID, "internal: CBC-MAC check segment outside the stream");
     const int b = int(m.fed & 1);  // (its last upload is two segments old, and the segment before this one was waited for behind it)
     const uint64_t first = m.records_done, n_states = ((first + n - 1) >> m.k) - (first >> m.k) + 2;  // one chain per group the segment touches (cbcmac_device.hpp, mac_chain_count), and one state more
     if (n_states > m.slice_cap) return fail(GSV_ERR_INVALID, "internal: CBC-MAC check slice overflow");
     for (size_t i = 0; i < m.n_inst; ++i)
       if (!states(i, int64_t(first >> m.k) - 1, n_states, m.stage[b].get() + i * size_t(n_states) * 16)) return fail(GSV_ERR_INVALID, std::string("cannot read the checkpoints of ") + noun + " " + std::to_string(i));
     HIPCHK(hipMemcpyAsync(m.slice.get(), m.stage[b].get(), m.n_inst * size_t(n_states) * 16, hipMemcpyHostToDevice, st));
-    if (gsvk_cbcmac_check(te, buf, stride, first, n, m.k, m.total, m.slice.get(), n_states, m.carry[m.cpar].get(), m.carry[m.cpar ^ 1].get(), m.bad.get(), uint32_t(m.n_inst), st) != 0) {
+    const int krc = ix ? gsvk_cbcmac_check_indexed(te, buf, stride, ix->ct_pos, ix->n_ct, ix->block_records, ix->first, first, n, m.k, m.total, m.slice.get(), n_states, m.carry[m.cpar].get(), m.carry[m.cpar ^ 1].get(), m.bad.get(), uint32_t(m.n_inst), st)
+                       : gsvk_cbcmac_check(te, buf, stride, first, n, m.k, m.total, m.slice.get(), n_states, m.carry[m.cpar].get(), m.carry[m.cpar ^ 1].get(), m.bad.get(), uint32_t(m.n_inst), st);
+    if (krc != 0) {
       (void)hipGetLastError();
       return fail(GSV_ERR_DEVICE, "CBC-MAC check kernel launch failed");
     }
-    m.cpar ^= 1; m.records_done += n; ++m.fed;
+    m.advance(n);
     HIPCHK(hipMemcpyAsync(m.bad_host[b].get(), m.bad.get(), m.n_inst * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(ev[b].get(), st));
     in_flight[b] = true;
@@ -112,6 +115,27 @@ struct MacCheckReceiver {
     return GSV_OK;
   }
 };
+
+// The check's state <-> a restart point of a sliced evaluation (EvalRestart, engine_blake3.ipp), through st.  Between two slices nothing
+// is in flight and no group has failed: the device half is the carries (the failing-group words are all ones), the host half the position.
+static int mac_save(const MacCheckStream& m, EvalRestart& r, hipStream_t st) {
+  for (int i = 0; i < 2; ++i) {
+    if (int rc = ensure_dev(r.mac_carry[i], m.n_inst * 16, "a restart point's CBC-MAC carries")) return rc;
+    HIPCHK(hipMemcpyAsync(r.mac_carry[i].get(), m.carry[i].get(), m.n_inst * 16, hipMemcpyDeviceToDevice, st));
+  }
+  r.mac_position = m;
+  r.mac = true;
+  return GSV_OK;
+}
+static int mac_restore(MacCheckStream& m, const EvalRestart& r, hipStream_t st) {
+  for (int i = 0; i < 2; ++i) {
+    if (r.mac_carry[i].bytes() < m.n_inst * 16) return fail(GSV_ERR_INVALID, "internal: a restart point of another CBC-MAC check shape");
+    HIPCHK(hipMemcpyAsync(m.carry[i].get(), r.mac_carry[i].get(), m.n_inst * 16, hipMemcpyDeviceToDevice, st));
+  }
+  HIPCHK(hipMemsetAsync(m.bad.get(), 0xff, m.n_inst * 8, st));  // (the failed slice may have lowered them)
+  static_cast<MacCheckPosition&>(m) = r.mac_position;
+  return GSV_OK;
+}
 
 static uint32_t mac_group_log2_or(uint32_t k) { return k == GSV_MAC_GROUP_DEFAULT ? knobs::mac_group_log2() : k; }
 

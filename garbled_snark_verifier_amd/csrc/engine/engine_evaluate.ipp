@@ -45,6 +45,7 @@ struct EvalPass {
   CtUploader& up;
   uint64_t seg_records;  // per instance: stride of the gate-order buffer
   B3Receiver& b3;        // BLAKE3 of the uploaded segments, when digests were asked for; verified mode: with the instances' outboards
+  MacCheckReceiver& mac; // the CBC-MAC check of the uploaded segments against checkpoints, when the pass verifies that way
   const EvalRange& rg;
   // `n` records per instance starting at stream index `base` -> the gate-order buffer through `st` (bounded page-locked chunks, hashed as read)
   int upload(uint64_t base, uint64_t n, hipStream_t st) {
@@ -57,7 +58,16 @@ struct EvalPass {
     }
   }
   // the `n` records per instance just uploaded to the gate-order buffer through `st`: hashed in front of their scatter
-  int hash(uint64_t n, hipStream_t st) { return b3.feed(s->ct_gate.get(), seg_records, n, st); }
+  int hash(uint64_t n, hipStream_t st) {
+    if (int rc = b3.feed(s->ct_gate.get(), seg_records, n, st)) return rc;
+    return mac.feed(s->ct_gate.get(), seg_records, n, st);
+  }
+  // verified modes, in front of a launch: every group value (BLAKE3) and every failing-group word (CBC-MAC) the segments uploaded so far
+  // have produced is waited for and looked at
+  int verified() {
+    if (b3.check) if (int rc = b3.flush()) return rc;
+    return mac.finish(false);
+  }
 };
 // Plan session over a ciphertext ring: the window (the whole pass) is launched FIRST; its calls wait on the device until the host's
 // position counter says their segment has been uploaded.  Segment after segment: wait until the calls whose blocks this segment's
@@ -110,8 +120,8 @@ static int evaluate_plan_windows(EvalPass& p) {
       if (rc == GSV_OK) rc = p.hash(sg.n_ct, s->e->stream.get());
       if (rc == GSV_OK) rc = permute_plan_calls(s, w, sg.call0, sg.call1, sg.ct0, p.seg_records, 1, nullptr, nullptr, nullptr);
     }
-    // verified mode: every group value the segments uploaded so far have produced is compared before the window that reads them is launched
-    if (rc == GSV_OK && p.b3.check) rc = p.b3.flush();
+    // verified modes: what the segments uploaded so far have produced is compared before the window that reads them is launched
+    if (rc == GSV_OK) rc = p.verified();
     if (rc == GSV_OK) rc = launch_plan_window(s, w, p.gate_id_base, true);
   }
   return rc;
@@ -125,7 +135,7 @@ static int evaluate_program_rings(EvalPass& p) {
     const uint64_t r1 = std::min(total, r0 + seg);
     rc = p.upload(r0 * n_ct, (r1 - r0) * n_ct, s->e->stream.get());
     if (rc == GSV_OK) rc = p.hash((r1 - r0) * n_ct, s->e->stream.get());
-    if (rc == GSV_OK && p.b3.check) rc = p.b3.flush();  // verified mode: compared before the ring is scattered and launched
+    if (rc == GSV_OK) rc = p.verified();  // verified modes: compared before the ring is scattered and launched
     if (rc != GSV_OK) break;
     if (gsvk_gather_segment(s->CT.get(), s->ct_stride(), s->dp->ct_pos.as<const uint32_t>(), n_ct, uint32_t(r1 - r0), uint32_t(s->n_inst), s->ct_gate.get(), p.seg_records, 1, s->e->stream.get()) != 0) { rc = fail(GSV_ERR_DEVICE, "ciphertext scatter launch failed"); break; }
     rc = launch(s, p.gate_id_base, true, r0, r1 - r0);
@@ -144,7 +154,12 @@ static int evaluate_program_rings(EvalPass& p) {
 // A pass in slices (EvalRange): the wire file stays where the previous slice left it, the uploader starts at the slice's first record
 // with the MAC states of the slice before, the B3Stream and the outboard comparison go on where they stood (s->evs); a slice that does
 // not end the pass leaves no group value in flight, gathers no outputs and writes no digests.
-struct EvalVerify { B3Check& check; const uint8_t* expected; uint64_t expected_len; EvalCommit kind; bool no_place = false; };  // kind: which Verified* of EvalCommit; no_place: the mismatch was the digest's, at the end of the pass
+// Verified against CBC-MAC checkpoints (EvalVerify::mac): where the claimed states come from — files or memory, opened and checked by
+// every slice —, their k, the commitments they claim (n_inst x 16) and where the slice that ends the pass writes them (or null)
+struct EvalMacVerify { MacStateSource states; uint32_t k = 0; std::vector<uint8_t> claimed; uint8_t* hashes_out = nullptr; };
+// kind: the verification's member of EvalCommit; no_place: the mismatch was the digest's, at the end of the pass; bad_*: where a stream
+// differs (what gsv_session_mismatch_info reports, and what decides which restart point a failed slice rolls back to)
+struct EvalVerify { B3Check& check; const uint8_t* expected; uint64_t expected_len; EvalCommit kind; bool no_place = false; EvalMacVerify* mac = nullptr; uint64_t bad_instance = 0, bad_group = 0, bad_record = 0; };
 static EvalCarry& eval_carry(gsv_session* s) { if (!s->evs) s->evs.reset(new EvalCarry()); return *s->evs; }
 static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests, EvalVerify* vf, const EvalRange& rg) {
   if (int urc = plan_session_usable(s)) return urc;
@@ -166,18 +181,26 @@ static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, 
     up.start_at(rg.ct0, hashes ? cy.macs : std::vector<CbcMacHost>());
   }
   if (up.alloc() != hipSuccess) return fail(GSV_ERR_DEVICE, "cannot allocate the ciphertext staging buffers");
-  B3Receiver b3(s->b3_eval, "the ciphertext stream of instance", vf ? &vf->check : nullptr);
-  EvalPass p{s, gate_id_base, up, seg_records, b3, rg};
+  B3Receiver b3(s->b3_eval, "the ciphertext stream of instance", vf && !vf->mac ? &vf->check : nullptr);
+  MacCheckReceiver mac(s->mac_eval, "the ciphertext stream of instance", s->e->te.get(), vf && vf->mac ? vf->mac->states : MacStateSource());
+  EvalPass p{s, gate_id_base, up, seg_records, b3, mac, rg};
+  // where the check found a stream that differs, for the caller
+  auto placed = [&](int rc) { if (rc == GSV_ERR_MISMATCH && mac.on) { vf->bad_instance = mac.bad_instance; vf->bad_group = mac.bad_group; vf->bad_record = mac.bad_record; } return rc; };
   // a pass starts the hash afresh, and verifies from group 0 (the pass the safe-schedule fallback repeats too); its later slices go on
   if (digests) {
     const int brc = rg.first ? b3.begin(n_inst, stream_records(s), seg_records, s->pass.b3_subtree_log2) : b3.resume(n_inst, stream_records(s), seg_records, s->pass.b3_subtree_log2);
     if (brc) return brc;
   }
+  // ... and so does the check against checkpoints: its carries and its position live in the session (s->mac_eval)
+  if (vf && vf->mac) {
+    const int mrc = rg.first ? mac.begin(n_inst, stream_records(s), seg_records, vf->mac->k, s->e->stream.get()) : mac.resume(n_inst, stream_records(s), seg_records, vf->mac->k);
+    if (mrc) return mrc;
+  }
   if (s->plan && rg.first) HIPCHK(hipMemsetAsync(s->ps.d_error.get(), 0, 4, s->e->stream.get()));
   HIPCHK(hipEventRecord(s->ev0.get(), s->e->stream.get()));
   int rc = s->plan ? (s->ring() ? evaluate_plan_ring(p) : evaluate_plan_windows(p)) : evaluate_program_rings(p);
   if (hipStreamSynchronize(s->e->stream.get()) != hipSuccess && rc == GSV_OK) rc = fail(GSV_ERR_DEVICE, "kernel failed");
-  if (rc != GSV_OK) return rc;
+  if (rc != GSV_OK) return placed(rc);
   if (s->plan) {
     HIPCHK(hipEventRecord(s->ev1.get(), s->e->stream.get()));
     if (rg.last) { rc = gather_plan_outputs(s, true); if (rc) return rc; }
@@ -193,14 +216,22 @@ static int evaluate_streaming_pass_inner(gsv_session* s, uint64_t gate_id_base, 
     rc = b3.finish(s->e->stream.get(), digests, vf ? vf->expected : nullptr, vf ? vf->expected_len : 0);
     if (rc) { if (vf) vf->no_place = b3.at_end; return rc; }
   } else if (digests) { rc = b3.flush(); if (rc) return rc; }  // the next slice's receiver finds nothing in flight
+  // the check against checkpoints: nothing is in flight between two slices; the slice that ends the pass has seen every group hold, so
+  // the last claimed states are the streams' true CBC-MACs
+  if (mac.on) {
+    rc = mac.finish(rg.last);
+    if (rc) return placed(rc);
+    if (rg.last && vf->mac->hashes_out) std::memcpy(vf->mac->hashes_out, vf->mac->claimed.data(), vf->mac->claimed.size());
+  }
   if (hashes) { cy.macs = up.mac_states(); up.digests(hashes); } else cy.macs.clear();
   return GSV_OK;
 }
 static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, uint8_t* hashes, uint8_t* digests, EvalVerify* vf, const EvalRange& rg) {
   if (vf) clear_mismatch(s);
   const int rc = evaluate_streaming_pass_inner(s, gate_id_base, read, hashes, digests, vf, rg);
-  if (rc == GSV_ERR_MISMATCH) {  // the stream differs from its outboard at the place the check holds
-    set_mismatch(s, vf->check.bad_instance, vf->check.bad_group, vf->check.bad_record);
+  if (rc == GSV_ERR_MISMATCH) {  // the stream differs from its outboard, or from its checkpoints, at the place the check holds
+    if (!vf->mac) { vf->bad_instance = vf->check.bad_instance; vf->bad_group = vf->check.bad_group; vf->bad_record = vf->check.bad_record; }
+    set_mismatch(s, vf->bad_instance, vf->bad_group, vf->bad_record);
     s->ran = false;  // no outputs for a stream that did not verify: gsv_session_read_outputs fails as after a pass that never ran
   }
   return rc;
@@ -208,7 +239,7 @@ static int evaluate_streaming_pass(gsv_session* s, uint64_t gate_id_base, const 
 // ---- restart points (include/gsv_engine.h "Sliced evaluation") ----
 // The session as it stands -> r, in front of the slice `rg`: stream-ordered copies on the engine's stream, which the slice's uploads,
 // scatters and launches follow.  (The slice at call 0 begins the B3Stream afresh: there is no B3 half to keep.)
-static int take_restart_point(gsv_session* s, EvalRestart& r, const EvalRange& rg, bool want_b3) {
+static int take_restart_point(gsv_session* s, EvalRestart& r, const EvalRange& rg, bool want_b3, bool want_mac) {
   EvalCarry& cy = *s->evs;
   const size_t n = s->n_inst, slots = s->prog().n_slots;
   const hipStream_t st = s->e->stream.get();
@@ -223,6 +254,11 @@ static int take_restart_point(gsv_session* s, EvalRestart& r, const EvalRange& r
   if (want_b3 && !rg.first) {
     if (!s->b3_eval) return fail(GSV_ERR_INVALID, "this slice continues a pass whose earlier slices computed no BLAKE3 commitment");
     if (int rc = b3_save(*s->b3_eval, r, st)) return rc;
+  }
+  r.mac = false;  // (likewise: the slice at call 0 begins the check afresh)
+  if (want_mac && !rg.first) {
+    if (!s->mac_eval) return fail(GSV_ERR_INVALID, "this slice continues a pass whose earlier slices ran no CBC-MAC check");
+    if (int rc = mac_save(*s->mac_eval, r, st)) return rc;
   }
   r.macs = rg.first ? std::vector<CbcMacHost>() : cy.macs;
   r.check_position = rg.first ? 0 : cy.check.position();
@@ -253,6 +289,7 @@ static int roll_back(gsv_session* s, const EvalRestart& r) {
     }
   }
   if (r.b3) { if (!s->b3_eval) return fail(GSV_ERR_INVALID, "internal: a restart point without its BLAKE3 stream"); if (int rc = b3_restore(*s->b3_eval, r, st)) return rc; }
+  if (r.mac) { if (!s->mac_eval) return fail(GSV_ERR_INVALID, "internal: a restart point without its CBC-MAC check"); if (int rc = mac_restore(*s->mac_eval, r, st)) return rc; }
   HIPCHK(hipStreamSynchronize(st));
   cy.macs = r.macs; cy.check.rewind(r.check_position);
   s->windows_launched = r.windows_launched;
@@ -273,14 +310,17 @@ static int roll_back(gsv_session* s, const EvalRestart& r) {
 static int check_slice_commit(gsv_session* s, const uint8_t* hashes, const uint8_t* digests, EvalCommit kind, const EvalRange& rg) {
   EvalCarry& cy = eval_carry(s);
   const EvalCommit commit = (hashes ? EvalCommit::Mac : EvalCommit::None) | (digests ? EvalCommit::B3 : EvalCommit::None) | kind;
-  if (!rg.first && commit != cy.commit) return fail(GSV_ERR_INVALID, "every slice of a streaming evaluation must ask for the same commitments and the same kind of verification as its first slice");
+  if (const char* why = eval_commit_refusal(cy.commit, commit, rg.first)) return fail(GSV_ERR_INVALID, why);
   cy.commit = commit;
   return GSV_OK;
 }
 static int evaluate_streaming_impl(gsv_session* s, uint64_t gate_id_base, const std::function<int(size_t, uint64_t, uint8_t*, uint64_t)>& read, uint8_t* hashes, uint8_t* digests, EvalRange rg, bool rereadable = false, EvalVerify* vf = nullptr) {
   EvalCarry& cy = eval_carry(s);
   if (int crc = check_slice_commit(s, hashes, digests, vf ? vf->kind : EvalCommit::None, rg)) return crc;  // (records cy.commit in front of the refusal below, not behind it: a verified slice's entry point has recorded the same value already)
-  if (vf && rg.restartable && rg.ct1 - rg.ct0 < (64ull << s->pass.b3_subtree_log2))
+  if (vf && vf->mac && rg.restartable && rg.ct1 - rg.ct0 < (1ull << vf->mac->k))
+    return fail(GSV_ERR_INVALID, "a verified restartable slice must hold at least one whole group of 2^k records per instance (k = " + std::to_string(vf->mac->k) + " in the checkpoints: " + std::to_string(1ull << vf->mac->k) +
+                                     " records): this one holds " + std::to_string(rg.ct1 - rg.ct0));
+  if (vf && !vf->mac && rg.restartable && rg.ct1 - rg.ct0 < (64ull << s->pass.b3_subtree_log2))
     return fail(GSV_ERR_INVALID, "a verified restartable slice must hold at least one whole group of 2^k chunks per instance (" + std::to_string(64ull << s->pass.b3_subtree_log2) + " records): this one holds " + std::to_string(rg.ct1 - rg.ct0));
   // the restart points: [0] is this slice's, [1] stays the one of the restartable slice before it — unless this is the repeat of a slice
   // the session was rolled back to, whose predecessor's is still the one in [1]
@@ -289,7 +329,7 @@ static int evaluate_streaming_impl(gsv_session* s, uint64_t gate_id_base, const 
   if (rg.first) cy.rp[0].held = cy.rp[1].held = false;
   if (rg.restartable) {
     if (!repeat) std::swap(cy.rp[0], cy.rp[1]);
-    if (int rc = take_restart_point(s, cy.rp[0], rg, digests != nullptr)) { cy.rp[0].held = cy.rp[1].held = false; cy.next_call = 0; return rc; }
+    if (int rc = take_restart_point(s, cy.rp[0], rg, digests != nullptr, vf && vf->mac)) { cy.rp[0].held = cy.rp[1].held = false; cy.next_call = 0; return rc; }
   } else cy.rp[0].held = cy.rp[1].held = false;
   int rc = evaluate_streaming_pass(s, gate_id_base, read, hashes, digests, vf, rg);
   if (rc == GSV_ERR_DEVICE && s->plan && s->dep_fault && !s->safe()) {
@@ -317,7 +357,7 @@ static int evaluate_streaming_impl(gsv_session* s, uint64_t gate_id_base, const 
   else if (rg.restartable && rc == GSV_ERR_MISMATCH && vf && !vf->no_place) {
     // the group that differs may have begun in the slice before (THE GUARANTEE: one open group per instance is evaluated before it is
     // verified): that slice's wire file cannot be trusted either
-    const int which = vf->check.bad_record < rg.ct0 ? 1 : 0;
+    const int which = vf->bad_record < rg.ct0 ? 1 : 0;
     if (cy.rp[which].held) to = &cy.rp[which]; else from_call_0 = true;
     if (to && which == 1) { std::swap(cy.rp[0], cy.rp[1]); cy.rp[1].held = false; to = &cy.rp[0]; }
   }
@@ -514,4 +554,94 @@ int gsv_session_evaluate_streaming_source_calls(gsv_session* s, uint64_t gate_id
   if (int rc = eval_slice_range(s, first_call, n_calls, restartable, &rg)) return rc;
   if (outboards) { if (int rc = check_verified_args(s, expected, expected_len, blake3_digests)) return rc; }
   return evaluate_from_source(s, gate_id_base, source, user, outboards, outboard_bytes, last_chunks, expected, expected_len, cbcmac_hashes, blake3_digests, rg);
+}
+// ---- verified against CBC-MAC checkpoints (include/gsv_engine.h "CBC-MAC checkpoints while evaluating") ----
+// What the two entry points below share once the checkpoints of the slice have been opened (files) or bounds-checked (memory) — both
+// before anything is uploaded and before a source is called: the commitments the checkpoints claim meet the ones the caller trusts (a
+// difference there has no place in the stream) — in EVERY slice, since every slice opens the files or takes the checkpoints anew and
+// the slice that ends the pass returns what IT read —; then the slice runs with the receiver in place of the MAC workers.
+static int evaluate_against_checkpoints(gsv_session* s, uint64_t gate_id_base, const CtUploader::Read& read, EvalMacVerify& mv, EvalCommit kind, const uint8_t* expected, const EvalRange& rg, bool rereadable) {
+  if (rg.first) {
+    clear_mismatch(s);
+    eval_carry(s).resumable = false;
+  }
+  for (size_t i = 0; expected && i < s->n_inst; ++i)
+    if (std::memcmp(mv.claimed.data() + 16 * i, expected + 16 * i, 16) != 0) {
+      set_mismatch(s, i, ~0ull, ~0ull);
+      s->ran = false;
+      eval_carry(s).resumable = false;
+      return fail(GSV_ERR_MISMATCH, "the last checkpoint of instance " + std::to_string(i) + " does not match the commitment");
+    }
+  EvalVerify vf{eval_carry(s).check, nullptr, 0, kind};
+  vf.mac = &mv;
+  return evaluate_streaming_impl(s, gate_id_base, read, nullptr, nullptr, rg, rereadable, &vf);
+}
+// the call range of the two: a program session takes the whole pass only, as gsv_session_garble_streaming_check does
+static int eval_checkpoint_range(gsv_session* s, uint64_t first_call, uint64_t n_calls, int restartable, EvalRange* rg) {
+  if (!s->plan) {
+    if (first_call || n_calls || restartable) return fail(GSV_ERR_INVALID, "program sessions are evaluated in one pass (first_call = n_calls = 0, no restart point)");
+    return eval_whole_range(s, rg);
+  }
+  if (int rc = eval_slice_range(s, first_call, n_calls, restartable, rg)) return rc;
+  return s->ring() ? fail(GSV_ERR_INVALID, VERIFIED_OVER_A_RING) : GSV_OK;
+}
+int gsv_session_evaluate_streaming_mac_calls(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, int restartable, const char* dir, const uint64_t* indexes, uint64_t first_index,
+                                             const char* checkpoint_dir, const uint8_t* expected, uint8_t* cbcmac_hashes) {
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
+  if (!s || !dir || !checkpoint_dir || !cbcmac_hashes) return fail(GSV_ERR_INVALID, "null argument");
+  EvalRange rg;
+  if (int rc = eval_checkpoint_range(s, first_call, n_calls, restartable, &rg)) return rc;
+  if (int rc = check_slice_commit(s, nullptr, nullptr, EvalCommit::CheckpointFiles, rg)) return rc;
+  auto index = [&](size_t i) { return indexes ? indexes[i] : first_index + i; };
+  GcFileSource files;
+  std::string why;
+  std::vector<std::string> names(s->n_inst);
+  std::vector<const char*> ptrs(s->n_inst);
+  for (size_t i = 0; i < s->n_inst; ++i) {
+    if (!files.add(std::string(dir) + "/gc_" + std::to_string(index(i)) + ".bin", &why)) return fail(GSV_ERR_INVALID, why);
+    names[i] = CheckpointWriter::path(checkpoint_dir, index(i)); ptrs[i] = names[i].c_str();
+  }
+  // the checkpoint files are opened and validated by every slice (headers, lengths, the session's stream length); they are never held whole
+  const uint64_t records = stream_records(s);
+  std::vector<MacCheckpointFile> cks;
+  if (!open_mac_checkpoints(ptrs.data(), s->n_inst, &records, &cks, &why)) return fail(GSV_ERR_INVALID, why);
+  EvalMacVerify mv;
+  mv.k = cks[0].head.k; mv.hashes_out = cbcmac_hashes;
+  mv.claimed.resize(s->n_inst * 16);
+  for (size_t i = 0; i < s->n_inst; ++i) if (!cks[i].commitment(mv.claimed.data() + 16 * i)) return fail(GSV_ERR_INVALID, "read error on " + cks[i].path());
+  mv.states = [&cks](size_t i, int64_t s0, uint64_t count, uint8_t* dst) { return cks[i].read_states(s0, count, dst); };
+  return evaluate_against_checkpoints(s, gate_id_base, [&](size_t i, uint64_t first, uint8_t* dst, uint64_t n) { return files.read(i, first, dst, n); }, mv, EvalCommit::CheckpointFiles, expected, rg, /*rereadable=*/true);
+}
+int gsv_session_evaluate_streaming_source_mac_calls(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, int restartable, gsv_ct_source_fn source, void* user,
+                                                    const uint8_t* const* checkpoints, const uint64_t* checkpoint_bytes, const uint8_t* expected, uint8_t* cbcmac_hashes) {
+  PassGuard pass_guard(s);  // destroys requested while this pass runs wait for its end (deferred release)
+  if (!s || !source || !checkpoints || !checkpoint_bytes || !cbcmac_hashes) return fail(GSV_ERR_INVALID, "null argument");
+  EvalRange rg;
+  if (int rc = eval_checkpoint_range(s, first_call, n_calls, restartable, &rg)) return rc;
+  if (int rc = check_slice_commit(s, nullptr, nullptr, EvalCommit::CheckpointMemory, rg)) return rc;
+  // the host hands the checkpoints in with every slice, and every slice bounds-checks them again (as the in-memory outboards)
+  const uint64_t records = stream_records(s);
+  EvalMacVerify mv;
+  mv.hashes_out = cbcmac_hashes;
+  mv.claimed.assign(s->n_inst * 16, 0);
+  std::string why;
+  for (size_t i = 0; i < s->n_inst; ++i) {
+    const std::string who = "checkpoints[" + std::to_string(i) + "]: ";
+    MacCheckpoints h;
+    if (!checkpoints[i]) return fail(GSV_ERR_INVALID, who + "null");
+    if (!MacCheckpoints::parse_header(checkpoints[i], checkpoint_bytes[i], &h, &why)) return fail(GSV_ERR_INVALID, who + why);
+    if (h.n_records != records) return fail(GSV_ERR_INVALID, who + "for a stream of " + std::to_string(h.n_records) + " records, the stream here holds " + std::to_string(records));
+    if (i && h.k != mv.k) return fail(GSV_ERR_INVALID, "the checkpoints of one call must agree on k: checkpoints[0] has " + std::to_string(mv.k) + ", checkpoints[" + std::to_string(i) + "] has " + std::to_string(h.k));
+    if (!h.length_ok(checkpoint_bytes[i], &why)) return fail(GSV_ERR_INVALID, who + why);
+    mv.k = h.k;
+    if (h.states()) std::memcpy(mv.claimed.data() + 16 * i, checkpoints[i] + MacCheckpoints::HEADER_BYTES + (h.states() - 1) * 16, 16);
+  }
+  const uint64_t n_states = MacCheckpoints::state_count(records, mv.k);
+  mv.states = [checkpoints, n_states](size_t i, int64_t s0, uint64_t count, uint8_t* dst) {
+    if (count && s0 < 0) { std::memset(dst, 0, 16); dst += 16; ++s0; --count; }
+    if (uint64_t(s0) + count > n_states) return false;
+    std::memcpy(dst, checkpoints[i] + MacCheckpoints::HEADER_BYTES + uint64_t(s0) * 16, size_t(count) * 16);
+    return true;
+  };
+  return evaluate_against_checkpoints(s, gate_id_base, source_reader(source, user), mv, EvalCommit::CheckpointMemory, expected, rg, /*rereadable=*/false);
 }

@@ -267,6 +267,7 @@ struct gsv_session {
   std::unique_ptr<MacCheckStream> mac_check;  // the CBC-MAC check of a garbling pass against checkpoint files (engine_cbcmac.ipp): device buffers, carries, position — beside `b3`, chained from slice to slice
   uint32_t mck_k = 0;                  // log2 of the group size of the checkpoint files the pass in progress writes (GSV_MAC_GROUP_LOG2 when its first slice began)
   std::unique_ptr<B3Stream> b3_eval;   // ... of the streams a streaming evaluation reads (gsv_session_evaluate_streaming*_commit): apart from `b3`, which a garbling pass chains from slice to slice
+  std::unique_ptr<MacCheckStream> mac_eval;  // ... and the CBC-MAC check of the streams a streaming evaluation reads, against checkpoints (gsv_session_evaluate_streaming_mac_calls): apart from `mac_check`, as b3_eval from b3
   std::unique_ptr<EvalCarry> evs;      // a streaming evaluation in slices: next call, MAC states, outboards, restart points (engine_blake3.ipp; created on first use)
   // verified streaming evaluation (gsv_session_evaluate_streaming_verified): where the last such pass found a stream that differs from its outboard
   bool mismatch = false;

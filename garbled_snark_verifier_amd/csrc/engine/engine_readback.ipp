@@ -167,6 +167,78 @@ int gsv_session_ciphertext_blake3(gsv_session* s, uint8_t* digests) {
   if (rc) return rc;
   return s->plan ? check_plan_error(s) : GSV_OK;  // (behind an asynchronous garble: a pass whose dependency wait gave up left no stream to commit to)
 }
+// The retained stream of every instance verified against checkpoint files where it lies (cbcmac_device.hpp, cbcmac_check_indexed_kernel):
+// gsv_session_ciphertext_blake3's ranges — at most GSV_MAC_RESIDENT_RECORDS records per instance, of the one ring or of one call block
+// after the other; groups straddle ranges and blocks through the carry — fed to the receiver of gsv_session_garble_streaming_check.
+int gsv_session_ciphertext_cbcmac_check(gsv_session* s, const char* checkpoint_dir, const uint64_t* indexes, uint64_t first_index, const uint8_t* expected, uint8_t* hashes) {
+  if (!s || !checkpoint_dir || !hashes) return fail(GSV_ERR_INVALID, "null argument");
+  const knobs::ResidentMac kn;
+  if (s->ct_cap != s->replays || (s->plan && !s->retain())) return fail(GSV_ERR_INVALID, "the session retains only part of the stream (ct_capacity_replays < replays)");
+  const uint64_t total = s->ct_stride();
+  if (int rc = check_resident_stream(s, total)) return rc;
+  const size_t n = s->n_inst;
+  std::vector<std::string> names(n);
+  std::vector<const char*> ptrs(n);
+  for (size_t i = 0; i < n; ++i) { names[i] = CheckpointWriter::path(checkpoint_dir, indexes ? indexes[i] : first_index + i); ptrs[i] = names[i].c_str(); }
+  std::string why;
+  std::vector<MacCheckpointFile> cks;
+  if (!open_mac_checkpoints(ptrs.data(), n, &total, &cks, &why)) return fail(GSV_ERR_INVALID, why);
+  clear_mismatch(s);
+  // the commitments the files claim: compared with the ones the caller trusts before anything is launched
+  std::vector<uint8_t> claimed(n * 16);
+  for (size_t i = 0; i < n; ++i) {
+    if (!cks[i].commitment(claimed.data() + 16 * i)) return fail(GSV_ERR_INVALID, "read error on " + cks[i].path());
+    if (expected && std::memcmp(claimed.data() + 16 * i, expected + 16 * i, 16) != 0) {
+      set_mismatch(s, i, ~0ull, ~0ull);
+      return fail(GSV_ERR_MISMATCH, "the last checkpoint of instance " + std::to_string(i) + " does not match the commitment");
+    }
+  }
+  HIPCHK(hipSetDevice(s->e->device));
+  const uint32_t k = cks[0].head.k;
+  uint64_t cap = kn.resident_records;
+  if (!cap) {
+    // only the slice of claimed states has to fit: (cap >> k) + 3 states of 16 bytes per instance, once on the device and twice
+    // page-locked on the host (MacCheckReceiver::begin) — the three together in a tenth of what is free on the device
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t states = uint64_t(free_b) / 10 / (3 * 16 * n);
+    cap = std::min<uint64_t>(64ull << 20, states > 3 ? std::min<uint64_t>(states - 3, 64ull << 20) << k : 1);
+  }
+  cap = std::min(cap, std::max<uint64_t>(total, 1));
+  const hipStream_t st = s->e->stream.get();
+  std::unique_ptr<MacCheckStream> slot;
+  MacCheckReceiver rx(slot, "the ciphertext stream of instance", s->e->te.get(), [&cks](size_t i, int64_t s0, uint64_t count, uint8_t* dst) { return cks[i].read_states(s0, count, dst); });
+  struct Quiesce { hipStream_t st; ~Quiesce() { (void)hipStreamSynchronize(st); } } quiesce{st};  // declared after `slot`: nothing of its buffers is in flight when they go
+  int rc = rx.begin(n, total, cap, k, st);
+  if (rc) return rc;
+  // records [first, first + m) of the gate-order stream of one block (block_off records into every instance's stream, whole replays of n_ct records)
+  auto feed = [&](uint64_t block_off, const DevBuf& ct_pos, uint64_t n_ct, uint64_t block_records) -> int {
+    for (uint64_t first = 0; first < block_records; first += cap) {
+      const MacIndexed ix{ct_pos.get(), n_ct, block_records, first};
+      if (int frc = rx.feed(static_cast<const uint8_t*>(s->CT.get()) + block_off * 16, s->ct_stride(), std::min(cap, block_records - first), st, &ix)) return frc;
+    }
+    return GSV_OK;
+  };
+  if (!s->plan) rc = total ? feed(0, s->dp->ct_pos, s->prog().n_ct, total) : GSV_OK;
+  else
+    for (size_t c = 0; c < s->plan->calls.size() && rc == GSV_OK; ++c) {
+      const uint64_t n_ct = s->call_prog(c).n_ct;
+      if (n_ct) rc = feed(s->plan->calls[c].ct_off, s->call_dev[c]->ct_pos, n_ct, n_ct);
+    }
+  if (rc == GSV_OK) rc = rx.finish();
+  // behind an asynchronous garble: a pass whose dependency wait gave up left no stream to verify — that is the error to report, not
+  // the mismatch the check finds in what the pass left behind (finish() has waited for the stream up to the last failing-group word)
+  if (s->plan && (rc == GSV_OK || rc == GSV_ERR_MISMATCH)) {
+    const std::string found = g_err;
+    HIPCHK(hipStreamSynchronize(st));
+    if (int prc = check_plan_error(s)) return prc;
+    if (rc) g_err = found;
+  }
+  if (rc == GSV_ERR_MISMATCH) set_mismatch(s, rx.bad_instance, rx.bad_group, rx.bad_record);
+  if (rc) return rc;
+  std::memcpy(hashes, claimed.data(), claimed.size());
+  return GSV_OK;
+}
 int gsv_cbcmac_chains_per_step(void) { return CbcMacHost::have_vaes() ? 16 : GSV_HOST_AESNI ? 4 : 1; }
 int gsv_cbcmac_update_many(uint8_t* states, const uint8_t* const* cts, size_t n_chains, uint64_t n_records) {
   if ((!states || !cts) && n_chains) return fail(GSV_ERR_INVALID, "null argument");

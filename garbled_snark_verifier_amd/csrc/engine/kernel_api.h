@@ -124,4 +124,9 @@ int gsvk_b3_reduce(void* cv, uint64_t cv_stride, uint32_t n_have, uint32_t k, vo
 // bad[inst]: a 64-bit word the kernel lowers to the lowest group that does not hold
 int gsvk_cbcmac_check(const void* te, const void* seg, uint64_t seg_stride, uint64_t first, uint64_t n, uint32_t k, uint64_t total, const void* slice, uint64_t slice_stride,
                       const void* carry_in, void* carry_out, void* bad, uint32_t n_instances, hipStream_t s);
+// the same with the records read where a resident stream lies: record q of the segment is record p = block_first + q of the gate-order
+// stream of block[inst], i.e. block[inst][(p / n_ct) * n_ct + ct_pos[p % n_ct]] (block_stride in records; block_records: whole replays of
+// n_ct records, and the segment must lie inside them).  The block is only read.
+int gsvk_cbcmac_check_indexed(const void* te, const void* block, uint64_t block_stride, const void* ct_pos, uint64_t n_ct, uint64_t block_records, uint64_t block_first, uint64_t first, uint64_t n,
+                              uint32_t k, uint64_t total, const void* slice, uint64_t slice_stride, const void* carry_in, void* carry_out, void* bad, uint32_t n_instances, hipStream_t s);
 }

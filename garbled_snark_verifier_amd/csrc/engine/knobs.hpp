@@ -58,6 +58,9 @@
 // -- a knobs::ResidentB3 at gsv_session_ciphertext_blake3 (with GSV_B3_SUBTREE_LOG2)
 // GSV_B3_RESIDENT_RECORDS     int      by free memory       gsv_session_ciphertext_blake3          most records per instance one launch range of the resident hash covers
 //                                                                                                    (default: the two chunk-value buffers take <= 1/10 of the free memory, <= 64 M records)
+// -- a knobs::ResidentMac at gsv_session_ciphertext_cbcmac_check (k comes from the checkpoint files)
+// GSV_MAC_RESIDENT_RECORDS    int      by free memory       gsv_session_ciphertext_cbcmac_check    most records per instance one launch range of the resident check covers
+//                                                                                                    (default: the slices of claimed states take <= 1/10 of the free memory, <= 64 M records)
 #pragma once
 #include <algorithm>  // (with <initializer_list>)
 #include <cstdlib>
@@ -130,5 +133,8 @@ struct Pass {
 struct ResidentB3 {
   uint32_t b3_subtree_log2 = knobs::b3_subtree_log2();
   uint64_t resident_records = at_least_1("GSV_B3_RESIDENT_RECORDS");  // 0 = by free memory
+};
+struct ResidentMac {
+  uint64_t resident_records = at_least_1("GSV_MAC_RESIDENT_RECORDS");  // 0 = by free memory
 };
 }  // namespace gsv::knobs

@@ -65,6 +65,15 @@ struct MacCheckpoints {
   }
 };
 
+// The host's half of a device check between two segments (MacCheckStream, engine_cbcmac.ipp): which of the two carry buffers the next
+// segment reads, how many records of every stream and how many segments have been enqueued.  Plain values: what a restart point of a
+// sliced evaluation keeps beside the carries themselves, and puts back.
+struct MacCheckPosition {
+  int cpar = 0;
+  uint64_t records_done = 0, fed = 0;
+  void advance(uint64_t n) { cpar ^= 1; records_done += n; ++fed; }  // a segment of n records per stream has been enqueued
+};
+
 // A checkpoint file that is open and has passed the header and length checks.  It is never held whole: state ranges are read as they
 // are needed (1 024 instances x a 47 GB stream at k = 0 would be terabytes; even at k = 12 the files of a call are better left on disk).
 class MacCheckpointFile {

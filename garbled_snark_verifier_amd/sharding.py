@@ -393,7 +393,29 @@ class ConsistencyError(Exception):
         self.kind, self.index, self.details = kind, index, details
 
 
-def _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment="cbcmac", outboard_dir=None):
+def _last_checkpoint(path, n_records):
+    """The commitment a CBC-MAC checkpoint file claims for a stream of n_records records: its last state, sixteen zero bytes for the
+    empty stream.  The file is not read whole (2^-k of the stream: large at small k): its byte length comes from the engine
+    (cbcmac_checkpoints_size, the one place that knows the format) for the k the header names, and the last 16 bytes are read."""
+    import os
+    from . import cbcmac_checkpoints_size
+    with open(path, "rb") as f:
+        head = f.read(24)
+        size = os.fstat(f.fileno()).st_size
+        if len(head) < 24 or head[:8] != b"GSVMACK\n" or int.from_bytes(head[8:12], "little") != 1:
+            raise ValueError("%s is not a version 1 checkpoint file" % path)
+        k, n = int.from_bytes(head[12:16], "little"), int.from_bytes(head[16:24], "little")
+        if n != n_records:
+            raise ValueError("%s holds the checkpoints of a stream of %d records, the stream here holds %d" % (path, n, n_records))
+        if k > 30 or size != cbcmac_checkpoints_size(n, k):
+            raise ValueError("%s: k = %d and n_records = %d do not make %d bytes" % (path, k, n, size))
+        if n == 0:
+            return bytes(16)
+        f.seek(size - 16)
+        return f.read(16)
+
+
+def _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment="cbcmac", outboard_dir=None, checkpoint_dir=None):
     """Default evaluation backend of evaluate_from: EvaluateMode over FileSources on the GPU, ALL finalized instances in one session —
     one launch per window of the stream for the whole batch (gsv_session_evaluate_streaming_indexed).  The reference evaluates the
     cases side by side on a rayon pool (`into_par_iter`, cut_and_choose/evaluator.rs:354-475); a one-instance session per case would
@@ -401,7 +423,8 @@ def _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment="cbcmac", o
     worker i mod T of the engine's pool, beside the uploads (engine.cpp, evaluate_streaming_impl).  commitment="blake3": the hash of a
     case is the first 16 bytes of its file's BLAKE3 digest instead, computed on the device from the uploaded segments (no MAC worker).
     outboard_dir: verified streaming — `run` then takes expected= (the committed 16-byte hashes) and raises CiphertextMismatch, with the
-    position in the batch as its instance, at the first group that differs from its outboard."""
+    position in the batch as its instance, at the first group that differs from its outboard.  checkpoint_dir (commitment="cbcmac"):
+    the same against the CBC-MAC checkpoint files gc_<i>.mck of that directory, on the device and without MAC workers."""
     from . import Engine, Plan, Program, Session
     _check_commitment(commitment)
     eng = engine or Engine(0)
@@ -414,6 +437,8 @@ def _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment="cbcmac", o
             consts = np.stack([np.asarray(false_active, np.uint8).reshape(B, 16), np.asarray(true_active, np.uint8).reshape(B, 16)], axis=1)
             sess.set_evaluate_inputs(consts, np.asarray(input_active, np.uint8).reshape(B, -1, 16), np.asarray(input_bits, np.uint8).reshape(B, -1))
             kw = {"outboard_dir": outboard_dir, "expected": expected} if outboard_dir is not None else {}
+            if checkpoint_dir is not None:
+                kw = {"checkpoint_dir": checkpoint_dir, "expected": expected}
             hashes = [h[:16] for h in sess.evaluate_streaming_indexed(gc_dir, [int(i) for i in indexes], commitment=commitment, **kw)]
             labels, bits = sess.read_outputs(with_bits=True)
             return [(labels[k], bits[k], hashes[k]) for k in range(B)]
@@ -422,7 +447,7 @@ def _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment="cbcmac", o
     return run
 
 
-def evaluate_from(commits, cases, circuit, gc_dir, n_outputs, engine=None, program=None, evaluate=None, evaluate_batch=None, commitment="cbcmac", outboard_dir=None):
+def evaluate_from(commits, cases, circuit, gc_dir, n_outputs, engine=None, program=None, evaluate=None, evaluate_batch=None, commitment="cbcmac", outboard_dir=None, checkpoint_dir=None):
     """Evaluator::evaluate_from (cut_and_choose/evaluator.rs:338-476): evaluate the finalized instances from their gc_<i>.bin and
     check everything the evaluator was handed against the garbler's commit record BEFORE trusting the result.
     `cases`: list of dicts {index, true_constant_wire[16], false_constant_wire[16], input_active[n_in,16], input_bits[n_in]}
@@ -444,12 +469,19 @@ def evaluate_from(commits, cases, circuit, gc_dir, n_outputs, engine=None, progr
     evaluator stops at the first group of 2^k chunks that differs from its outboard (Session.evaluate_streaming_indexed(outboard_dir=,
     expected=)).  Either is ConsistencyError("CiphertextMismatch", index) with the group in its message; the checks of the cases in
     front of that one which need no evaluation still come first.  With a stand-in the up-front check runs here on the host, and the
-    stand-in may raise CiphertextMismatch itself (a batch stand-in: with the position in the batch as its instance)."""
+    stand-in may raise CiphertextMismatch itself (a batch stand-in: with the position in the batch as its instance).
+    checkpoint_dir (with commitment="cbcmac"): the garbler's CBC-MAC checkpoint files gc_<i>.mck lie there and the evaluation is
+    VERIFIED in the same way against them — each file's last state must be the committed hash before anything is evaluated, and the
+    default GPU evaluator stops at the first group of 2^k records that does not arrive at its claimed state
+    (Session.evaluate_streaming_indexed(checkpoint_dir=, expected=)), with no MAC worker on the host.  The errors, their order and
+    the stand-ins' part are those of outboard_dir."""
     import os
-    from . import CiphertextMismatch, blake3_outboard_root, gc_file_name, outboard_file_name
+    from . import CiphertextMismatch, blake3_outboard_root, checkpoint_file_name, gc_file_name, outboard_file_name
     _check_commitment(commitment)
     if outboard_dir is not None and commitment != "blake3":
         raise ValueError("outboard_dir needs commitment='blake3'")
+    if checkpoint_dir is not None and commitment != "cbcmac":
+        raise ValueError("checkpoint_dir needs commitment='cbcmac'")
     commits = np.asarray(commits, np.uint8)
     gpu_default = evaluate_batch is None and evaluate is None
     if evaluate_batch is None:
@@ -463,7 +495,7 @@ def evaluate_from(commits, cases, circuit, gc_dir, n_outputs, engine=None, progr
                         raise CiphertextMismatch(str(e), k, e.group, e.first_record)
                 return out
         else:
-            evaluate_batch = _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment, outboard_dir)
+            evaluate_batch = _gpu_evaluate_batch(circuit, engine, program, gc_dir, commitment, outboard_dir, checkpoint_dir)
     n_in_committed = (commits.shape[1] - record_len(n_outputs, 0)) // 32
     parsed, first_error = [], None
     for case in cases:
@@ -510,8 +542,16 @@ def evaluate_from(commits, cases, circuit, gc_dir, n_outputs, engine=None, progr
                 raise ciphertext_mismatch(pos, outboard=str(e))
             if root[:16] != bytes(c[5]):
                 raise ciphertext_mismatch(pos, outboard="outboard or last chunk does not match the commitment")
+    if parsed and checkpoint_dir is not None and not gpu_default:
+        for pos, c in enumerate(parsed):  # (likewise: each file's last state against the record's hash)
+            try:
+                claimed = _last_checkpoint(os.path.join(checkpoint_dir, checkpoint_file_name(c[0])), os.path.getsize(os.path.join(gc_dir, gc_file_name(c[0]))) // 16)
+            except Exception as e:  # noqa: BLE001 - no checkpoint file, or a malformed one
+                raise ciphertext_mismatch(pos, checkpoints=str(e))
+            if claimed != bytes(c[5]):
+                raise ciphertext_mismatch(pos, checkpoints="the last checkpoint does not match the commitment")
     if parsed:
-        kw = {"expected": [bytes(c[5]) for c in parsed]} if gpu_default and outboard_dir is not None else {}
+        kw = {"expected": [bytes(c[5]) for c in parsed]} if gpu_default and (outboard_dir is not None or checkpoint_dir is not None) else {}
         try:
             evaluated = evaluate_batch([c[0] for c in parsed], np.stack([c[1] for c in parsed]), np.stack([c[2] for c in parsed]),
                                        np.stack([c[3] for c in parsed]), np.stack([c[4] for c in parsed]), **kw)

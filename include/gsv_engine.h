@@ -782,6 +782,65 @@ int gsv_session_evaluate_streaming_source_calls(gsv_session* s, uint64_t gate_id
                                                 uint8_t* cbcmac_hashes /* or NULL */, uint8_t* blake3_digests /* or NULL; required when verified */);
 int gsv_session_evaluate_resume_info(const gsv_session* s, uint64_t* next_call, uint64_t* next_record);
 
+/* ---- CBC-MAC checkpoints while evaluating ------------------------------------------------------------------------------------------
+ * The streaming evaluators verified against the checkpoints of "CBC-MAC checkpoints" instead of folding the chains on host MAC
+ * workers: the commitment stays the reference's AESAccumulatingHash, a bad file is found at the launch that would read it, the place
+ * is named, and a slice can be repeated.  Two calls, the mirrors of gsv_session_evaluate_streaming_calls / _source_calls: over
+ * <dir>/gc_<index>.bin with <checkpoint_dir>/gc_<index>.mck (index = indexes ? indexes[i] : first_index + i), and over the generic
+ * source with the checkpoint files in memory (checkpoints[i], checkpoint_bytes[i]: byte for byte a gc_<i>.mck).  first_call = n_calls
+ * = 0 is the whole pass — the only form a PROGRAM session accepts, where `restartable` is refused too (GSV_ERR_INVALID).
+ *
+ * Every uploaded segment is checked in its gate-order buffer, on the stream that scatters it and in front of the scatter; no MAC
+ * worker starts.  k and n_records come from the checkpoints, never from a knob.
+ * CHECKPOINTS ARE UNTRUSTED INPUT and go through the parsing above: a wrong magic, version, k or byte length, an n_records other than
+ * the session's stream length, or checkpoints of one call that disagree are GSV_ERR_INVALID with a message that names what is wrong —
+ * before anything is uploaded and before the source is called at all.  Files are opened and validated by every slice and never held
+ * whole; in-memory checkpoints are handed in, and bounds-checked, again with every slice.
+ * With `expected` (n x 16) every instance's last state is compared with the commitment the caller trusts, in every slice (each reads
+ * the checkpoints anew) and before anything of the slice is uploaded: a difference is GSV_ERR_MISMATCH without a place
+ * (gsv_session_mismatch_info gives UINT64_MAX), the slice has not run and nothing is there to resume.  Without `expected` comparing the
+ * returned cbcmac_hashes with the commitments is the caller's part.
+ *
+ * THE GUARANTEE, as for the BLAKE3 outboards.  Before a window — or a program session's ring — is launched, the failing-group words
+ * of every segment uploaded so far have been waited for and looked at.  The one group per instance that is still open at a launch is
+ * evaluated before it is verified; every other record a launch reads has been verified first.  No output is ever returned for a
+ * stream that did not verify.
+ * On GSV_ERR_MISMATCH nothing further is pulled from the source or launched; gsv_session_mismatch_info names the instance, the group
+ * and the group's first record (group << k); gsv_session_read_outputs fails as after a pass that never ran; cbcmac_hashes is untouched.
+ * cbcmac_hashes (n x 16, required) is written only by the slice that ends the pass, when every group held: the last claimed states,
+ * which by then are the streams' true CBC-MACs.
+ *
+ * Slices follow "Sliced evaluation".  Every slice of a pass must ask for the same kind of verification — checkpoints from files and
+ * checkpoints in memory are two kinds, and neither mixes with the BLAKE3 kinds or with an unverified slice (GSV_ERR_INVALID).  A
+ * restart point also keeps the check's state: the per-instance carries (16 bytes each; the failing-group words are all ones between
+ * two slices) as stream-ordered copies, and the position.  THE OPEN GROUP rule is the one stated there; a verified restartable slice
+ * must hold at least one whole group, 2^k records per instance with the k of the checkpoints, else GSV_ERR_INVALID.  A short file or
+ * a dry source (GSV_ERR_EXHAUSTED) rolls a restartable slice back as ever.
+ * Plan sessions over a ciphertext ring (retain_stream = GSV_STREAM_RING) are refused with GSV_ERR_INVALID, for the reason given for
+ * verified BLAKE3 evaluation: their pass is one launch that waits on the device for the host's stream position.
+ * Safe-schedule fallback: as for verified BLAKE3 evaluation — a repeated pass verifies from group 0 again, a restartable slice over
+ * files is repeated alone from its restart point. */
+int gsv_session_evaluate_streaming_mac_calls(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, int restartable,
+                                             const char* dir, const uint64_t* indexes /* NULL: first_index + i */, uint64_t first_index,
+                                             const char* checkpoint_dir, const uint8_t* expected /* n x 16 or NULL */, uint8_t* cbcmac_hashes /* n x 16 */);
+int gsv_session_evaluate_streaming_source_mac_calls(gsv_session* s, uint64_t gate_id_base, uint64_t first_call, uint64_t n_calls, int restartable,
+                                                    gsv_ct_source_fn source, void* user,
+                                                    const uint8_t* const* checkpoints, const uint64_t* checkpoint_bytes,
+                                                    const uint8_t* expected /* n x 16 or NULL */, uint8_t* cbcmac_hashes /* n x 16 */);
+/* The RESIDENT stream checked where it lies: gsv_session_ciphertext_hash fetches a retained stream and folds it serially, one instance
+ * at a time; this verifies every instance's retained stream against <checkpoint_dir>/gc_<index>.mck in program order, through the
+ * position table (the mapping of gsv_session_ciphertext_blake3), and nothing of the stream is copied or moved.  For sessions that
+ * retain the whole stream — program sessions with ct_capacity_replays == replays, plan sessions with retain_stream = 1 — after
+ * gsv_session_garble or after gsv_session_upload_ciphertexts; the refusals of gsv_session_ciphertext_blake3 apply (a partly retained
+ * stream: GSV_ERR_INVALID; an upload that does not cover the stream: GSV_ERR_EXHAUSTED).  At most GSV_MAC_RESIDENT_RECORDS records per
+ * instance and launch (default: by free device memory — only the slice of claimed states has to fit), plan sessions call block after
+ * call block; groups straddle ranges and blocks through the carry.  The checkpoint files are untrusted input, validated as above.
+ * With `expected` (n x 16) the files' last states are compared first: GSV_ERR_MISMATCH without a place.  A group that does not hold is
+ * GSV_ERR_MISMATCH, and gsv_session_mismatch_info names the instance, the group and its first record.  hashes (n x 16) is written only
+ * when everything held.  The empty stream's commitment is sixteen zero bytes. */
+int gsv_session_ciphertext_cbcmac_check(gsv_session* s, const char* checkpoint_dir, const uint64_t* indexes /* NULL: first_index + i */, uint64_t first_index,
+                                        const uint8_t* expected /* n x 16 or NULL */, uint8_t* hashes /* n x 16 */);
+
 #ifdef __cplusplus
 }
 #endif
